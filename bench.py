@@ -10,12 +10,16 @@ all queries, one all-reduce(min) of Q packed keys -- issued by libganleaks_hip.s
 context's stream); torch.distributed is the launcher's rendezvous only (gloo: carries the RCCL unique id, the barrier and the
 max-over-ranks of the timing).
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (fields: see the project brief); progress goes to stderr.  With the default flags on one GPU the line
-also carries two further measurements of the same run:
+Prints ONE JSON line on rank 0 (fields: see the project brief); progress goes to stderr.  A plain run sets up, warms up, times the K
+steps and prints the line; its roofline, kernels and phases come from the library's HIP events inside those same timed steps.
+--dump-outputs DIR writes what the last timed step returned to the host, dist[Q] and idx[Q], as DIR/dist.npy (float32) and DIR/idx.npy
+(float64); the inputs are seeded, so two builds can be compared output for output.
+--full adds everything that takes work of its own: the oracle parity check, the AUROC, the CPU baseline and, with the default flags on
+one GPU, live PMC traffic passes, BASELINE configs[0] ("config0") and two further measurements:
     "secondary"       BASELINE configs[2]: the same 10k x 100k problem under the reference's own fbb distance 0.2*LPIPS + L2
                       (attack_models/fbb.py:148), with its own roofline, parity block and cpu_baseline
     "secondary_fp32"  the headline workload with strict fp32 MFMA products in the generator (--gen-precision 0)
@@ -45,6 +49,21 @@ D = 3 * 64 * 64
 
 def log(*a):
     print(*a, file=sys.stderr, flush=True)
+
+
+DUMP_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, dist, idx):
+    """dist[Q] (float32) and idx[Q] (float64, exact below 2^53) as out_dir/{dist,idx}.npy.  Above DUMP_BYTES a fixed seeded sample of the
+    queries is written, with its query numbers in out_dir/query.npy."""
+    os.makedirs(out_dir, exist_ok=True)
+    sel = np.arange(len(dist))
+    if len(dist) * 12 > DUMP_BYTES:
+        sel = np.sort(np.random.default_rng(0).choice(len(dist), DUMP_BYTES // 20, replace=False))
+        np.save(os.path.join(out_dir, "query.npy"), sel.astype(np.float64))
+    np.save(os.path.join(out_dir, "dist.npy"), dist[sel].astype(np.float32))
+    np.save(os.path.join(out_dir, "idx.npy"), idx[sel].astype(np.float64))
 
 
 class Job:
@@ -294,6 +313,8 @@ def measure(job, args, distance, gen_precision, steps, warmup, cpu_leg, headline
         elapsed = float(t.item())
     ms_per_step = 1e3 * elapsed / steps
     value = Q / (elapsed / steps)
+    if headline and args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, out_dist, out_idx)      # the last timed step's result: every rank holds the reduced keys
 
     # ---------------------------------------------------------------- per-kernel rooflines (this rank's launches)
     def kernel_entry(name, alg_per_step, bound, peak, unit, scale, executed_factor=1.0, note=None):
@@ -370,7 +391,7 @@ def measure(job, args, distance, gen_precision, steps, warmup, cpu_leg, headline
     # ---------------------------------------------------------------- parity check against the oracle (untimed)
     parity = None
     auroc = None
-    if args.check_queries > 0 and lp_model is not None and world == 1:
+    if args.full and args.check_queries > 0 and lp_model is not None and world == 1:
         # l2-lpips: fp64 oracle on a small sub-problem (8 queries x the first 256 bank samples)
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import lpips_oracle
@@ -391,7 +412,7 @@ def measure(job, args, distance, gen_precision, steps, warmup, cpu_leg, headline
             parity["full_size_census"] = {"source": os.path.relpath(census[-1], ROOT), "idx_mismatches": c["idx_mismatches"], "of_queries": c["config"]["queries"],
                                           "dist_max_abs_diff": c["dist_max_abs_diff"], "auroc_abs_delta": c["auroc_abs_delta"],
                                           "runner_up_gap_below_1e-5": c.get("runner_up_gap", {}).get("below_1e-5")}
-    elif args.check_queries > 0 and lp_model is None:
+    elif args.full and args.check_queries > 0 and lp_model is None:
         sys.path.insert(0, os.path.join(ROOT, "oracle"))
         import c_oracle
         nchk = min(args.check_queries, Q)
@@ -406,7 +427,7 @@ def measure(job, args, distance, gen_precision, steps, warmup, cpu_leg, headline
         o_dist = ((okeys >> np.uint64(32)).astype(np.float64) * (4.0 / (65025.0 * D))).astype(np.float32)
         parity = {"queries_checked": int(nchk), "idx_equal": bool(np.array_equal(o_idx, out_idx[sel])),
                   "max_abs_dist_err": float(np.abs(o_dist.astype(np.float64) - out_dist[sel]).max())}
-    if rank == 0:
+    if rank == 0 and args.full:
         _, _, _, auc, ap_, prec = plot_roc(-out_dist[:n_pos].astype(np.float64), -out_dist[n_pos:].astype(np.float64))
         auroc = {"auc": auc, "ap": ap_, "precision_at_-0.14": prec}
 
@@ -643,9 +664,14 @@ def main():
     ap.add_argument("--bank", type=int, default=100000)
     ap.add_argument("--batch-size", type=int, default=64)
     ap.add_argument("--chunk", type=int, default=0, help="generator images per pass (0 = library default)")
-    ap.add_argument("--cpu-queries", type=int, default=128, help="queries timed for the CPU baseline (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what takes work of its own beyond the timed steps: oracle parity, AUROC, CPU baseline and, with the default "
+                         "one-GPU headline, the secondary workloads, config0 and live PMC traffic passes")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's dist[Q] and idx[Q] as DIR/dist.npy (float32) and DIR/idx.npy (float64)")
+    ap.add_argument("--cpu-queries", type=int, default=128, help="--full: queries timed for the CPU baseline (0 = skip)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="torch CPU threads for the baseline (0 = min(16, usable cores))")
-    ap.add_argument("--check-queries", type=int, default=64, help="queries checked against the oracle after the run")
+    ap.add_argument("--check-queries", type=int, default=64, help="--full: queries checked against the oracle after the run")
     ap.add_argument("--gen-precision", type=int, default=1, choices=[0, 1],
                     help="generator arithmetic: 1 = split-fp16 (three fp16 MFMAs per product, default), 0 = fp32 MFMA")
     ap.add_argument("--collective", default="native", choices=["native", "torch", "gloo"],
@@ -661,21 +687,23 @@ def main():
     ap.add_argument("--distance", default="l2", choices=["l2", "l2-lpips"],
                     help="l2 = BASELINE configs[1] (default, the headline); l2-lpips = configs[2] (0.2*LPIPS+L2; needs ~2 MB of HBM per image)")
     ap.add_argument("--secondary", default="auto", choices=["auto", "on", "off"],
-                    help="the two further measurements (configs[2] under 0.2*LPIPS+L2, and the fp32-MFMA generator): auto = with the default one-GPU "
-                         "headline workload only")
+                    help="--full: the two further measurements (configs[2] under 0.2*LPIPS+L2, and the fp32-MFMA generator): auto = with the default "
+                         "one-GPU headline workload only")
     ap.add_argument("--secondary-steps", type=int, default=2)
     ap.add_argument("--live-traffic", default="auto", choices=["auto", "on", "off"],
-                    help="roofline.traffic from rocprofv3 --pmc passes of child runs of this workload made now (auto: in the default one-GPU run only); "
-                         "otherwise, and when the profiler is unavailable, from the newest committed passes under profiles/")
+                    help="--full: roofline.traffic from rocprofv3 --pmc passes of child runs of this workload made now (auto: in the default one-GPU "
+                         "run only); otherwise, and when the profiler is unavailable, from the newest committed passes under profiles/")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.backend == "nccl":
         args.collective = "torch"
     elif args.backend == "gloo":
         args.collective = "gloo"
 
     job = setup_job(args)
-    line = measure(job, args, args.distance, args.gen_precision, args.steps, args.warmup, cpu_leg=True, headline=True)
-    default_run = job.world == 1 and args.distance == "l2" and args.gen_precision == 1 and (
+    line = measure(job, args, args.distance, args.gen_precision, args.steps, args.warmup, cpu_leg=args.full, headline=True)
+    default_run = args.full and job.world == 1 and args.distance == "l2" and args.gen_precision == 1 and (
         args.secondary == "on" or (args.secondary == "auto" and args.queries == 10000 and args.bank == 100000))
     if default_run:
         import gc
@@ -688,7 +716,7 @@ def main():
         line["secondary"] = {k: sec[k] for k in keep + ("cpu_baseline_features_once", "speedup_vs_cpu_features_once", "algorithmic_speedup_on_cpu") if k in sec}
         line["secondary_fp32"] = {k: f32[k] for k in keep if k != "cpu_baseline" and k != "speedup_vs_cpu_baseline"}
         line["config0"] = measure_config0(job, args)
-    live = job.world == 1 and (args.live_traffic == "on" or (args.live_traffic == "auto" and default_run))
+    live = args.full and job.world == 1 and (args.live_traffic == "on" or (args.live_traffic == "auto" and default_run))
     if live:
         import gc
         gc.collect()

@@ -1,9 +1,11 @@
-"""The driver's contract with bench.py: one JSON line on stdout with the agreed fields, also at reduced sizes and for both distances."""
+"""The driver's contract with bench.py: one JSON line on stdout with the agreed fields, also at reduced sizes and for both distances; a plain run
+times the headline only, --full adds the checks and further measurements, --dump-outputs writes what the timed path returned."""
 import json
 import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 import gpu_common  # noqa: F401
@@ -20,7 +22,7 @@ def _run(*flags):
 
 
 def test_bench_line_fields():
-    d = _run("--steps", "2", "--warmup", "1", "--queries", "512", "--bank", "4096", "--cpu-queries", "8", "--cpu-seconds", "5")
+    d = _run("--full", "--steps", "2", "--warmup", "1", "--queries", "512", "--bank", "4096", "--cpu-queries", "8", "--cpu-seconds", "5")
     for key, typ in (("metric", str), ("value", float), ("unit", str), ("n_gpus", int), ("steps", int), ("warmup", int), ("ms_per_step", float),
                      ("higher_is_better", bool), ("scaling", str), ("dtype", str), ("data", str), ("config", dict), ("roofline", dict), ("cpu_baseline", dict)):
         assert isinstance(d[key], typ), (key, d[key])
@@ -35,7 +37,7 @@ def test_bench_line_fields():
 
 
 def test_bench_line_l2_lpips():
-    d = _run("--distance", "l2-lpips", "--steps", "1", "--warmup", "1", "--queries", "256", "--bank", "1024", "--cpu-queries", "0")
+    d = _run("--full", "--distance", "l2-lpips", "--steps", "1", "--warmup", "1", "--queries", "256", "--bank", "1024", "--cpu-queries", "0")
     assert d["roofline"]["bound"] == "mfma" and d["cpu_baseline"] is None and d["parity"]["idx_equal"] is True
     assert d["parity"]["max_abs_dist_err"] < 1e-5
 
@@ -43,7 +45,8 @@ def test_bench_line_l2_lpips():
 def test_bench_line_with_secondary_measurements():
     """what the driver's default run prints, at a reduced size: the headline line plus `secondary` (configs[2]: 0.2*LPIPS+L2, own roofline, parity and
     cpu_baseline) and `secondary_fp32` (generator with fp32 MFMA products)"""
-    d = _run("--steps", "2", "--warmup", "1", "--queries", "512", "--bank", "4096", "--cpu-queries", "8", "--cpu-seconds", "4", "--secondary", "on")
+    d = _run("--full", "--steps", "2", "--warmup", "1", "--queries", "512", "--bank", "4096", "--cpu-queries", "8", "--cpu-seconds", "4",
+             "--secondary", "on")
     assert d["roofline"]["kernel"] == "gather_conv" and d["cpu_baseline"]["kind"] == "port"
     s = d["secondary"]
     assert "configs[2]" in s["config"]["workload"] and s["roofline"]["kernel"] == "feat_knn" and s["roofline"]["bound"] == "mfma"
@@ -63,3 +66,23 @@ def test_bench_line_with_secondary_measurements():
     f = d["secondary_fp32"]
     assert f["dtype"].startswith("f32") and f["roofline"]["peak"] == 157.3 and f["parity"]["idx_equal"] is True
     assert f["ms_per_step"] > 0 and "cpu_baseline" not in f
+
+
+def test_plain_run_times_the_headline_and_dumps_its_outputs(tmp_path):
+    """without --full: the headline fields and nothing that needs work of its own; the dumped outputs are those of a --full run of the same
+    arguments, whose parity block checks every query against the oracle"""
+    size = ("--steps", "3", "--warmup", "1", "--queries", "512", "--bank", "4096")
+    d = _run(*size, "--dump-outputs", str(tmp_path / "plain"))
+    for key, typ in (("metric", str), ("value", float), ("unit", str), ("higher_is_better", bool), ("dtype", str), ("ms_per_step", float)):
+        assert isinstance(d[key], typ), (key, d[key])
+    assert d["steps"] == 3 and d["warmup"] == 1 and abs(d["value"] - 512 / (d["ms_per_step"] * 1e-3)) / d["value"] < 1e-3
+    assert d["cpu_baseline"] is None and d["parity"] is None and d["auroc"] is None
+    assert not {"secondary", "secondary_fp32", "config0"} & set(d)
+    f = _run(*size, "--full", "--cpu-queries", "0", "--check-queries", "512", "--dump-outputs", str(tmp_path / "full"))
+    assert f["parity"]["queries_checked"] == 512 and f["parity"]["idx_equal"] is True and f["parity"]["max_abs_dist_err"] == 0.0
+    assert sorted(os.listdir(tmp_path / "plain")) == ["dist.npy", "idx.npy"]
+    for name, dtype in (("dist", np.float32), ("idx", np.float64)):
+        a, b = np.load(tmp_path / "plain" / (name + ".npy")), np.load(tmp_path / "full" / (name + ".npy"))
+        assert a.dtype == dtype and a.shape == (512,) and np.array_equal(a, b), name
+    idx = np.load(tmp_path / "plain" / "idx.npy")
+    assert idx.min() >= 0 and idx.max() < 4096 and np.array_equal(idx, np.round(idx))

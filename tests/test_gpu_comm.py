@@ -142,7 +142,7 @@ def test_bench_two_ranks_sharing_the_gpu():
     env = dict(os.environ, MASTER_ADDR="127.0.0.1")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1", "--master-port",
            str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--collective", "gloo", "--queries", "512",
-           "--bank", "8192", "--cpu-queries", "0"]
+           "--bank", "8192", "--cpu-queries", "0", "--full"]
     out = subprocess.run(cmd, check=True, stdout=subprocess.PIPE, cwd=ROOT, env=env, timeout=600).stdout.decode()
     lines = [l for l in out.splitlines() if l.strip().startswith("{")]
     assert len(lines) == 1, out

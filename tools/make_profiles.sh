@@ -14,10 +14,10 @@ OUT=$ROOT/gpurun_out/profiles_$TAG
 DEST=$OUT/final
 mkdir -p "$OUT" "$DEST"
 cd /tmp && export TMPDIR=/tmp
-B="python3 $ROOT/bench.py --secondary off"
+B="python3 $ROOT/bench.py --full --secondary off"
 ONE="$B --steps 1 --warmup 0 --cpu-queries 0 --check-queries 0"
 SQ="SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_LDS_BANK_CONFLICT GRBM_GUI_ACTIVE"
-echo "[profiles] bench (headline + secondaries)"; python3 "$ROOT/bench.py" > "$OUT/bench.json"
+echo "[profiles] bench (headline + secondaries)"; python3 "$ROOT/bench.py" --full > "$OUT/bench.json"
 echo "[profiles] kernel trace, headline"
 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- $B --cpu-queries 0 > "$OUT/bench_under_rocprof.json"
 rm -f "$OUT"/trace/*/*kernel_trace.csv

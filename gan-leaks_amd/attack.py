@@ -78,15 +78,26 @@ class Bank:
     kind 'u8' : biased int8 rows + int32 row norms (exact path), bytes are image codes: x = 2*(u/255.)-1
     kind 'int': the same, bytes are the values themselves: x = float(u)  (float inputs only; uint8 input always means image codes)
     kind 'f32': the fp32 rows as given (fixed-order fp32 path)
-    `index_base` is the global index of row 0 (non-zero for a shard of a larger bank)."""
+    `index_base` is the global index of row 0 (non-zero for a shard of a larger bank).
+    The int32 norms limit 'u8' / 'int' banks to d <= gl_l2_max_d(0) = 262143 values per row; `from_images(..., norms64=True)` prepares the
+    wide form instead (int64 norms, any d up to gl_l2_max_d(1) = 2^24, gl_l2_knn_i8_wide), and norms64='auto' only where d needs it."""
 
     def __init__(self, ctx, kind, n, d, index_base=0, rows_i8=None, norms=None, rows_f32=None, u8=None):
         self.ctx, self.kind, self.n, self.d = ctx, kind, int(n), int(d)
         self.index_base = int(index_base)
         self.rows_i8, self.norms, self.rows_f32, self.u8 = rows_i8, norms, rows_f32, u8
 
+    @property
+    def wide(self):
+        """True when the row norms are int64 (gl_l2_prepare_wide / gl_l2_knn_i8_wide)"""
+        return self.norms is not None and self.norms.dtype == np.dtype(np.int64)
+
     @classmethod
-    def from_images(cls, images, ctx=None, index_base=0, keep_u8=False, force_kind=None):
+    def from_images(cls, images, ctx=None, index_base=0, keep_u8=False, force_kind=None, norms64=False):
+        """norms64: False (int32 norms, d <= gl_l2_max_d(0)), True (int64 norms, d <= gl_l2_max_d(1)) or 'auto' (int64 only when d
+        exceeds the int32 limit).  Only 'u8' / 'int' banks have norms."""
+        if norms64 not in (False, True, "auto"):
+            raise ValueError("norms64 must be False, True or 'auto', got %r" % (norms64,))
         ctx = ctx or Context.get()
         rows = _to_device_rows(ctx, images)
         n, d = rows.shape
@@ -113,8 +124,11 @@ class Bank:
             raise ValueError("uint8 input is read as image codes; pass float rows for the integer lattice")
         stride = int(ctx.lib.gl_l2_row_stride(d))
         rows_i8 = ctx.empty((n, stride), np.int8)
-        norms = ctx.empty((max(n, 1),), np.int32)
-        check(ctx.lib.gl_l2_prepare(ctx.handle, _p(rows.ptr), n, d, _p(rows_i8.ptr), _p(norms.ptr)))
+        if norms64 == "auto":
+            norms64 = needs_wide(ctx, d)
+        norms = ctx.empty((max(n, 1),), np.int64 if norms64 else np.int32)
+        prepare = ctx.lib.gl_l2_prepare_wide if norms64 else ctx.lib.gl_l2_prepare
+        check(prepare(ctx.handle, _p(rows.ptr), n, d, _p(rows_i8.ptr), _p(norms.ptr)))
         ctx.sync()
         return cls(ctx, kind, n, d, index_base, rows_i8=rows_i8, norms=norms, u8=rows if keep_u8 else None)
 
@@ -146,6 +160,18 @@ class Bank:
 
     def __len__(self):
         return self.n
+
+
+def needs_wide(ctx, d):
+    """True when rows of d values exceed the int32-norm limit of the exact path (gl_l2_max_d(0)) and need the wide form"""
+    return int(d) > int(ctx.lib.gl_l2_max_d(0))
+
+
+def _norms64_for(queries):
+    """the norm width a bank prepared for `queries` must have: the width of a prepared exact-path query Bank, else 'auto'"""
+    if isinstance(queries, Bank) and queries.kind in ("u8", "int"):
+        return queries.wide
+    return "auto"
 
 
 class GeneratedBank:
@@ -205,19 +231,23 @@ def knn_keys(bank, queries, n_rows=None, keys=None, fpath=None):
     u8 path: (S << 32) | global index; f32 path: (float_bits(dist) << 32) | global index.  Asynchronous."""
     ctx = bank.ctx
     if not isinstance(queries, Bank):
-        queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind="f32" if bank.kind == "f32" else None)
+        queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind="f32" if bank.kind == "f32" else None, norms64=bank.wide)
     if queries.d != bank.d:
         raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
     if queries.kind != bank.kind:
         # one side is off-lattice: compare in fp32 (the lattice side decodes exactly to what read_image yields)
         bank, queries = bank.as_f32(), queries.as_f32()
+    elif bank.kind in ("u8", "int") and queries.wide != bank.wide:
+        raise ValueError("the query Bank has %s row norms, the bank %s: prepare both with the same norms64" %
+                         ("int64" if queries.wide else "int32", "int64" if bank.wide else "int32"))
     n_rows = bank.n if n_rows is None else int(n_rows)
     if keys is None:
         keys = ctx.empty((max(queries.n, 1),), np.uint64)
         check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), queries.n))
     if bank.kind in ("u8", "int"):
-        check(ctx.lib.gl_l2_knn_i8(ctx.handle, _p(bank.rows_i8.ptr), _p(bank.norms.ptr), n_rows, bank.index_base,
-                                   _p(queries.rows_i8.ptr), _p(queries.norms.ptr), queries.n, bank.d, _p(keys.ptr)))
+        knn = ctx.lib.gl_l2_knn_i8_wide if bank.wide else ctx.lib.gl_l2_knn_i8
+        check(knn(ctx.handle, _p(bank.rows_i8.ptr), _p(bank.norms.ptr), n_rows, bank.index_base,
+                  _p(queries.rows_i8.ptr), _p(queries.norms.ptr), queries.n, bank.d, _p(keys.ptr)))
     elif float_path(fpath) == "mfma":
         (bv, bn, bs), (qv, qn, qs) = bank.split_rows(), queries.split_rows()
         check(ctx.lib.gl_rows_knn_split(ctx.handle, _p(bv.ptr), _p(bn.ptr), _p(bs.ptr), n_rows, bank.index_base, _p(qv.ptr), _p(qn.ptr), _p(qs.ptr),
@@ -309,7 +339,7 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
 
     # 'l2': every chunk must take the same arithmetic path.  Exact integers unless the queries or some chunk are off the 8-bit lattice;
     # then everything is redone on the fixed-order fp32 path (what the resident form does for such inputs).
-    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True)
+    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64="auto")
     for force in ((fq.kind, "f32") if fq.kind != "f32" else ("f32",)):
         q_side = fq if fq.kind == force else fq.as_f32()
         step = max(1, int(chunk_bytes // ((4 if force == "f32" else 2) * fq.d)))
@@ -317,7 +347,7 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
         for lo in range(0, n_rows, step):
             hi = min(lo + step, n_rows)
             try:
-                b = Bank.from_images(rows(lo, hi), ctx, index_base=base + lo, force_kind=force)
+                b = Bank.from_images(rows(lo, hi), ctx, index_base=base + lo, force_kind=force, norms64=fq.wide)
             except ValueError:           # an off-lattice chunk
                 ok = False
                 break
@@ -345,7 +375,7 @@ def prepare_queries(queries, distance, ctx=None, lpips=None, comm=None):
                 and len(queries) >= 8 * comm.nranks):
             return _lp.features_sharded(model, queries, comm)
         return model.features(queries, role=model.search_role("query"))
-    return Bank.from_images(queries, ctx or Context.get(), keep_u8=True)
+    return Bank.from_images(queries, ctx or Context.get(), keep_u8=True, norms64="auto")
 
 
 def attack(queries, bank, distance="l2", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, float_path=None, index_base=0):
@@ -432,7 +462,7 @@ def attack(queries, bank, distance="l2", batch_size=64, ctx=None, reduce_fn=None
         return unpack_keys(ctx, keys, fq.n, fb.K, "f32")
 
     if not prepared:
-        bank = Bank.from_images(bank, ctx, index_base=index_base, keep_u8=True)
+        bank = Bank.from_images(bank, ctx, index_base=index_base, keep_u8=True, norms64=_norms64_for(queries))
     keys, q, kind = knn_keys(bank, queries, n_rows, fpath=float_path)
     if reduce_fn is not None:
         keys = reduce_fn(keys)

@@ -96,7 +96,7 @@ def _cached_bank(syn_imgs, n_rows, loss, fmt=None):
         if loss.distance == "l2-lpips":
             _bank_cache["bank"] = loss.lpips_model.features(syn_imgs[:n_rows], role=loss.lpips_model.search_role("bank"), fmt=fmt)
         else:
-            _bank_cache["bank"] = Bank.from_images(syn_imgs[:n_rows], keep_u8=True)
+            _bank_cache["bank"] = Bank.from_images(syn_imgs[:n_rows], keep_u8=True, norms64="auto")
         _bank_cache["key"] = key
     return _bank_cache["bank"]
 

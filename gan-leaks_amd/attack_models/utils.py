@@ -197,8 +197,8 @@ class Loss:
                 raise ValueError("x_gt must hold 1 image or as many as x_hat (broadcast rule of utils.py:168-169)")
             lp, l2 = _lp.rows_dist(a, g)
             return self._finish(x_hat, lp, l2)
-        a = Bank.from_images(x_hat, ctx, keep_u8=True)
-        g = Bank.from_images(x_gt, ctx, keep_u8=True, force_kind="f32" if a.kind == "f32" else None)
+        a = Bank.from_images(x_hat, ctx, keep_u8=True, norms64="auto")
+        g = Bank.from_images(x_gt, ctx, keep_u8=True, force_kind="f32" if a.kind == "f32" else None, norms64="auto")
         if a.d != g.d:
             raise ValueError("image sizes differ")
         if a.kind != g.kind or a.kind == "int":

@@ -142,9 +142,50 @@ __global__ void __launch_bounds__(kThreads) l2_prepare_kernel(const uint8_t *__r
     }
 }
 
+// the same rows for d up to GL_L2_WIDE_MAX_D with int64 norms (<= 16384 d < 2^38).  A lane sums up to 256 d, past 2^31 from d = 2^23 on,
+// so each 16-byte group's four sdot4 (<= 2^18 together) go into a 64-bit lane total.
+__global__ void __launch_bounds__(kThreads) l2_prepare_wide_kernel(const uint8_t *__restrict__ rows, int64_t count, int64_t d, int64_t stride,
+                                                                   int8_t *__restrict__ out, int64_t *__restrict__ norms)
+{
+    const int lane = threadIdx.x & 63;
+    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
+    const bool vec = ((d & 15) == 0) && ((reinterpret_cast<uintptr_t>(rows) & 15) == 0);
+    for (int64_t r = wave; r < count; r += nwaves) {
+        const uint8_t *src = rows + r * d;
+        int8_t *dst = out + r * stride;
+        long long acc = 0;
+        if (vec) {
+            for (int64_t k = (int64_t)lane * 16; k < stride; k += 64 * 16) {
+                uint4 v = make_uint4(0, 0, 0, 0);
+                if (k < d) {
+                    v = *reinterpret_cast<const uint4 *>(src + k);
+                    v.x ^= 0x80808080u; v.y ^= 0x80808080u; v.z ^= 0x80808080u; v.w ^= 0x80808080u;
+                    int s = __builtin_amdgcn_sdot4((int)v.x, (int)v.x, 0, false);
+                    s = __builtin_amdgcn_sdot4((int)v.y, (int)v.y, s, false);
+                    s = __builtin_amdgcn_sdot4((int)v.z, (int)v.z, s, false);
+                    s = __builtin_amdgcn_sdot4((int)v.w, (int)v.w, s, false);
+                    acc += s;
+                }
+                *reinterpret_cast<uint4 *>(dst + k) = v;
+            }
+        } else {
+            for (int64_t k = lane; k < stride; k += 64) {
+                int b = 0;
+                if (k < d) { b = (int)src[k] - 128; acc += b * b; }
+                dst[k] = (int8_t)b;
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+        if (lane == 0) norms[r] = acc;
+    }
+}
+
 // per-row squared L2 between x_hat rows and x_gt (one row broadcast, or one per x_hat row): the [B]
 // vector Loss('l2').forward returns (attack_models/utils.py:163,169,176).  One wave per row,
-// S = sum a^2 + sum b^2 - 2 sum ab with the unsigned 8-bit dot instruction, exact in uint32.
+// S = sum a^2 + sum b^2 - 2 sum ab with the unsigned 8-bit dot instruction; each dot (<= 4 * 255^2) is added into 64-bit lane sums
+// (d / 64 values of up to 255^2 per lane pass 32 bits from d of about 4.2 M on), so S is exact up to GL_L2_WIDE_MAX_D.
 __global__ void __launch_bounds__(kThreads) l2_rows_u8_kernel(const uint8_t *__restrict__ xh, int64_t b, const uint8_t *__restrict__ xg, int64_t b_gt,
                                                               int64_t d, double scale, float *__restrict__ out)
 {
@@ -154,13 +195,13 @@ __global__ void __launch_bounds__(kThreads) l2_rows_u8_kernel(const uint8_t *__r
     for (int64_t r = wave; r < b; r += nwaves) {
         const uint8_t *pa = xh + r * d;
         const uint8_t *pb = xg + (b_gt == 1 ? 0 : r) * d;
-        unsigned saa = 0, sbb = 0, sab = 0;
+        unsigned long long saa = 0, sbb = 0, sab = 0;
         if (((d & 3) == 0) && (((reinterpret_cast<uintptr_t>(pa) | reinterpret_cast<uintptr_t>(pb)) & 3) == 0)) {
             for (int64_t k = (int64_t)lane * 4; k < d; k += 256) {
                 const unsigned a = *reinterpret_cast<const unsigned *>(pa + k), c = *reinterpret_cast<const unsigned *>(pb + k);
-                saa = __builtin_amdgcn_udot4(a, a, saa, false);
-                sbb = __builtin_amdgcn_udot4(c, c, sbb, false);
-                sab = __builtin_amdgcn_udot4(a, c, sab, false);
+                saa += __builtin_amdgcn_udot4(a, a, 0u, false);
+                sbb += __builtin_amdgcn_udot4(c, c, 0u, false);
+                sab += __builtin_amdgcn_udot4(a, c, 0u, false);
             }
         } else {
             for (int64_t k = lane; k < d; k += 64) {
@@ -168,7 +209,7 @@ __global__ void __launch_bounds__(kThreads) l2_rows_u8_kernel(const uint8_t *__r
                 saa += a * a; sbb += c * c; sab += a * c;
             }
         }
-        long long s = (long long)saa + (long long)sbb - 2ll * (long long)sab;   // per-lane parts fit 32 unsigned bits (d / 64 values each)
+        long long s = (long long)saa + (long long)sbb - 2ll * (long long)sab;
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
         if (lane == 0) out[r] = (float)((double)s * scale);
@@ -257,7 +298,15 @@ int gl_quantize_f32(gl_ctx *ctx, const float *x_dev, int64_t count, int mode, ui
     return GL_OK;
 }
 
-int64_t gl_l2_row_stride(int64_t d) { return d <= 0 ? 0 : gl_ceil_div(d, 128) * 128; }
+// Rows of the wide range (d > GL_L2_MAX_D) that would be an even number of 128-byte lines get one zero line more.  The search kernel
+// reads the same 128-byte K slice of a tile's 128 rows together; at 3 x 512 x 512 (768 KiB = 3 * 2^18 bytes per row) those would share
+// their low 18 address bits, i.e. one L2 set, while an odd number of lines per row spreads them over 128 sets.
+int64_t gl_l2_row_stride(int64_t d)
+{
+    if (d <= 0) return 0;
+    const int64_t s = gl_ceil_div(d, 128) * 128;
+    return d > GL_L2_MAX_D && gl_tuning_int("GL_L2_WIDE_PAD", 1) && ((s >> 7) & 1) == 0 ? s + 128 : s;
+}
 
 int gl_l2_prepare(gl_ctx *ctx, const uint8_t *rows_u8_dev, int64_t count, int64_t d, int8_t *rows_i8_dev, int32_t *norms_dev)
 {
@@ -278,10 +327,29 @@ int gl_l2_prepare(gl_ctx *ctx, const uint8_t *rows_u8_dev, int64_t count, int64_
     return GL_OK;
 }
 
+int gl_l2_prepare_wide(gl_ctx *ctx, const uint8_t *rows_u8_dev, int64_t count, int64_t d, int8_t *rows_i8_dev, int64_t *norms_dev)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && count >= 0 && d > 0, "gl_l2_prepare_wide: bad ctx/count/d");
+    GL_REQUIRE(d <= GL_L2_WIDE_MAX_D, "gl_l2_prepare_wide: d=%lld exceeds the exact-integer limit %lld", (long long)d, (long long)GL_L2_WIDE_MAX_D);
+    if (count == 0) return GL_OK;
+    GL_REQUIRE(rows_u8_dev && rows_i8_dev && norms_dev, "gl_l2_prepare_wide: NULL device pointer");
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(rows_i8_dev) & 15) == 0, "gl_l2_prepare_wide: rows_i8_dev must be 16-byte aligned");
+    int64_t blocks = gl_ceil_div(count, kThreads / 64);
+    if (blocks > 4096) blocks = 4096;
+    gl_prof_scope prof_(ctx, GL_PROF_L2_PREPARE);
+    hipLaunchKernelGGL(l2_prepare_wide_kernel, dim3((int)blocks), dim3(kThreads), 0, ctx->stream, rows_u8_dev, count, d, gl_l2_row_stride(d),
+                       rows_i8_dev, norms_dev);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int64_t gl_l2_max_d(int wide) { return wide ? GL_L2_WIDE_MAX_D : GL_L2_MAX_D; }
+
 int gl_l2_rows_u8(gl_ctx *ctx, const uint8_t *x_hat_u8_dev, int64_t b, const uint8_t *x_gt_u8_dev, int64_t b_gt, int64_t d, float *out_dev)
 {
     gl_make_current(ctx);
-    GL_REQUIRE(ctx && b >= 0 && d > 0 && d <= GL_L2_MAX_D, "gl_l2_rows_u8: bad ctx/b/d");
+    GL_REQUIRE(ctx && b >= 0 && d > 0 && d <= GL_L2_WIDE_MAX_D, "gl_l2_rows_u8: bad ctx/b/d");
     GL_REQUIRE(b_gt == 1 || b_gt == b, "gl_l2_rows_u8: x_gt must hold 1 row or %lld rows (broadcast rule of utils.py:163), got %lld", (long long)b,
                (long long)b_gt);
     if (b == 0) return GL_OK;

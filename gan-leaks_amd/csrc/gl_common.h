@@ -116,6 +116,8 @@ static inline void gl_make_current(const gl_ctx *ctx)
 // because the cross-GPU minimum runs on the int64 view of the keys; shift is 32 for d <= 33025 (everything up to 3 x 104 x 104)
 // and shrinks by one bit per doubling of d beyond that (29 at 3 x 256 x 256, leaving 2^29 bank rows).
 constexpr int64_t GL_L2_MAX_D = 262143;          // row norms sum (u-128)^2 <= 16384 d must fit 32 unsigned bits
+// the wide pair (gl_l2_prepare_wide / gl_l2_knn_i8_wide): int64 row norms, S <= 65025 d < 2^40, shift 23 at the top (3 x 2048 x 2048 fits)
+constexpr int64_t GL_L2_WIDE_MAX_D = 1ll << 24;
 static inline int gl_l2_key_shift(int64_t d)
 {
     const unsigned long long smax = 65025ull * (unsigned long long)d;

@@ -159,6 +159,111 @@ l2_knn_i8_kernel(const int8_t *__restrict__ bank, const int32_t *__restrict__ ba
     }
 }
 
+// The wide range, d <= GL_L2_WIDE_MAX_D = 2^24: the tile, K loop and 64-bit flush of l2_knn_i8_kernel<true> with int64 row norms
+// (sum (u-128)^2 <= 16384 d < 2^38).  |cross| <= 2^30 per 512-slice segment as there, the totals stay below 2^38, and
+// S = |a|^2 + |b|^2 - 2 cross <= 65025 d < 2^40 is formed in 64 bits; key = S << gl_l2_key_shift(d) | global index stays below 2^63.
+__global__ void __launch_bounds__(THREADS, 2)
+l2_knn_i8_wide_kernel(const int8_t *__restrict__ bank, const int64_t *__restrict__ bank_norm, int64_t n_rows, int64_t index_base,
+                      const int8_t *__restrict__ query, const int64_t *__restrict__ query_norm, int64_t nq, int64_t stride,
+                      unsigned long long *__restrict__ keys, int q_tiles, int n_tiles, int shift)
+{
+    constexpr int FLUSH = 512;                        // slices per 64-bit flush: 64 KiB of K
+    extern __shared__ __attribute__((aligned(16))) char smem[];   // [2 buffers][bank 16 KiB | query 16 KiB]
+
+    const unsigned nwg = (unsigned)q_tiles * (unsigned)n_tiles;
+    const unsigned id = gl_xcd_remap(blockIdx.x, nwg);
+    int qt, nt;
+    gl_strip_order(id, q_tiles, n_tiles, qt, nt);
+    const int64_t n0 = (int64_t)nt * TILE_N, q0 = (int64_t)qt * TILE_Q;
+
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int wn = wave >> 1, wq = wave & 1;
+    const int frow = lane & 15, fk = lane >> 4;
+
+    v4i acc[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) acc[i][j] = (v4i){0, 0, 0, 0};
+    long long tot[4][4][4] = {};
+    auto flush = [&]() {
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) { tot[i][j][r] += (long long)acc[i][j][r]; acc[i][j][r] = 0; }
+    };
+
+    const int nk = (int)(stride / TILE_K);
+    stage_operand(bank, n0, n_rows, stride, 0, smem, wave, lane);
+    stage_operand(query, q0, nq, stride, 0, smem + OPER_BYTES, wave, lane);
+
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();
+        char *cur = smem + (kt & 1) * 2 * OPER_BYTES;
+        if (kt + 1 < nk) {
+            char *nxt = smem + ((kt + 1) & 1) * 2 * OPER_BYTES;
+            stage_operand(bank, n0, n_rows, stride, (int64_t)(kt + 1) * TILE_K, nxt, wave, lane);
+            stage_operand(query, q0, nq, stride, (int64_t)(kt + 1) * TILE_K, nxt + OPER_BYTES, wave, lane);
+        }
+        const char *lb = cur + (wn * 64) * TILE_K;
+        const char *lq = cur + OPER_BYTES + (wq * 64) * TILE_K;
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const int chunk = ks * 4 + fk;
+            v4i a[4], b[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int r = i * 16 + frow;
+                a[i] = *reinterpret_cast<const v4i *>(lb + r * TILE_K + ((chunk ^ (r & 7)) << 4));
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int r = j * 16 + frow;
+                b[j] = *reinterpret_cast<const v4i *>(lq + r * TILE_K + ((chunk ^ (r & 7)) << 4));
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc[i][j] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a[i], b[j], acc[i][j], 0, 0, 0);
+        }
+        if ((kt % FLUSH) == FLUSH - 1) flush();
+    }
+    flush();
+
+    const int64_t nbase = n0 + wn * 64 + fk * 4;
+    long long bn[4][4];
+#pragma unroll
+    for (int i = 0; i < 4; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            const int64_t n = nbase + i * 16 + r;
+            bn[i][r] = n < n_rows ? bank_norm[n] : 0;
+        }
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int64_t q = q0 + wq * 64 + j * 16 + frow;
+        const long long qn = q < nq ? query_norm[q] : 0;
+        unsigned long long best = ~0ull;
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const int64_t n = nbase + i * 16 + r;
+                const unsigned long long s = (unsigned long long)(bn[i][r] + qn - 2ll * tot[i][j][r]);
+                const unsigned long long key = (s << shift) | (unsigned long long)(index_base + n);
+                if (n < n_rows && key < best) best = key;
+            }
+        unsigned long long o = __shfl_xor(best, 16, 64);
+        best = o < best ? o : best;
+        o = __shfl_xor(best, 32, 64);
+        best = o < best ? o : best;
+        if (fk == 0 && q < nq && best != ~0ull) atomicMin(&keys[q], best);
+    }
+}
+
 // 256 bank rows x 256 queries per workgroup: half the operand bytes per MFMA of the 128 x 128 tile.  The bank and the queries
 // are streamed from beyond L2 (a tile's two panels are 2 x 256 x d bytes; the co-resident tiles of an XCD cycle through more
 // panels than its 4 MiB L2 holds), and with the int8 matrix rate twice the fp16 one that stream, not the matrix pipe, sets the
@@ -394,6 +499,34 @@ int gl_l2_knn_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *bank_nor
     return GL_OK;
 }
 
+int gl_l2_knn_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, int64_t index_base,
+                      const int8_t *query_i8_dev, const int64_t *query_norm_dev, int64_t nq, int64_t d, uint64_t *keys_dev)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx, "gl_l2_knn_i8_wide: NULL ctx");
+    GL_REQUIRE(n_rows >= 0 && nq >= 0 && d > 0 && d <= GL_L2_WIDE_MAX_D, "gl_l2_knn_i8_wide: bad sizes n_rows=%lld nq=%lld d=%lld (d <= %lld)",
+               (long long)n_rows, (long long)nq, (long long)d, (long long)GL_L2_WIDE_MAX_D);
+    const int shift = gl_l2_key_shift(d);
+    GL_REQUIRE(index_base >= 0 && index_base + n_rows <= (1ll << shift), "gl_l2_knn_i8_wide: global index does not fit the %d index bits of a key at d=%lld",
+               shift, (long long)d);
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    GL_REQUIRE(bank_i8_dev && bank_norm_dev && query_i8_dev && query_norm_dev && keys_dev, "gl_l2_knn_i8_wide: NULL device pointer");
+    GL_REQUIRE(((reinterpret_cast<uintptr_t>(bank_i8_dev) | reinterpret_cast<uintptr_t>(query_i8_dev)) & 15) == 0,
+               "gl_l2_knn_i8_wide: prepared rows must be 16-byte aligned");
+    const int64_t stride = gl_l2_row_stride(d);
+    const int64_t q_tiles = gl_ceil_div(nq, TILE_Q), n_tiles = gl_ceil_div(n_rows, TILE_N);
+    GL_REQUIRE(q_tiles * n_tiles < (1ll << 31), "gl_l2_knn_i8_wide: grid too large");
+    const int lds = 4 * OPER_BYTES;
+    GL_ONCE_PER_DEVICE(ctx, \
+        GL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(l2_knn_i8_wide_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds)););
+    gl_prof_scope prof_(ctx, GL_PROF_L2_KNN);
+    hipLaunchKernelGGL(l2_knn_i8_wide_kernel, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), lds, ctx->stream, bank_i8_dev, bank_norm_dev, n_rows,
+                       index_base, query_i8_dev, query_norm_dev, nq, stride, reinterpret_cast<unsigned long long *>(keys_dev), (int)q_tiles,
+                       (int)n_tiles, shift);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
 int gl_fbb_knn_l2_host(gl_ctx *ctx, const uint8_t *bank_u8_host, int64_t n_bank, const uint8_t *queries_u8_host, int64_t nq, int64_t d,
                        int64_t batch_size, float *dist_host, int64_t *idx_host)
 {
@@ -410,7 +543,9 @@ int gl_fbb_knn_l2_host(gl_ctx *ctx, const uint8_t *bank_u8_host, int64_t n_bank,
     const int64_t stride = gl_l2_row_stride(d);
     uint8_t *raw = nullptr;
     int8_t *bank_i8 = nullptr, *q_i8 = nullptr;
-    int32_t *bank_nrm = nullptr, *q_nrm = nullptr;
+    void *bank_nrm = nullptr, *q_nrm = nullptr;        // int32 norms, int64 above GL_L2_MAX_D (the wide pair)
+    const bool wide = d > GL_L2_MAX_D;
+    const size_t nrm_bytes = wide ? 8 : 4;
     uint64_t *keys = nullptr;
     float *dist = nullptr;
     int64_t *idx = nullptr;
@@ -420,18 +555,19 @@ int gl_fbb_knn_l2_host(gl_ctx *ctx, const uint8_t *bank_u8_host, int64_t n_bank,
     GL_TRY(gl_malloc(ctx, raw_bytes, (void **)&raw));
     GL_TRY(gl_malloc(ctx, (size_t)n_eff * stride, (void **)&bank_i8));
     GL_TRY(gl_malloc(ctx, (size_t)nq * stride, (void **)&q_i8));
-    GL_TRY(gl_malloc(ctx, (size_t)n_eff * 4, (void **)&bank_nrm));
-    GL_TRY(gl_malloc(ctx, (size_t)nq * 4, (void **)&q_nrm));
+    GL_TRY(gl_malloc(ctx, (size_t)n_eff * nrm_bytes, &bank_nrm));
+    GL_TRY(gl_malloc(ctx, (size_t)nq * nrm_bytes, &q_nrm));
     GL_TRY(gl_malloc(ctx, (size_t)nq * 8, (void **)&keys));
     GL_TRY(gl_malloc(ctx, (size_t)nq * 4, (void **)&dist));
     GL_TRY(gl_malloc(ctx, (size_t)nq * 8, (void **)&idx));
     GL_TRY(gl_memcpy_h2d(ctx, raw, bank_u8_host, (size_t)n_eff * d));
-    GL_TRY(gl_l2_prepare(ctx, raw, n_eff, d, bank_i8, bank_nrm));
+    GL_TRY(wide ? gl_l2_prepare_wide(ctx, raw, n_eff, d, bank_i8, (int64_t *)bank_nrm) : gl_l2_prepare(ctx, raw, n_eff, d, bank_i8, (int32_t *)bank_nrm));
     GL_TRY(gl_ctx_sync(ctx));
     GL_TRY(gl_memcpy_h2d(ctx, raw, queries_u8_host, (size_t)nq * d));
-    GL_TRY(gl_l2_prepare(ctx, raw, nq, d, q_i8, q_nrm));
+    GL_TRY(wide ? gl_l2_prepare_wide(ctx, raw, nq, d, q_i8, (int64_t *)q_nrm) : gl_l2_prepare(ctx, raw, nq, d, q_i8, (int32_t *)q_nrm));
     GL_TRY(gl_keys_init(ctx, keys, nq));
-    GL_TRY(gl_l2_knn_i8(ctx, bank_i8, bank_nrm, n_eff, 0, q_i8, q_nrm, nq, d, keys));
+    GL_TRY(wide ? gl_l2_knn_i8_wide(ctx, bank_i8, (const int64_t *)bank_nrm, n_eff, 0, q_i8, (const int64_t *)q_nrm, nq, d, keys)
+                : gl_l2_knn_i8(ctx, bank_i8, (const int32_t *)bank_nrm, n_eff, 0, q_i8, (const int32_t *)q_nrm, nq, d, keys));
     GL_TRY(gl_keys_unpack(ctx, keys, nq, d, dist, idx));
     GL_TRY(gl_memcpy_d2h(ctx, dist_host, dist, (size_t)nq * 4));
     GL_TRY(gl_memcpy_d2h(ctx, idx_host, idx, (size_t)nq * 8));

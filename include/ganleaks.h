@@ -105,24 +105,35 @@ int gl_decode_u8(gl_ctx *ctx, const uint8_t *u8_dev, int64_t count, float *x_dev
 int gl_quantize_f32(gl_ctx *ctx, const float *x_dev, int64_t count, int mode, uint8_t *u8_dev);
 
 /* ---------------------------------------------------------------- L2 nearest neighbour (the hot path) */
-/* bytes one prepared row occupies: D rounded up to the kernel's K tile */
+/* bytes one prepared row occupies: D rounded up to the kernel's K tile of 128 bytes; above 262143 (the wide pair) an odd number of tiles,
+ * one zero tile more when needed, so that the rows of a search tile do not share one L2 set */
 int64_t gl_l2_row_stride(int64_t d);
 /* u8 rows -> biased int8 rows (u-128, zero padded to gl_l2_row_stride(d)) and per-row sum (u-128)^2.
  * rows_i8_dev: [count][gl_l2_row_stride(d)] bytes; norms_dev: [count] int32 (the bit pattern of an unsigned value when d > 131071).
- * d <= 262143 (3 x 256 x 256 = 196608 fits). */
+ * d <= 262143 (3 x 256 x 256 = 196608 fits); larger images: gl_l2_prepare_wide. */
 int gl_l2_prepare(gl_ctx *ctx, const uint8_t *rows_u8_dev, int64_t count, int64_t d, int8_t *rows_i8_dev, int32_t *norms_dev);
 /* keys[q] = UINT64_MAX */
 int gl_keys_init(gl_ctx *ctx, uint64_t *keys_dev, int64_t nq);
 /* keys[q] = min(keys[q], (S(q,n) << shift) | (index_base + n)) over n in [0, n_rows):
  *   S = sum_k (uq_k - ub_k)^2, exact integers (d <= 66051: modulo 2^32 with S < 2^32; up to d = 262143: int32 segments of 64 KiB of K
- *   summed in 64 bits).  shift = 32 for d <= 33025 and one bit less per doubling of d beyond (31 at 3x128x128, 29 at 3x256x256) so that
- *   keys stay below 2^63 for the int64 all-reduce(min); index_base + n_rows <= 2^shift.  gl_keys_unpack derives the same shift from d.
+ *   summed in 64 bits; larger d: gl_l2_knn_i8_wide below).  shift = 32 for d <= 33025 and one bit less per doubling of d beyond (31 at
+ *   3x128x128, 29 at 3x256x256, 27 at 3x512x512, 25 at 3x1024x1024, 23 at 2^24) so that keys stay below 2^63 for the int64
+ *   all-reduce(min); index_base + n_rows <= 2^shift.  gl_keys_unpack derives the same shift from d, for any d.
  *   Replaces the loop body + torch.min of custom_knn
  *   (attack_models/fbb.py:77-86) with Loss('l2') (attack_models/utils.py:163,169,176) for the whole
  *   query set at once.  The caller applies the BATCH_SIZE truncation (fbb.py:77) by passing
  *   n_rows = n_eff.  index_base is the global index of bank row 0 (bank shards). */
 int gl_l2_knn_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *bank_norm_dev, int64_t n_rows, int64_t index_base,
                  const int8_t *query_i8_dev, const int32_t *query_norm_dev, int64_t nq, int64_t d, uint64_t *keys_dev);
+/* Images larger than 262143 values (3x512x512, 3x1024x1024, up to gl_l2_max_d(1) = 2^24 = 3x2048x2048 and a bit beyond): the same exact
+ * search with int64 row norms (sum (u-128)^2 <= 16384 d < 2^38).  gl_l2_prepare_wide writes the same int8 rows as gl_l2_prepare and
+ * norms_dev [count] int64; gl_l2_knn_i8_wide takes them and gives the keys gl_l2_knn_i8 gives wherever both apply (d <= 262143), with the
+ * same checks.  Loss('l2') (attack_models/utils.py:163) and custom_knn (attack_models/fbb.py:73-88) at --resolution 512 and above. */
+int gl_l2_prepare_wide(gl_ctx *ctx, const uint8_t *rows_u8_dev, int64_t count, int64_t d, int8_t *rows_i8_dev, int64_t *norms_dev);
+int gl_l2_knn_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, int64_t index_base,
+                      const int8_t *query_i8_dev, const int64_t *query_norm_dev, int64_t nq, int64_t d, uint64_t *keys_dev);
+/* largest d of the exact-integer search: 262143 for gl_l2_prepare / gl_l2_knn_i8 (wide = 0), 2^24 for the wide pair (wide != 0) */
+int64_t gl_l2_max_d(int wide);
 /* keys -> (distance fp32 = fl32(S * 4/(255^2 d)), index int64).  `min_distance.item(), indices[min_index].item()`, fbb.py:88 */
 int gl_keys_unpack(gl_ctx *ctx, const uint64_t *keys_dev, int64_t nq, int64_t d, float *dist_dev, int64_t *idx_dev);
 /* The same exact path for tables of small non-negative integers (x == (float)u, u in 0..255: binary / count rows such as medGAN's thresholded
@@ -134,7 +145,7 @@ int gl_keys_unpack_integers(gl_ctx *ctx, const uint64_t *keys_dev, int64_t nq, i
 
 /* out[i] = fl32(S(x_hat[i], x_gt[b_gt == 1 ? 0 : i]) * 4/(255^2 d)), i < b: the per-sample loss vector
  * Loss('l2').forward(x_hat, x_gt) returns (attack_models/utils.py:163,169,171-177; x_gt broadcasts
- * when it holds one image, fbb.py:79).  u8 rows on the device. */
+ * when it holds one image, fbb.py:79).  u8 rows on the device, d <= gl_l2_max_d(1). */
 int gl_l2_rows_u8(gl_ctx *ctx, const uint8_t *x_hat_u8_dev, int64_t b, const uint8_t *x_gt_u8_dev, int64_t b_gt, int64_t d, float *out_dev);
 
 /* ---- arbitrary fp32 images (values off the 8-bit lattice): fixed-order fp32 evaluation of

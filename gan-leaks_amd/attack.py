@@ -270,6 +270,117 @@ def unpack_keys(ctx, keys, nq, d, kind="u8"):
     return dist.numpy()[:nq], idx.numpy()[:nq]
 
 
+GL_TOPK_MAX = 32
+
+
+def _check_k(k):
+    if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
+        raise TypeError("k must be an integer, got %r" % (k,))
+    if not 1 <= int(k) <= GL_TOPK_MAX:
+        raise ValueError("k must be in [1, %d], got %d" % (GL_TOPK_MAX, int(k)))
+    return int(k)
+
+
+def topk_keys(bank, queries, k, n_rows=None, keys=None):
+    """the k smallest packed keys of every query over bank rows [0, n_rows): DeviceArray [Q, k] (uint64), ascending per query, ~0 in
+    empty slots.  `keys` from an earlier call (another chunk of the bank) is folded in.  Exact-integer banks only ('u8' / 'int', either
+    norm width): the keys of the fp32 paths hold rounded floats."""
+    ctx = bank.ctx
+    k = _check_k(k)
+    if bank.kind not in ("u8", "int"):
+        raise NotImplementedError("top-k needs rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
+    if not isinstance(queries, Bank):
+        queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind=bank.kind, norms64=bank.wide)
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    if queries.kind != bank.kind:
+        raise NotImplementedError("top-k needs queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" % (queries.kind, bank.kind))
+    if queries.wide != bank.wide:
+        raise ValueError("the query Bank has %s row norms, the bank %s: prepare both with the same norms64" %
+                         ("int64" if queries.wide else "int32", "int64" if bank.wide else "int32"))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if keys is None:
+        keys = ctx.empty((max(queries.n, 1), k), np.uint64)
+        check(ctx.lib.gl_topk_init(ctx.handle, _p(keys.ptr), queries.n, k))
+    fn = ctx.lib.gl_l2_topk_i8_wide if bank.wide else ctx.lib.gl_l2_topk_i8
+    check(fn(ctx.handle, _p(bank.rows_i8.ptr), _p(bank.norms.ptr), n_rows, bank.index_base, _p(queries.rows_i8.ptr), _p(queries.norms.ptr),
+             queries.n, bank.d, k, _p(keys.ptr)))
+    return keys, queries, bank.kind
+
+
+def unpack_topk(ctx, keys, nq, k, d, kind="u8"):
+    """[Q, k] keys -> (dist float32 [Q, k], idx int64 [Q, k]); an empty slot gives +inf and -1"""
+    if kind not in ("u8", "int"):
+        raise NotImplementedError("top-k keys exist for the exact-integer kinds 'u8' and 'int' only")
+    dist = ctx.empty((max(nq, 1), k), np.float32)
+    idx = ctx.empty((max(nq, 1), k), np.int64)
+    check(ctx.lib.gl_topk_unpack(ctx.handle, _p(keys.ptr), nq, k, d, 1 if kind == "int" else 0, _p(dist.ptr), _p(idx.ptr)))
+    return dist.numpy()[:nq], idx.numpy()[:nq]
+
+
+def set_topk_workspace(ctx, nbytes):
+    """bytes of pairwise distances one slice of a top-k search may keep on the device (0: the default, 1 GiB).  The result does not
+    depend on it; tests use it to force the slicing."""
+    check(ctx.lib.gl_topk_set_workspace(ctx.handle, int(nbytes)))
+
+
+def _attack_topk(queries, bank, k, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """attack(..., k=k): the bank passes through HBM in chunks like _attack_streamed's (one chunk when it fits), every chunk folds its keys
+    into the same [Q, k] lists."""
+    k = _check_k(k)
+    unsupported = "top-k is built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError(unsupported + "got LPIPS feature rows")
+    prepared = isinstance(bank, Bank)
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx = bank.ctx
+        base = bank.index_base
+    else:
+        ctx = ctx or Context.get()
+        base = int(index_base)
+    shard = reduce_fn is not None or base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    if not shard and k > n_rows:
+        raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_rows))
+    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
+    if fq.kind == "f32":
+        raise NotImplementedError(unsupported + "the queries are off both lattices")
+    keys = None
+    if prepared:
+        keys, _, _ = topk_keys(bank, fq, k, n_rows)
+    else:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
+
+        def rows(lo, hi):
+            if generated:
+                return bank.rows(lo, hi)
+            if isinstance(bank, DeviceArray):
+                return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+            return bank[lo:hi]
+
+        for lo in range(0, n_rows, step):
+            hi = min(lo + step, n_rows)
+            chunk = rows(lo, hi)
+            if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
+                raise NotImplementedError(unsupported + "the queries are an integer table, the bank 8-bit image codes")
+            try:
+                b = Bank.from_images(chunk, ctx, index_base=base + lo, force_kind=fq.kind, norms64=fq.wide)
+            except ValueError as e:
+                raise NotImplementedError(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
+            keys, _, _ = topk_keys(b, fq, k, keys=keys)
+            ctx.sync()
+    if keys is None:                         # a shard without rows still takes part in the reduction
+        keys = ctx.empty((max(fq.n, 1), k), np.uint64)
+        check(ctx.lib.gl_topk_init(ctx.handle, _p(keys.ptr), fq.n, k))
+    if reduce_fn is not None:
+        keys = reduce_fn(keys)
+    return unpack_topk(ctx, keys, fq.n, k, fq.d, fq.kind)
+
+
 def _feature_row_bytes(ctx, model, images):
     h, w = int(images.shape[2]), int(images.shape[3])
     if model.search_rows == "fp16":
@@ -378,7 +489,8 @@ def prepare_queries(queries, distance, ctx=None, lpips=None, comm=None):
     return Bank.from_images(queries, ctx or Context.get(), keep_u8=True, norms64="auto")
 
 
-def attack(queries, bank, distance="l2", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, float_path=None, index_base=0):
+def attack(queries, bank, distance="l2", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, float_path=None, index_base=0,
+           k=None):
     """nearest bank sample of every query.
 
     queries : [Q,C,H,W] images, u8 or float; numpy / torch / DeviceArray / Bank / FeatureBank
@@ -396,9 +508,17 @@ def attack(queries, bank, distance="l2", batch_size=64, ctx=None, reduce_fn=None
     index_base: for an unprepared image array that is one shard of a larger bank: the global index of its row 0 (prepared and generated
               banks carry their own).  Like them, a shard (index_base > 0 or reduce_fn given) is not truncated again.
     float_path: 'exact' | 'mfma' for rows that are on neither lattice (see attack.float_path; default $GANLEAKS_FLOAT_PATH or 'exact').
+    k: None, or 1 <= k <= 32: the k nearest bank samples instead of one -- (dist float32 [Q, k], idx int64 [Q, k]), ordered by
+              (distance, index), column 0 = the k-less result.  distance 'l2' on the exact-integer path only (8-bit images or integer
+              tables on both sides); off-lattice rows and 'l2-lpips' raise NotImplementedError, k > (N // batch_size) * batch_size
+              ValueError.  With reduce_fn the callable receives and returns the [Q, k] key lists (shard.allreduce_topk_keys).
     """
     if distance not in ("l2", "l2-lpips"):
         raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    if k is not None:
+        if distance != "l2":
+            raise NotImplementedError("top-k is built for distance='l2' on the exact-integer path; %r keys hold rounded floats" % (distance,))
+        return _attack_topk(queries, bank, k, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
     prepared = isinstance(bank, Bank) or getattr(bank, "kind", None) == "feat"
     generated = getattr(bank, "kind", None) == "generated"
     if prepared or generated:

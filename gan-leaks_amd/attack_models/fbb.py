@@ -8,6 +8,9 @@ Additions (flagged [build] in SURVEY.md 5): --distance {l2,l2-lpips} (the refere
 'l2-lpips', fbb.py:148); --ngpu N / --devices 0,1,... shard the PNG bank over GPUs (the reference is
 single-device, fbb.py:40): rank r uploads and searches rows [bounds[r], bounds[r+1]) of the sorted file list,
 one all-reduce(min) of the packed keys gives the single-device result bit for bit (ganleaks_amd.shard).
+--knn_out (with --distance l2) also writes the --K nearest samples of every query, from the same pass over the bank:
+{pos,neg}_knn_loss.npy float64 [n, K] and {pos,neg}_knn_idx.npy int64 [n, K], ordered by (distance, index); column 0 is what
+{pos,neg}_loss.npy and {pos,neg}_nn_idx.npy hold.  Without the flag --K is parsed and unused, as in the reference.
 The reference has no `attack()`; the batched entry point named by the project brief lives in
 ganleaks_amd.attack.attack and is re-exported here.
 """
@@ -42,6 +45,8 @@ _FLAGS = (
                            help="[build] distance operator; the reference always uses 'l2-lpips' (fbb.py:148)")),
     (('--ngpu',), dict(type=int, default=1, help='[build] shard the bank over the first N GPUs (one context and host thread per GPU, RCCL min)')),
     (('--devices',), dict(type=str, default=None, help='[build] explicit device ordinals for the shards, e.g. 0,1,2,3 (overrides --ngpu)')),
+    (('--knn_out',), dict(action='store_true', default=False,
+                          help="[build] with --distance l2: also write the --K nearest samples per query (pos/neg_knn_loss.npy, pos/neg_knn_idx.npy)")),
 )
 
 
@@ -72,6 +77,9 @@ def check_args(args):
         save_dir = os.path.join(root, args.exp_name)
     check_folder(save_dir)
     record = vars(args)
+    if not record.get("knn_out", False):
+        # an unset --knn_out leaves the record as it was before the flag existed
+        record = {key: value for key, value in record.items() if key != "knn_out"}
     lines = ["%s:%s" % (key, value) for key, value in record.items()]
     with open(os.path.join(save_dir, 'params.txt'), 'w') as handle:
         handle.write("".join(line + "\n" for line in lines))
@@ -147,6 +155,19 @@ def custom_knn(syn_imgs, sample, loss, args):
     return float(dist[0]), int(idx[0])
 
 
+def custom_knn_k(syn_imgs, sample, loss, args):
+    """custom_knn keeping the args.K nearest samples (fbb.py:35) instead of one, for Loss('l2') on 8-bit images: (list of K distances as
+    python floats, list of K indices as python ints), ordered by (distance, index); entry 0 is custom_knn's result."""
+    if getattr(loss, "distance", None) != "l2":
+        raise NotImplementedError("custom_knn_k is built for Loss('l2') (exact-integer L2); other distances have top-1 only (custom_knn)")
+    n_rows = (len(syn_imgs) // args.BATCH_SIZE) * args.BATCH_SIZE
+    if n_rows == 0:
+        raise ValueError("torch.cat(): expected a non-empty list of Tensors")   # what fbb.py:83 raises
+    q = sample.unsqueeze(0) if hasattr(sample, "unsqueeze") else np.asarray(sample)[None]
+    dist, idx = attack(q, _cached_bank(syn_imgs, n_rows, loss), distance="l2", batch_size=args.BATCH_SIZE, k=int(args.K))
+    return [float(v) for v in dist[0]], [int(v) for v in idx[0]]
+
+
 def plot_closest_images(idx, query_imgs_u8, syn_imgs_u8, save_dir, class_type, num=20):
     """attack_models/fbb.py:91-106: query | nearest sample, side by side, <i><class_type>.png.
     Works on the 8-bit codes directly (the reference converts float -> uint8 with truncation)."""
@@ -174,6 +195,13 @@ def shard_devices(args):
 
 def main(args):
     """attack_models/fbb.py:111-179."""
+    if getattr(args, "knn_out", False):
+        # refused before any file is read
+        if getattr(args, "distance", "l2-lpips") != "l2":
+            raise SystemExit("--knn_out needs --distance l2: the K nearest samples are built for the exact-integer L2 search, "
+                             "'%s' has the nearest sample only" % getattr(args, "distance", "l2-lpips"))
+        if not 1 <= int(args.K) <= 32:
+            raise SystemExit("--knn_out needs 1 <= --K <= 32, got %s" % (args.K,))
     devices = shard_devices(args)
     group = None
     if devices is not None:
@@ -199,7 +227,8 @@ def _main(args, group):
         args.syn_data_path = subdir
         args.params = subdir.split('/')[-1] if args.hyperparameter_search else args.params
         args, save_dir = check_args(args)
-        print(args)
+        # (an unset --knn_out is not echoed either: the output of a plain run is what it was before the flag existed)
+        print(args if getattr(args, 'knn_out', False) else argparse.Namespace(**{key: value for key, value in vars(args).items() if key != 'knn_out'}))
         print('exp_name: ', args.exp_name)
         print('params: ', args.params)
         resolution = args.resolution
@@ -230,10 +259,16 @@ def _main(args, group):
         # prepared rows -- int8 rows or VGG16/LPIPS feature rows -- are built once, and streamed through HBM in chunks when
         # they would not fit (ganleaks_amd.attack, $GANLEAKS_CHUNK_GB)
         n_pos = len(pos_query_imgs)
+        knn_k = int(args.K) if getattr(args, "knn_out", False) else None
         if group is not None:
-            all_d, all_i = group.attack(prepared, bank=syn_imgs, distance=distance, batch_size=args.BATCH_SIZE)
+            all_d, all_i = group.attack(prepared, bank=syn_imgs, distance=distance, batch_size=args.BATCH_SIZE, k=knn_k)
         else:
-            all_d, all_i = attack(prepared, syn_imgs, distance=distance, batch_size=args.BATCH_SIZE, lpips=custom_loss.lpips_model)
+            all_d, all_i = attack(prepared, syn_imgs, distance=distance, batch_size=args.BATCH_SIZE, lpips=custom_loss.lpips_model, k=knn_k)
+        if knn_k is not None:
+            # [build] the K nearest samples; column 0 is the nearest one and feeds the reference's files below
+            save_files(save_dir, ['pos_knn_loss', 'pos_knn_idx'], [all_d[:n_pos].astype(np.float64), all_i[:n_pos]])
+            save_files(save_dir, ['neg_knn_loss', 'neg_knn_idx'], [all_d[n_pos:].astype(np.float64), all_i[n_pos:]])
+            all_d, all_i = np.ascontiguousarray(all_d[:, 0]), np.ascontiguousarray(all_i[:, 0])
         pos_d, pos_i, neg_d, neg_i = all_d[:n_pos], all_i[:n_pos], all_d[n_pos:], all_i[n_pos:]
         pos_loss = pos_d.astype(np.float64).reshape(-1, 1)          # python floats -> float64 [Q,1] (fbb.py:160)
         plt_pos_idx = pos_i.reshape(-1, 1)

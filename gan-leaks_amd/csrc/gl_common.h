@@ -22,6 +22,7 @@ struct gl_ctx {
     int num_cu;              // compute units of the device
     char *pair_scratch;      // lazily allocated workspace of the persistent pairwise kernel: per-workgroup fp32 totals + cluster counters
     size_t pair_scratch_bytes;
+    size_t topk_budget;      // gl_topk_set_workspace: bytes of S values one slice of gl_l2_topk_i8* may occupy (0 = the default, 1 GiB)
     // arena: device blocks of >= 256 MiB that gl_free keeps for the next gl_malloc of (almost) the same size instead of returning them to the
     // driver (allocating and freeing the 153 GiB of query rows of a 256 x 256 attack costs 2-7 s per call); gl_ctx_trim releases them
     std::mutex *arena_mu;

@@ -45,6 +45,16 @@ def merge_keys_host(key_arrays):
     return out
 
 
+def merge_topk_host(key_arrays, k):
+    """the top-k merge on host arrays: every array is [Q, k_i] packed keys (~0 = empty slot); returns [Q, k], per query the k smallest keys
+    of all of them in ascending order, ~0 where fewer than k exist.  What gl_topk_merge computes (tests, the host route of DeviceGroup)."""
+    parts = [np.asarray(a, np.uint64) for a in key_arrays]
+    parts = [a.reshape(len(a), -1) for a in parts]
+    nq = len(parts[0])
+    pad = np.full((nq, int(k)), np.uint64(0xFFFFFFFFFFFFFFFF), np.uint64)
+    return np.sort(np.concatenate(parts + [pad], axis=1), axis=1)[:, :int(k)].copy()
+
+
 class HostMerge:
     """min-merge of per-rank key arrays between the threads of one process (the fallback of attack_on_devices when RCCL cannot form a
     communicator).  merge(rank, keys) blocks until every rank has called it and returns the element-wise minimum; it may be called
@@ -57,10 +67,11 @@ class HostMerge:
         self._barrier = threading.Barrier(self.world)
         self._deposits = [None] * self.world
 
-    def merge(self, rank, keys_host):
+    def merge(self, rank, keys_host, k=None):
+        """k: None for the element-wise minimum of [Q] keys, or the k of [Q, k] top-k lists (merge_topk_host)"""
         self._deposits[rank] = np.asarray(keys_host, np.uint64)
         self._barrier.wait()                                 # every rank has deposited
-        merged = merge_keys_host(self._deposits)
+        merged = merge_keys_host(self._deposits) if k is None else merge_topk_host(self._deposits, k)
         self._barrier.wait()                                 # every rank has merged: the slots may be reused
         return merged
 
@@ -134,6 +145,28 @@ def allreduce_min_keys(keys, group=None, comm=None, _even_alone=False):
     return ctx.to_device(host.numpy().view(np.uint64))
 
 
+def allreduce_topk_keys(keys, k, comm=None):
+    """the top-k counterpart of allreduce_min_keys: every rank's [Q, k] key lists (DeviceArray uint64) are all-gathered
+    (gl_allgather_rows, Q x k x 8 bytes per rank) and folded with gl_topk_merge, both on the context's stream; every rank ends with the k
+    smallest keys of the whole bank.  A world of one (comm None or a single rank) returns its input."""
+    import ctypes
+    from ._lib import check
+    if comm is None or comm.nranks == 1:
+        return keys
+    if keys.dtype != np.dtype(np.uint64):
+        raise TypeError("keys must be uint64")
+    ctx, k = keys.ctx, int(k)
+    nq = int(np.prod(keys.shape, dtype=np.int64)) // k
+    gathered = ctx.empty((comm.nranks, max(nq, 1), k), np.uint64)
+    out = ctx.empty((max(nq, 1), k), np.uint64)
+    p = ctypes.c_void_p
+    check(ctx.lib.gl_allgather_rows(comm.handle, p(keys.ptr), p(gathered.ptr), nq * k * 8))
+    check(ctx.lib.gl_topk_init(ctx.handle, p(out.ptr), nq, k))
+    check(ctx.lib.gl_topk_merge(ctx.handle, p(out.ptr), p(gathered.ptr), nq, k, comm.nranks))
+    ctx.sync()                                               # `gathered` is released on return
+    return out
+
+
 def allreduce_min_keys_host(keys_host, group=None):
     """same reduce for a host uint64 array (pure-CPU rehearsal of the merge with gloo)."""
     import torch
@@ -181,7 +214,7 @@ class DeviceGroup:
         return "rccl" if self.comms is not None else ("host-merge" if self.world > 1 else "none")
 
     def attack(self, queries, make_generator=None, z=None, bank=None, distance="l2", batch_size=64, make_lpips=None, weights=None,
-               **generate_kwargs):
+               k=None, **generate_kwargs):
         """see attack_on_devices"""
         import threading
         from ._lib import DeviceArray
@@ -201,6 +234,13 @@ class DeviceGroup:
         n_eff = (n_total // int(batch_size)) * int(batch_size)
         if n_eff == 0:
             raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+        if k is not None:
+            if distance != "l2":
+                raise NotImplementedError("top-k is built for distance='l2' on the exact-integer path; %r keys hold rounded floats" % (distance,))
+            from .attack import _check_k
+            k = _check_k(k)
+            if k > n_eff:
+                raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_eff))
         bounds = weighted_bounds(n_eff, weights, int(batch_size)) if weights is not None else [n_eff * r // world for r in range(world + 1)]
         host = HostMerge(world)
         ready = threading.Barrier(world)
@@ -209,10 +249,10 @@ class DeviceGroup:
 
         def reduce_fn_for(rank, ctx):
             if comms is not None:
-                return comms[rank].allreduce_min_keys
+                return comms[rank].allreduce_min_keys if k is None else (lambda keys: allreduce_topk_keys(keys, k, comm=comms[rank]))
             if world == 1:
                 return None
-            return lambda keys: ctx.to_device(host.merge(rank, keys.numpy()))
+            return lambda keys: ctx.to_device(host.merge(rank, keys.numpy(), k))
 
         def fail(e, after_setup):
             with lock:
@@ -264,7 +304,7 @@ class DeviceGroup:
                     self._queries[rank] = (qkey, prepare_queries(queries, distance, ctx, model, comm=comms[rank]), queries)
                 prepared = self._queries[rank][1]
                 results[rank] = attack(prepared, shard, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn_for(rank, ctx),
-                                       lpips=model, index_base=lo)
+                                       lpips=model, index_base=lo, k=k)
             except BaseException as e:  # noqa: BLE001
                 fail(e, True)
 
@@ -302,7 +342,7 @@ class DeviceGroup:
 
 
 def attack_on_devices(queries, make_generator=None, z=None, devices=None, distance="l2", batch_size=64, make_lpips=None, weights=None,
-                      bank=None, **generate_kwargs):
+                      bank=None, k=None, **generate_kwargs):
     """One sharded attack on a DeviceGroup built for the call.  The bank is either generated on the devices or handed over:
       make_generator(ctx), z -> rank r generates rows [bounds[r], bounds[r+1]) from z[lo:hi] with a generator bound to its context
                                 (e.g. dcgan.Generator(100, 3, 64, ctx) + load_state_dict); never materialised;
@@ -310,6 +350,7 @@ def attack_on_devices(queries, make_generator=None, z=None, devices=None, distan
                                 reference's fbb.main reads from image_*.png (attack_models/fbb.py:133-135).  Rank r uploads its rows only.
     make_lpips(ctx)     -> an LpipsModel for 'l2-lpips' (default: lpips.model_for(ctx): the registered factory, else the local weight files)
     devices             -> list of device ordinals (default: all visible); weights -> relative speeds for `weighted_bounds`
+    k                   -> None, or 1..32: the k nearest samples, [Q, k] (see attack.attack; 'l2' on the exact-integer path)
     returns (dist float32 [Q], idx int64 [Q]), identical to the single-device result."""
     with DeviceGroup(devices) as group:
-        return group.attack(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, **generate_kwargs)
+        return group.attack(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, k, **generate_kwargs)

@@ -88,6 +88,7 @@ int gl_event_elapsed_ms(void *start, void *stop, float *out_ms);   /* synchronis
 #define GL_PROF_CONVT_RGB 2     /* generator tail: ConvT -> 3 channels + tanh + quantise */
 #define GL_PROF_L2_PREPARE 3    /* u8 -> biased int8 + norms */
 #define GL_PROF_FEAT_KNN 4      /* fp32-MFMA pairwise |V_q - V_n|^2 + argmin (l2-lpips) */
+#define GL_PROF_TOPK_SELECT 5   /* top-K: selection over the stored S values + list merge (the pairwise kernel itself reports as GL_PROF_L2_KNN) */
 int gl_prof_enable(gl_ctx *ctx, int on);
 int gl_prof_read(gl_ctx *ctx, int tag, double *out_total_ms, int64_t *out_launches);
 int gl_prof_reset(gl_ctx *ctx);
@@ -142,6 +143,35 @@ int gl_keys_unpack(gl_ctx *ctx, const uint64_t *keys_dev, int64_t nq, int64_t d,
 int gl_encode_integers_f32(gl_ctx *ctx, const float *x_dev, int64_t count, uint8_t *u8_dev, int32_t *off_lattice_dev);
 int gl_decode_u8_integers(gl_ctx *ctx, const uint8_t *u8_dev, int64_t count, float *x_dev);
 int gl_keys_unpack_integers(gl_ctx *ctx, const uint64_t *keys_dev, int64_t nq, int64_t d, float *dist_dev, int64_t *idx_dev);
+
+/* ---- the K nearest bank rows of every query under the same exact distance, 1 <= k <= GL_TOPK_MAX.
+ * topk_keys_dev is [nq][k] keys, ascending per query: the k smallest keys (S << shift | global index, as gl_l2_knn_i8 packs them) seen so
+ * far, UINT64_MAX in slots that are still empty.  Keys are unique and totally ordered, so ties in S go to the smaller global index in
+ * every column and the lists do not depend on tile, slicing, chunking or sharding; column 0 is the key gl_l2_knn_i8 gives.
+ * This is custom_knn (attack_models/fbb.py:73-88) keeping the args.K nearest samples (fbb.py:35) instead of one. */
+#define GL_TOPK_MAX 32
+/* every slot = UINT64_MAX (empty) */
+int gl_topk_init(gl_ctx *ctx, uint64_t *topk_keys_dev, int64_t nq, int k);
+/* row q of topk_keys_dev = the k smallest of (what it held) and the keys of bank rows [0, n_rows): accumulates like gl_l2_knn_i8, so a
+ * streamed bank is searched chunk by chunk into one list.  Unlike gl_l2_knn_i8's minimum this is not idempotent: every global index
+ * (index_base + n) may be folded into a list at most once, searching the same rows twice leaves duplicate keys in it.
+ * Arguments and checks as gl_l2_knn_i8 / gl_l2_knn_i8_wide.  The pairwise
+ * contraction runs once whatever k is: the kernel stores the exact S of every pair, a selection kernel keeps the k smallest keys.  The S
+ * values of one slice of queries x bank rows live in a workspace from gl_malloc of at most 1 GiB (gl_topk_set_workspace); the library walks
+ * the slices itself and the result does not depend on them.  Synchronises when it returns its workspace (gl_free). */
+int gl_l2_topk_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *bank_norm_dev, int64_t n_rows, int64_t index_base,
+                  const int8_t *query_i8_dev, const int32_t *query_norm_dev, int64_t nq, int64_t d, int k, uint64_t *topk_keys_dev);
+int gl_l2_topk_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, int64_t index_base,
+                       const int8_t *query_i8_dev, const int64_t *query_norm_dev, int64_t nq, int64_t d, int k, uint64_t *topk_keys_dev);
+/* dst[q] = the k smallest of dst[q] and src[l][q], l < n_lists; src_dev is [n_lists][nq][k] (e.g. what gl_allgather_rows delivers from the
+ * ranks of a sharded bank).  Key-agnostic: any lists of ascending unique 64-bit keys. */
+int gl_topk_merge(gl_ctx *ctx, uint64_t *dst_dev, const uint64_t *src_dev, int64_t nq, int k, int64_t n_lists);
+/* [nq][k] keys -> dist_dev [nq][k] fp32, idx_dev [nq][k] int64: gl_keys_unpack (integers = 0) or gl_keys_unpack_integers (integers != 0)
+ * per slot; an empty slot gives +inf and -1. */
+int gl_topk_unpack(gl_ctx *ctx, const uint64_t *topk_keys_dev, int64_t nq, int k, int64_t d, int integers, float *dist_dev, int64_t *idx_dev);
+/* bytes of S values one slice of gl_l2_topk_i8* may occupy (0 = the default of 1 GiB; never less than one tile).  For tests of the slicing
+ * and for hosts that are short of memory; the result does not depend on it. */
+int gl_topk_set_workspace(gl_ctx *ctx, size_t bytes);
 
 /* out[i] = fl32(S(x_hat[i], x_gt[b_gt == 1 ? 0 : i]) * 4/(255^2 d)), i < b: the per-sample loss vector
  * Loss('l2').forward(x_hat, x_gt) returns (attack_models/utils.py:163,169,171-177; x_gt broadcasts

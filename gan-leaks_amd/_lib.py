@@ -83,6 +83,10 @@ SIGNATURES = {
     "gl_topk_merge": (_i, [_p, _p, _p, _i64, _i, _i64]),
     "gl_topk_unpack": (_i, [_p, _p, _i64, _i, _i64, _i, _p, _p]),
     "gl_topk_set_workspace": (_i, [_p, _sz]),
+    "gl_counts_init": (_i, [_p, _p, _i64, _i]),
+    "gl_l2_count_i8": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
+    "gl_l2_count_i8_wide": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
+    "gl_counts_add": (_i, [_p, _p, _p, _i64, _i, _i64]),
     "gl_l2_rows_u8": (_i, [_p, _p, _i64, _p, _i64, _i64, _p]),
     "gl_l2_knn_f32": (_i, [_p, _p, _i64, _i64, _p, _i64, _i64, _p]),
     "gl_keys_unpack_f32": (_i, [_p, _p, _i64, _p, _p]),
@@ -291,7 +295,7 @@ class Context:
     def event(self):
         return Event(self)
 
-    PROF_TAGS = {"gather_conv": 0, "l2_knn": 1, "convt_rgb": 2, "l2_prepare": 3, "feat_knn": 4, "topk_select": 5}
+    PROF_TAGS = {"gather_conv": 0, "l2_knn": 1, "convt_rgb": 2, "l2_prepare": 3, "feat_knn": 4, "topk_select": 5, "l2_count": 6}
 
     def prof_enable(self, on=True):
         check(self.lib.gl_prof_enable(self.handle, 1 if on else 0))

@@ -381,6 +381,181 @@ def _attack_topk(queries, bank, k, batch_size, ctx, reduce_fn, chunk_bytes, inde
     return unpack_topk(ctx, keys, fq.n, k, fq.d, fq.kind)
 
 
+GL_COUNT_MAX_T = 16
+
+
+def _check_eps(eps):
+    """eps (a number or a sequence of 1..GL_COUNT_MAX_T numbers) -> float32 [T]; needs no GPU"""
+    e = np.atleast_1d(np.asarray(eps, np.float64))
+    if e.ndim != 1:
+        raise ValueError("eps must be a number or a flat sequence of numbers, got shape %r" % (e.shape,))
+    if not 1 <= len(e) <= GL_COUNT_MAX_T:
+        raise ValueError("eps must hold 1..%d values, got %d" % (GL_COUNT_MAX_T, len(e)))
+    if np.any(np.isnan(e)):
+        raise ValueError("eps holds NaN")
+    with np.errstate(over="ignore"):
+        return e.astype(np.float32)
+
+
+def _dist32(S, d, kind):
+    """the float32 distance gl_keys_unpack ('u8') / gl_keys_unpack_integers ('int') give for the exact sum of squared differences S"""
+    if kind == "int":
+        return np.float32(np.float64(S) / np.float64(d))
+    return np.float32(np.float64(S) * (4.0 / (65025.0 * float(d))))
+
+
+def eps_to_ssd(eps, d, kind="u8"):
+    """the largest exact sum of squared differences S whose float32 distance -- fl32(S * 4 / (65025 d)) for 8-bit images ('u8'),
+    fl32(S / d) for integer tables ('int'): what attack() returns -- is <= float32(eps): int64 [T], -1 where no S qualifies, at most
+    65025 d (the largest S there is).  The float32 distance is non-decreasing in S, so dist <= eps  <=>  S <= eps_to_ssd(eps): the
+    thresholds of gl_l2_count_i8.  A float64 estimate of eps / scale, then corrected by stepping (in doubling strides) for as long as the
+    float32 comparison itself says so.  Host only."""
+    if kind not in ("u8", "int"):
+        raise ValueError("kind must be 'u8' or 'int', got %r" % (kind,))
+    d = int(d)
+    if d <= 0:
+        raise ValueError("d must be positive")
+    e32 = _check_eps(eps)
+    s_max = 65025 * d
+    out = np.empty(len(e32), np.int64)
+
+    def ok(s):
+        return bool(_dist32(s, d, kind) <= e)
+
+    for t, e in enumerate(e32):
+        if e < 0:
+            out[t] = -1
+            continue
+        if np.isinf(e) or ok(s_max):
+            out[t] = s_max
+            continue
+        est = float(e) * d if kind == "int" else float(e) / (4.0 / (65025.0 * d))
+        s = min(max(int(est), 0), s_max)
+        # bracket: lo qualifies (or is -1), hi does not; then bisect
+        step = 1
+        if ok(s):
+            lo = s
+            while ok(min(lo + step, s_max)):           # ok(s_max) is False here
+                lo, step = lo + step, step * 2
+            hi = min(lo + step, s_max)
+        else:
+            hi = s
+            while hi - step >= 0 and not ok(hi - step):
+                hi, step = hi - step, step * 2
+            lo = max(hi - step, -1)
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if ok(mid):
+                lo = mid
+            else:
+                hi = mid
+        out[t] = lo
+    return out
+
+
+def count_balls(bank, queries, thr, n_rows=None, counts=None):
+    """launch the counting kernel: counts DeviceArray [Q, T] (uint64), counts[q, t] += #{ n < n_rows : S(q, n) <= thr[t] } for the ascending
+    int64 thresholds `thr` on S (eps_to_ssd).  `counts` from an earlier call (another chunk of the bank) is added to.  Exact-integer banks only
+    ('u8' / 'int', either norm width).  Asynchronous."""
+    ctx = bank.ctx
+    if bank.kind not in ("u8", "int"):
+        raise NotImplementedError("ball counts need rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
+    if not isinstance(queries, Bank):
+        queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind=bank.kind, norms64=bank.wide)
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    if queries.kind != bank.kind:
+        raise NotImplementedError("ball counts need queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" %
+                                  (queries.kind, bank.kind))
+    if queries.wide != bank.wide:
+        raise ValueError("the query Bank has %s row norms, the bank %s: prepare both with the same norms64" %
+                         ("int64" if queries.wide else "int32", "int64" if bank.wide else "int32"))
+    thr = np.ascontiguousarray(thr, np.int64)
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if counts is None:
+        counts = new_counts(ctx, queries.n, len(thr))
+    fn = ctx.lib.gl_l2_count_i8_wide if bank.wide else ctx.lib.gl_l2_count_i8
+    check(fn(ctx.handle, _p(bank.rows_i8.ptr), _p(bank.norms.ptr), n_rows, _p(queries.rows_i8.ptr), _p(queries.norms.ptr), queries.n, bank.d,
+             thr.ctypes.data_as(_p), len(thr), _p(counts.ptr)))
+    return counts, queries, bank.kind
+
+
+def new_counts(ctx, nq, n_thr):
+    """zeroed counters DeviceArray [max(nq, 1), n_thr] uint64 (gl_counts_init)"""
+    counts = ctx.empty((max(int(nq), 1), int(n_thr)), np.uint64)
+    check(ctx.lib.gl_counts_init(ctx.handle, _p(counts.ptr), max(int(nq), 1), int(n_thr)))
+    return counts
+
+
+def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0):
+    """how many bank samples lie within eps of every query: the Monte-Carlo / eps-ball membership score (Hilprecht et al., PoPETs 2019) is
+    counts / n_eff, over the bank and the 'l2' distance attack() searches.
+
+    eps     : a float or a sequence of 1..16 floats, any order, repeats allowed; column t of the result belongs to eps[t].
+    returns counts int64 [Q, T]: counts[q, t] = #{ n < n_eff : dist32(S(q, n)) <= float32(eps[t]) }, dist32 the float32 distance attack()
+              returns for the exact S (see eps_to_ssd), n_eff = (N // batch_size) * batch_size unless the bank is a shard (index_base != 0 or
+              reduce_fn given) -- attack()'s rule.  So counts[q, t] >= 1  <=>  attack()'s distance of q is <= eps[t].
+    queries, bank, batch_size, ctx, chunk_bytes, index_base: as attack(..., distance='l2', k=...): images (numpy / torch / DeviceArray), a
+              prepared `Bank`, a `GeneratedBank`; banks beyond `chunk_bytes` are streamed and the counters accumulate across the chunks.
+              Exact-integer L2 only: rows off both lattices raise NotImplementedError (the fp32 paths hold rounded distances).
+    reduce_fn: optional callable(counts DeviceArray [Q, T] uint64) -> DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts)."""
+    e32 = _check_eps(eps)                    # before any Context: these checks run without a GPU
+    unsupported = "ball counts are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError(unsupported + "got LPIPS feature rows")
+    prepared = isinstance(bank, Bank)
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx = bank.ctx
+        base = bank.index_base
+    else:
+        ctx = ctx or Context.get()
+        base = int(index_base)
+    shard = reduce_fn is not None or base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    if prepared and bank.kind == "f32":
+        raise NotImplementedError(unsupported + "the bank is off both lattices")
+    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
+    if fq.kind == "f32":
+        raise NotImplementedError(unsupported + "the queries are off both lattices")
+    # the library sees the thresholds sorted; the columns are put back in the caller's order at the end
+    thr = eps_to_ssd(e32, fq.d, fq.kind)
+    order = np.argsort(thr, kind="stable")
+    counts = new_counts(ctx, fq.n, len(thr))              # fresh counters per call
+    if prepared:
+        count_balls(bank, fq, thr[order], n_rows, counts)
+    else:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
+
+        def rows(lo, hi):
+            if generated:
+                return bank.rows(lo, hi)
+            if isinstance(bank, DeviceArray):
+                return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+            return bank[lo:hi]
+
+        for lo in range(0, n_rows, step):
+            hi = min(lo + step, n_rows)
+            chunk = rows(lo, hi)
+            if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
+                raise NotImplementedError(unsupported + "the queries are an integer table, the bank 8-bit image codes")
+            try:
+                b = Bank.from_images(chunk, ctx, index_base=base + lo, force_kind=fq.kind, norms64=fq.wide)
+            except ValueError as e:
+                raise NotImplementedError(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
+            count_balls(b, fq, thr[order], counts=counts)
+            ctx.sync()
+    if reduce_fn is not None:                # (a shard without rows takes part with zeros)
+        counts = reduce_fn(counts)
+    host = counts.numpy()[:fq.n]
+    out = np.empty((fq.n, len(thr)), np.int64)
+    out[:, order] = host.astype(np.int64)
+    return out
+
+
 def _feature_row_bytes(ctx, model, images):
     h, w = int(images.shape[2]), int(images.shape[3])
     if model.search_rows == "fp16":

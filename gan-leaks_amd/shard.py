@@ -55,6 +55,15 @@ def merge_topk_host(key_arrays, k):
     return np.sort(np.concatenate(parts + [pad], axis=1), axis=1)[:, :int(k)].copy()
 
 
+def merge_counts_host(count_arrays):
+    """the cross-shard reduction of ball counts on host arrays: the element-wise sum of [Q, T] counters (what gl_counts_add computes; tests,
+    the host route of DeviceGroup)."""
+    out = np.asarray(count_arrays[0], np.uint64).copy()
+    for c in count_arrays[1:]:
+        out += np.asarray(c, np.uint64)
+    return out
+
+
 class HostMerge:
     """min-merge of per-rank key arrays between the threads of one process (the fallback of attack_on_devices when RCCL cannot form a
     communicator).  merge(rank, keys) blocks until every rank has called it and returns the element-wise minimum; it may be called
@@ -67,11 +76,15 @@ class HostMerge:
         self._barrier = threading.Barrier(self.world)
         self._deposits = [None] * self.world
 
-    def merge(self, rank, keys_host, k=None):
-        """k: None for the element-wise minimum of [Q] keys, or the k of [Q, k] top-k lists (merge_topk_host)"""
+    def merge(self, rank, keys_host, k=None, op="min"):
+        """k: None for the element-wise minimum of [Q] keys, or the k of [Q, k] top-k lists (merge_topk_host); op='sum': the element-wise
+        sum of [Q, T] ball counts instead (merge_counts_host)"""
         self._deposits[rank] = np.asarray(keys_host, np.uint64)
         self._barrier.wait()                                 # every rank has deposited
-        merged = merge_keys_host(self._deposits) if k is None else merge_topk_host(self._deposits, k)
+        if op == "sum":
+            merged = merge_counts_host(self._deposits)
+        else:
+            merged = merge_keys_host(self._deposits) if k is None else merge_topk_host(self._deposits, k)
         self._barrier.wait()                                 # every rank has merged: the slots may be reused
         return merged
 
@@ -167,6 +180,28 @@ def allreduce_topk_keys(keys, k, comm=None):
     return out
 
 
+def allreduce_sum_counts(counts, comm=None, _even_alone=False):
+    """the ball-count counterpart of allreduce_topk_keys: every rank's [Q, T] counters (DeviceArray uint64) are all-gathered
+    (gl_allgather_rows, Q x T x 8 bytes per rank) and summed with gl_counts_add, both on the context's stream; every rank ends with the
+    counts over the whole bank.  A world of one (comm None or a single rank) returns its input."""
+    import ctypes
+    from ._lib import check
+    if comm is None or (comm.nranks == 1 and not _even_alone):
+        return counts
+    if counts.dtype != np.dtype(np.uint64) or len(counts.shape) != 2:
+        raise TypeError("counts must be uint64 [Q, T]")
+    ctx = counts.ctx
+    nq, n_thr = counts.shape
+    gathered = ctx.empty((comm.nranks, nq, n_thr), np.uint64)
+    out = ctx.empty((nq, n_thr), np.uint64)
+    p = ctypes.c_void_p
+    check(ctx.lib.gl_allgather_rows(comm.handle, p(counts.ptr), p(gathered.ptr), nq * n_thr * 8))
+    check(ctx.lib.gl_counts_init(ctx.handle, p(out.ptr), nq, n_thr))
+    check(ctx.lib.gl_counts_add(ctx.handle, p(out.ptr), p(gathered.ptr), nq, n_thr, comm.nranks))
+    ctx.sync()                                               # `gathered` is released on return
+    return out
+
+
 def allreduce_min_keys_host(keys_host, group=None):
     """same reduce for a host uint64 array (pure-CPU rehearsal of the merge with gloo)."""
     import torch
@@ -216,9 +251,62 @@ class DeviceGroup:
     def attack(self, queries, make_generator=None, z=None, bank=None, distance="l2", batch_size=64, make_lpips=None, weights=None,
                k=None, **generate_kwargs):
         """see attack_on_devices"""
+        from .attack import attack
+        k_of = []                                             # [k as validate() normalised it]: filled before any closure below runs
+
+        def validate(n_eff):
+            kk = k
+            if kk is not None:
+                if distance != "l2":
+                    raise NotImplementedError("top-k is built for distance='l2' on the exact-integer path; %r keys hold rounded floats" % (distance,))
+                from .attack import _check_k
+                kk = _check_k(kk)
+                if kk > n_eff:
+                    raise ValueError("k=%d exceeds the %d bank rows that take part" % (kk, n_eff))
+            k_of.append(kk)
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            kk = k_of[0]
+            if comms is not None:
+                return comms[rank].allreduce_min_keys if kk is None else (lambda keys: allreduce_topk_keys(keys, kk, comm=comms[rank]))
+            if self.world == 1:
+                return None
+            return lambda keys: ctx.to_device(host.merge(rank, keys.numpy(), kk))
+
+        def call(prepared, shard, ctx, reduce_fn, model, lo):
+            return attack(prepared, shard, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, lpips=model, index_base=lo, k=k_of[0])
+
+        return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call)
+
+    def ball_counts(self, queries, make_generator=None, z=None, bank=None, eps=None, batch_size=64, weights=None, **generate_kwargs):
+        """attack.ball_counts over the group's contexts: rank r counts over rows [bounds[r], bounds[r+1]) of the bank (handed over or
+        generated, as in attack_on_devices), the [Q, T] counters are summed across the ranks (allreduce_sum_counts, or on the host where RCCL
+        cannot form the communicator).  int64 [Q, T], identical to the single-device result.  The queries are prepared once per context and
+        shared with attack(distance='l2') on the same array."""
+        from .attack import _check_eps, ball_counts
+        if eps is None:
+            raise ValueError("needs eps")
+        eps = _check_eps(eps)
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            if comms is not None:
+                return lambda counts: allreduce_sum_counts(counts, comm=comms[rank])
+            if self.world == 1:
+                return None
+            return lambda counts: ctx.to_device(host.merge(rank, counts.numpy(), op="sum"))
+
+        def call(prepared, shard, ctx, reduce_fn, model, lo):
+            return ball_counts(prepared, shard, eps, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, index_base=lo)
+
+        return self._run(queries, make_generator, z, bank, "l2", batch_size, None, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
+
+    def _run(self, queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call):
+        """the worker scaffolding of one sharded job: a host thread per context, the fallible setup before a rendezvous, the failure vote.
+        validate(n_eff) checks the job's own arguments; reduce_fn_for(rank, ctx, comms, host) gives the rank's cross-shard reduction;
+        call(prepared queries, shard, ctx, reduce_fn, model, lo) is the per-rank job.  Returns rank 0's result."""
         import threading
         from ._lib import DeviceArray
-        from .attack import GeneratedBank, attack, prepare_queries
+        from .attack import GeneratedBank, prepare_queries
         if self._broken:
             raise RuntimeError("this DeviceGroup failed in an earlier call; build a new one")
         if (bank is None) == (make_generator is None):
@@ -234,25 +322,12 @@ class DeviceGroup:
         n_eff = (n_total // int(batch_size)) * int(batch_size)
         if n_eff == 0:
             raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-        if k is not None:
-            if distance != "l2":
-                raise NotImplementedError("top-k is built for distance='l2' on the exact-integer path; %r keys hold rounded floats" % (distance,))
-            from .attack import _check_k
-            k = _check_k(k)
-            if k > n_eff:
-                raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_eff))
+        validate(n_eff)
         bounds = weighted_bounds(n_eff, weights, int(batch_size)) if weights is not None else [n_eff * r // world for r in range(world + 1)]
         host = HostMerge(world)
         ready = threading.Barrier(world)
         results, errors, lock = [None] * world, [], threading.Lock()
         qkey = (id(queries), distance, tuple(getattr(queries, "shape", ())))
-
-        def reduce_fn_for(rank, ctx):
-            if comms is not None:
-                return comms[rank].allreduce_min_keys if k is None else (lambda keys: allreduce_topk_keys(keys, k, comm=comms[rank]))
-            if world == 1:
-                return None
-            return lambda keys: ctx.to_device(host.merge(rank, keys.numpy(), k))
 
         def fail(e, after_setup):
             with lock:
@@ -303,8 +378,7 @@ class DeviceGroup:
                     # all-gathered: a collective, hence behind the rendezvous
                     self._queries[rank] = (qkey, prepare_queries(queries, distance, ctx, model, comm=comms[rank]), queries)
                 prepared = self._queries[rank][1]
-                results[rank] = attack(prepared, shard, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn_for(rank, ctx),
-                                       lpips=model, index_base=lo, k=k)
+                results[rank] = call(prepared, shard, ctx, reduce_fn_for(rank, ctx, comms, host), model, lo)
             except BaseException as e:  # noqa: BLE001
                 fail(e, True)
 
@@ -354,3 +428,10 @@ def attack_on_devices(queries, make_generator=None, z=None, devices=None, distan
     returns (dist float32 [Q], idx int64 [Q]), identical to the single-device result."""
     with DeviceGroup(devices) as group:
         return group.attack(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, k, **generate_kwargs)
+
+
+def ball_counts_on_devices(queries, make_generator=None, z=None, devices=None, eps=None, batch_size=64, weights=None, bank=None, **generate_kwargs):
+    """attack.ball_counts sharded over a DeviceGroup built for the call (arguments as attack_on_devices): int64 [Q, T], identical to the
+    single-device counts."""
+    with DeviceGroup(devices) as group:
+        return group.ball_counts(queries, make_generator, z, bank, eps, batch_size, weights, **generate_kwargs)

@@ -89,6 +89,7 @@ int gl_event_elapsed_ms(void *start, void *stop, float *out_ms);   /* synchronis
 #define GL_PROF_L2_PREPARE 3    /* u8 -> biased int8 + norms */
 #define GL_PROF_FEAT_KNN 4      /* fp32-MFMA pairwise |V_q - V_n|^2 + argmin (l2-lpips) */
 #define GL_PROF_TOPK_SELECT 5   /* top-K: selection over the stored S values + list merge (the pairwise kernel itself reports as GL_PROF_L2_KNN) */
+#define GL_PROF_L2_COUNT 6      /* int8-MFMA pairwise L2 + epsilon-ball counts (gl_l2_count_i8*) */
 int gl_prof_enable(gl_ctx *ctx, int on);
 int gl_prof_read(gl_ctx *ctx, int tag, double *out_total_ms, int64_t *out_launches);
 int gl_prof_reset(gl_ctx *ctx);
@@ -172,6 +173,28 @@ int gl_topk_unpack(gl_ctx *ctx, const uint64_t *topk_keys_dev, int64_t nq, int k
 /* bytes of S values one slice of gl_l2_topk_i8* may occupy (0 = the default of 1 GiB; never less than one tile).  For tests of the slicing
  * and for hosts that are short of memory; the result does not depend on it. */
 int gl_topk_set_workspace(gl_ctx *ctx, size_t bytes);
+
+/* ---- epsilon-ball counts under the same exact distance: how many bank rows lie within each of T thresholds of every query.  The score of
+ * the Monte-Carlo membership attack (Hilprecht et al., PoPETs 2019) is counts / n over the bank custom_knn searches
+ * (attack_models/fbb.py:73-88) and the per-sample distance of Loss('l2') (attack_models/utils.py:161-164); several thresholds in one pass give
+ * the per-query distance CDF.  counts_dev is [nq][n_thr] uint64.  Counts are integers of an exact S: they do not depend on tile, chunking or
+ * sharding. */
+#define GL_COUNT_MAX_T 16
+/* every counter = 0 */
+int gl_counts_init(gl_ctx *ctx, uint64_t *counts_dev, int64_t nq, int n_thr);
+/* counts[q][t] += #{ n in [0, n_rows) : S(q, n) <= thr_host[t] }, S as in gl_l2_knn_i8.  thr_host: n_thr (1..GL_COUNT_MAX_T) thresholds on S in
+ * HOST memory, ascending (equal neighbours allowed); a negative value means "no pair qualifies", a value above 65025 d "every pair".
+ * Accumulates, so a streamed bank is counted chunk by chunk into one table; counting the same rows twice counts them twice.  No bank index is
+ * involved (no index_base).  Other arguments and checks as gl_l2_knn_i8 / gl_l2_knn_i8_wide; n_rows == 0 or nq == 0 is GL_OK.  One kernel, no
+ * workspace: no pairwise value is written to memory.  Asynchronous on the context's stream. */
+int gl_l2_count_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
+                   const int32_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *thr_host, int n_thr, uint64_t *counts_dev);
+/* the same for rows prepared by gl_l2_prepare_wide (int64 norms, d <= gl_l2_max_d(1)); equal to gl_l2_count_i8 wherever both apply */
+int gl_l2_count_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
+                        const int64_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *thr_host, int n_thr, uint64_t *counts_dev);
+/* dst[q][t] += sum over l < n_lists of src[l][q][t]; src_dev is [n_lists][nq][n_thr] (e.g. what gl_allgather_rows delivers from the ranks of a
+ * sharded bank): the cross-shard sum, the counterpart of gl_topk_merge. */
+int gl_counts_add(gl_ctx *ctx, uint64_t *dst_dev, const uint64_t *src_dev, int64_t nq, int n_thr, int64_t n_lists);
 
 /* out[i] = fl32(S(x_hat[i], x_gt[b_gt == 1 ? 0 : i]) * 4/(255^2 d)), i < b: the per-sample loss vector
  * Loss('l2').forward(x_hat, x_gt) returns (attack_models/utils.py:163,169,171-177; x_gt broadcasts

@@ -144,6 +144,10 @@ SIGNATURES = {
     "gl_lpips_search_features_f32": (_i, [_p, _p, _i64, _i, _i, _i, _p, _p]),
     "gl_feat_knn_h1": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _p]),
     "gl_feat_knn_h1_scaled": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _p, ctypes.c_float]),
+    "gl_feat_count_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _i, _i, _i, _p]),
+    "gl_feat_count": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _i, _i, _p]),
+    "gl_feat_pair_dist_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _i64]),
+    "gl_feat_pair_dist": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i64]),
     "gl_feat_rows_dist": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64, _p, _p]),
     "gl_comm_unique_id": (_i, [_p]),
     "gl_comm_init_rank": (_i, [_p, _p, _i, _i, _pp]),
@@ -295,7 +299,7 @@ class Context:
     def event(self):
         return Event(self)
 
-    PROF_TAGS = {"gather_conv": 0, "l2_knn": 1, "convt_rgb": 2, "l2_prepare": 3, "feat_knn": 4, "topk_select": 5, "l2_count": 6}
+    PROF_TAGS = {"gather_conv": 0, "l2_knn": 1, "convt_rgb": 2, "l2_prepare": 3, "feat_knn": 4, "topk_select": 5, "l2_count": 6, "feat_count": 7}
 
     def prof_enable(self, on=True):
         check(self.lib.gl_prof_enable(self.handle, 1 if on else 0))

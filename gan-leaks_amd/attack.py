@@ -487,9 +487,9 @@ def new_counts(ctx, nq, n_thr):
     return counts
 
 
-def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0):
+def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0, distance="l2", lpips=None):
     """how many bank samples lie within eps of every query: the Monte-Carlo / eps-ball membership score (Hilprecht et al., PoPETs 2019) is
-    counts / n_eff, over the bank and the 'l2' distance attack() searches.
+    counts / n_eff, over the bank and the distance attack() searches: 'l2' (the default) or 'l2-lpips'.
 
     eps     : a float or a sequence of 1..16 floats, any order, repeats allowed; column t of the result belongs to eps[t].
     returns counts int64 [Q, T]: counts[q, t] = #{ n < n_eff : dist32(S(q, n)) <= float32(eps[t]) }, dist32 the float32 distance attack()
@@ -498,8 +498,18 @@ def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chu
     queries, bank, batch_size, ctx, chunk_bytes, index_base: as attack(..., distance='l2', k=...): images (numpy / torch / DeviceArray), a
               prepared `Bank`, a `GeneratedBank`; banks beyond `chunk_bytes` are streamed and the counters accumulate across the chunks.
               Exact-integer L2 only: rows off both lattices raise NotImplementedError (the fp32 paths hold rounded distances).
-    reduce_fn: optional callable(counts DeviceArray [Q, T] uint64) -> DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts)."""
+    reduce_fn: optional callable(counts DeviceArray [Q, T] uint64) -> DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts).
+    distance='l2-lpips' (0.2 * LPIPS + L2, the reference's fbb distance: attack_models/fbb.py:148, utils.py:166-176; `lpips`: the LpipsModel,
+              default lpips.default_model()): counts[q, t] = #{ n < n_eff : D32(q, n) <= float32(eps[t]) } with D32 the float32 distance
+              attack(..., distance='l2-lpips') minimises, bit for bit (the search kernel with a counting epilogue), so again
+              counts[q, t] >= 1  <=>  attack()'s distance of q is <= eps[t]; negative radii count nothing, inf counts n_eff.  Accepts what
+              attack(distance='l2-lpips') accepts: u8 or float images (off-lattice floats put both sides in the hi / lo layout), prepared
+              FeatureBanks, a GeneratedBank; banks beyond `chunk_bytes` are streamed, query sets beyond the query budget go in slices."""
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
     e32 = _check_eps(eps)                    # before any Context: these checks run without a GPU
+    if distance == "l2-lpips":
+        return _ball_counts_lpips(queries, bank, e32, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base)
     unsupported = "ball counts are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
     if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
         raise NotImplementedError(unsupported + "got LPIPS feature rows")
@@ -565,10 +575,32 @@ def _feature_row_bytes(ctx, model, images):
     return 4 * int(ctx.lib.gl_lpips_feature_dim(h, w))
 
 
-def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath=None, index_base=0):
+def _lpips_resident_rows(queries, bank, prepared, model, index_base):
+    """(bank rows, query rows) of a resident 'l2-lpips' search as FeatureBanks: `bank` is a FeatureBank (prepared) or the images that take
+    part; `queries` a FeatureBank or images"""
+    q_feat = getattr(queries, "kind", None) == "feat"
+    fb = bank if prepared else model.features(bank, index_base=index_base, role=model.search_role("bank"),
+                                              fmt=getattr(queries, "fmt", None) if q_feat else None)
+    q_role = "query" if getattr(fb, "role", None) else None          # queries follow the bank's row format
+    if q_feat:
+        return fb, queries
+    try:
+        fq = model.features(queries, role=q_role, fmt=getattr(fb, "fmt", None))
+    except ValueError:
+        # off-lattice float queries against lattice rows of an 8-bit bank: both sides in the hi / lo layout instead
+        if prepared or getattr(fb, "fmt", None) != "lattice":
+            raise
+        fb = model.features(bank, index_base=index_base, role="bank", fmt="hilo")
+        fq = model.features(queries, role="query", fmt="hilo")
+    return fb, fq
+
+
+def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath=None, index_base=0, count_thr=None):
     """bank rows [0, n_rows) pass through HBM in chunks of at most `chunk_bytes` of prepared rows (int8 rows for 'l2', feature
     rows for 'l2-lpips'); the packed keys accumulate the minimum across chunks (atomicMin), so the result is the one the
-    resident form gives.  `bank` is a GeneratedBank or a host array / DeviceArray of images (`index_base`: global index of its row 0)."""
+    resident form gives.  `bank` is a GeneratedBank or a host array / DeviceArray of images (`index_base`: global index of its row 0).
+    count_thr ('l2-lpips' only; ascending float32 thresholds): the same stream with lpips.feat_count in place of the search -- the [Q, T]
+    counters accumulate across chunks, reduce_fn is the cross-shard sum, and the result is the host array of counts, uint64 [Q, T]."""
     generated = getattr(bank, "kind", None) == "generated"
     base = bank.index_base if generated else int(index_base)
 
@@ -578,6 +610,11 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
         return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1))) if isinstance(bank, DeviceArray) else bank[lo:hi]
 
     def finish(keys, nq, d, kind):
+        if count_thr is not None:
+            counts = new_counts(ctx, nq, len(count_thr)) if keys is None else keys
+            if reduce_fn is not None:
+                counts = reduce_fn(counts)
+            return counts.numpy()[:nq]
         if keys is None:                 # a shard without rows still takes part in the reduction
             keys = ctx.empty((max(nq, 1),), np.uint64)
             check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), nq))
@@ -593,8 +630,10 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
             per_q = _feature_row_bytes(ctx, model, queries)
             q_step = max(1, int(_query_budget_bytes(chunk_bytes, ctx) // per_q))
             if len(queries) > q_step:
-                parts = [_attack_streamed(queries[a:a + q_step], bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath, index_base)
+                parts = [_attack_streamed(queries[a:a + q_step], bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath, index_base, count_thr)
                          for a in range(0, len(queries), q_step)]
+                if count_thr is not None:
+                    return np.concatenate(parts)
                 return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
         raw_queries = getattr(queries, "kind", None) != "feat"
         fq = model.features(queries, role=model.search_role("query")) if raw_queries else queries
@@ -615,7 +654,7 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
                         raise
                     ok = False
                     break
-                keys = _lp.feat_knn_keys(buf, fq, keys=keys)
+                keys = _lp.feat_knn_keys(buf, fq, keys=keys) if count_thr is None else _lp.feat_count(buf, fq, count_thr, counts=keys)
                 ctx.sync()
             if ok:
                 return finish(keys, fq.n, fq.K, "f32")
@@ -662,6 +701,80 @@ def prepare_queries(queries, distance, ctx=None, lpips=None, comm=None):
             return _lp.features_sharded(model, queries, comm)
         return model.features(queries, role=model.search_role("query"))
     return Bank.from_images(queries, ctx or Context.get(), keep_u8=True, norms64="auto")
+
+
+def _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base):
+    """(prepared, generated, ctx, index_base, n_rows) of an 'l2-lpips' bank by attack()'s rule: n_rows = (N // batch_size) * batch_size
+    unless the bank is a shard (index_base != 0 or reduce_fn given)"""
+    if isinstance(bank, Bank):
+        raise TypeError("this Bank holds int8 rows for distance='l2'; 'l2-lpips' needs images, a FeatureBank or a GeneratedBank")
+    prepared = getattr(bank, "kind", None) == "feat"
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx, index_base = bank.ctx, bank.index_base
+    else:
+        ctx, index_base = ctx or Context.get(), int(index_base)
+    shard = reduce_fn is not None or index_base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    return prepared, generated, ctx, index_base, n_rows
+
+
+def _ball_counts_lpips(queries, bank, e32, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base):
+    """ball_counts(distance='l2-lpips'): attack()'s resident / streamed decision and row preparation, lpips.feat_count for the search"""
+    from . import lpips as _lp
+    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
+    if model is None and not (prepared and getattr(queries, "kind", None) == "feat"):      # prepared rows on both sides need no VGG16
+        model = _lp.default_model()
+    # the library sees the radii sorted; the columns are put back in the caller's order at the end
+    order = np.argsort(e32, kind="stable")
+    thr = np.ascontiguousarray(e32[order])
+    host = None
+    if not prepared:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
+            need = chunk_bytes + 1
+        else:
+            per_img = _feature_row_bytes(ctx, model, bank)
+            need = per_img * n_rows
+            if getattr(queries, "kind", None) != "feat" and len(queries) * per_img > chunk_bytes:
+                need = chunk_bytes + 1       # the query rows alone exceed a chunk: streamed form (queries resident or in slices)
+        if need > chunk_bytes:
+            host = _attack_streamed(queries, bank, n_rows, "l2-lpips", ctx, reduce_fn, model, chunk_bytes, None, index_base, count_thr=thr)
+        else:
+            bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
+    if host is None:
+        fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
+        counts = _lp.feat_count(fb, fq, thr, n_rows)
+        if reduce_fn is not None:
+            counts = reduce_fn(counts)
+        host = counts.numpy()[:fq.n]
+    out = np.empty((len(host), len(thr)), np.int64)
+    out[:, order] = host.astype(np.int64)
+    return out
+
+
+def pair_distances(queries, bank, distance="l2-lpips", batch_size=64, lpips=None):
+    """the distance matrix attack(..., distance='l2-lpips') minimises over and ball_counts(..., distance='l2-lpips') counts in, float32
+    [Q, n_eff]: M[q, n] = D32(q, n), n_eff by attack()'s rule, so M.min(axis=1) / the first argmin are attack()'s (dist, idx) and
+    (M <= float32(eps)).sum(axis=1) is ball_counts'.  For small cases (the histogram a radius is read from): everything is resident, and a
+    matrix beyond 1 GiB raises ValueError.  queries, bank: images or FeatureBanks."""
+    if distance != "l2-lpips":
+        raise ValueError("pair_distances is built for distance='l2-lpips', got %r" % (distance,))
+    from . import lpips as _lp
+    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, None, None, 0)
+    if generated:
+        raise TypeError("pair_distances needs a materialised bank (images or a FeatureBank)")
+    if getattr(queries, "kind", None) != "feat" and len(queries) * n_rows * 4 > _lp.PAIR_DIST_MAX_BYTES:
+        raise ValueError("a %d x %d distance matrix exceeds 1 GiB; pair_distances is for small cases" % (len(queries), n_rows))
+    model = lpips
+    if model is None and not (prepared and getattr(queries, "kind", None) == "feat"):
+        model = _lp.default_model()
+    if not prepared:
+        bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
+    fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
+    return _lp.feat_pair_dist(fb, fq, n_rows)
 
 
 def attack(queries, bank, distance="l2", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, float_path=None, index_base=0,
@@ -736,21 +849,7 @@ def attack(queries, bank, distance="l2", batch_size=64, ctx=None, reduce_fn=None
             bank = bank[:n_rows]
 
     if distance == "l2-lpips":
-        q_feat = getattr(queries, "kind", None) == "feat"
-        fb = bank if prepared else model.features(bank, index_base=index_base, role=model.search_role("bank"),
-                                                  fmt=getattr(queries, "fmt", None) if q_feat else None)
-        q_role = "query" if getattr(fb, "role", None) else None          # queries follow the bank's row format
-        if q_feat:
-            fq = queries
-        else:
-            try:
-                fq = model.features(queries, role=q_role, fmt=getattr(fb, "fmt", None))
-            except ValueError:
-                # off-lattice float queries against lattice rows of an 8-bit bank: both sides in the hi / lo layout instead
-                if prepared or getattr(fb, "fmt", None) != "lattice":
-                    raise
-                fb = model.features(bank, index_base=index_base, role="bank", fmt="hilo")
-                fq = model.features(queries, role="query", fmt="hilo")
+        fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
         keys = _lp.feat_knn_keys(fb, fq, n_rows)
         if reduce_fn is not None:
             keys = reduce_fn(keys)

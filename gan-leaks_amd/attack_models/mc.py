@@ -3,15 +3,20 @@ against Generative Models", PoPETs 2019 -- the `MC` baseline GAN-Leaks is compar
 no such driver; the data flags, the YAML overlay and the layout of the result directory are fbb.py's (attack_models/fbb.py:18-67), so
 that eval_roc.py scores the result unchanged.
 
-Score of a query x:  f_eps(x) = #{ i < n_eff : dist(x, g_i) <= eps } / n_eff  over the sample bank g and the 'l2' distance of the
-full-black-box attack (Loss('l2'), attack_models/utils.py:161-164), n_eff = (N // BATCH_SIZE) * BATCH_SIZE (fbb.py:77).  All eps are
-counted in ONE pass over the bank (ganleaks_amd.attack.ball_counts, exact-integer L2 on the int8 matrix cores).
+Score of a query x:  f_eps(x) = #{ i < n_eff : dist(x, g_i) <= eps } / n_eff  over the sample bank g and a distance of the
+full-black-box attack, n_eff = (N // BATCH_SIZE) * BATCH_SIZE (fbb.py:77).  All eps are counted in ONE pass over the bank
+(ganleaks_amd.attack.ball_counts).
 
     python -m ganleaks_amd.attack_models.mc --syn_data_path ... --pos_data_dir ... --neg_data_dir ... [--eps e1,e2,... | --eps_quantile q1,q2,...]
+                                            [--distance {l2,l2-lpips}]
+
+--distance      l2 (default): Loss('l2'), attack_models/utils.py:161-164, exact-integer L2 on the int8 matrix cores.
+                l2-lpips: 0.2 * LPIPS + L2, the distance fbb.main hard-wires (fbb.py:148, utils.py:166-176), counted by the l2-lpips search
+                kernel with a counting epilogue; weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH as in fbb.py
 
 --eps           the radii themselves (up to 16)
 --eps_quantile  (default 0.5: Hilprecht's median heuristic) eps = that quantile (method 'lower': an attained distance) of the pooled
-                positive + negative nearest-sample distances, which one attack() over the same prepared rows gives
+                positive + negative nearest-sample distances, which one attack() under the same distance over the same prepared rows gives
 Files under ./mc_attack/<exp_name>/:
     eps.npy float32 [T]; {pos,neg}_count.npy int64 [n, T]; {pos,neg}_mc.npy float64 [n, T] = count / n_eff; params.txt;
     {pos,neg}_loss.npy float64 [n, 1] = -mc[:, 0], so `eval_roc --attack_type fbb -ldir mc_attack/<exp_name>` scores the first eps.
@@ -42,6 +47,8 @@ def parse_arguments(argv=None):
     parser.add_argument('--ngpu', type=int, default=1, help='shard the bank over the first N GPUs (counts summed across them)')
     parser.add_argument('--devices', type=str, default=None, help='explicit device ordinals for the shards, e.g. 0,1,2,3 (overrides --ngpu)')
     parser.add_argument('--eps', type=str, default=None, help='comma-separated radii (1..%d values); write a leading negative radius as --eps=-1,...' % GL_COUNT_MAX_T)
+    parser.add_argument('--distance', type=str, default='l2', choices=['l2', 'l2-lpips'],
+                        help="distance the balls are measured in: 'l2', or 'l2-lpips' = 0.2 * LPIPS + L2 (the reference's fbb distance)")
     parser.add_argument('--eps_quantile', type=str, default=None,
                         help='comma-separated quantiles of the pooled nearest-sample distances to use as radii (default 0.5, the median heuristic)')
     return parser.parse_args(argv)
@@ -78,6 +85,9 @@ def radii_request(args):
 
 def main(args):
     mode, values = radii_request(args)
+    distance = getattr(args, "distance", "l2")
+    if distance not in ("l2", "l2-lpips"):
+        raise SystemExit("--distance must be l2 or l2-lpips, got %r" % (distance,))
     assert os.path.exists(args.syn_data_path)
     save_dir = check_folder(os.path.join(os.getcwd(), 'mc_attack', args.exp_name))
     lines = ["%s:%s" % (key, value) for key, value in vars(args).items()]
@@ -101,7 +111,21 @@ def main(args):
         from ..shard import DeviceGroup
         group = DeviceGroup(devices)                 # every context prepares the (replicated) queries once, for both passes
     try:
-        if group is None:
+        if distance == "l2-lpips":
+            from ..lpips import default_model
+            if group is None:                        # (a group builds one model per context from the same local files)
+                model = default_model()
+                queries = prepare_queries(both, distance, lpips=model)
+                bank = syn_imgs
+                if getattr(queries, "kind", None) == "feat" and n_eff * queries.K * queries.V.dtype.itemsize <= _budget_bytes():
+                    # the bank's feature rows are computed once for both passes when they fit the streaming budget
+                    bank = model.features(syn_imgs[:n_eff], role=model.search_role("bank"), fmt=queries.fmt)
+                nearest = lambda: attack(queries, bank, distance=distance, batch_size=args.BATCH_SIZE, lpips=model)[0]                # noqa: E731
+                count = lambda eps: ball_counts(queries, bank, eps, batch_size=args.BATCH_SIZE, distance=distance, lpips=model)        # noqa: E731
+            else:
+                nearest = lambda: group.attack(both, bank=syn_imgs, distance=distance, batch_size=args.BATCH_SIZE)[0]            # noqa: E731
+                count = lambda eps: group.ball_counts(both, bank=syn_imgs, eps=eps, batch_size=args.BATCH_SIZE, distance=distance)  # noqa: E731
+        elif group is None:
             queries = prepare_queries(both, "l2")
             d = int(np.prod(syn_imgs.shape[1:], dtype=np.int64))
             # the bank's int8 rows are prepared once for both passes when they fit the streaming budget; otherwise both stream the images

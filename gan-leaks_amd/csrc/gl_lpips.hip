@@ -17,10 +17,13 @@
 // is im2col'ed by the input kernel into one 32-wide K slice (27 values + 5 zeros).
 #include "gl_conv.h"
 #include "gl_pair256.h"
+#include "gl_feat_pair.h"
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
 #include <vector>
+
+using namespace gl_feat_pair;     // tile shapes, K segments and the row scale shared with gl_feat_count.hip
 
 namespace {
 
@@ -59,8 +62,6 @@ __global__ void __launch_bounds__(256) maxpool2_nhwc_kernel(const float *__restr
         reinterpret_cast<float4 *>(out)[i] = m;
     }
 }
-
-constexpr float kVScale = 16384.0f;     // V is stored as halves of V * 2^14 (values of 1e-4 .. 1e-1 stay out of the fp16 subnormals)
 
 // "Lattice" search rows (8-bit images only): a pixel 2 c / 255 - 1 is m / 255 with m = 2 c - 255 an odd integer of 9 bits, so with the row
 // scale u = 255 sqrt(D) 2^e the image part of V * u is m * 2^e -- EXACT in one fp16, no hi / lo pair, one K segment of D halves instead of
@@ -680,10 +681,7 @@ __global__ void __launch_bounds__(256) rows_split_kernel(const float *__restrict
 // (128 bytes) double buffered in LDS via global_load_lds (rows may lie beyond 4 GiB: no buffer descriptor here);
 // epilogue: dist = max(|V_q|^2 + |V_n|^2 - 2 C / 2^28, 0), key = float_bits(dist) << 32 | global index, atomicMin.
 // ---------------------------------------------------------------------------------------------
-typedef _Float16 v8h __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-constexpr int FT = 128, FROW = 128, FOPER = FT * FROW;
-constexpr int kSplitSeg = 2048;          // slices (of 32 values) per accumulation segment
+// (v8h, v4f, the tile constants FT / FROW / FOPER and kSplitSeg: gl_feat_pair.h)
 
 __global__ void __launch_bounds__(256, 2)
 feat_knn_kernel(const char *__restrict__ bank, const float *__restrict__ bank_norm, int64_t n_rows, int64_t index_base,
@@ -808,7 +806,7 @@ feat_knn_kernel(const char *__restrict__ bank, const float *__restrict__ bank_no
 // operands) double buffered in 128 KiB of LDS, one workgroup per CU.  Block order: strips of 4 bank tiles with the bank tile
 // fastest, so the 32 workgroups of an XCD cover 4 bank x 8 query tiles and share operand panels in its L2.
 // ---------------------------------------------------------------------------------------------
-constexpr int GT = 256, GOPER = GT * FROW;
+// (GT, GOPER: gl_feat_pair.h)
 
 #ifdef GL_TUNING      // the round-1 kernel and the one-workgroup-per-tile pipelined kernel: A/B material of tools/bench_pairwise.py only
 __global__ void __launch_bounds__(512, 2)
@@ -986,22 +984,7 @@ feat_knn_h1p_kernel(const char *__restrict__ bank, const float *__restrict__ ban
 // K segments: after every SEG slices the fp32 accumulators are added into per-workgroup totals in HBM and cleared, which turns the
 // 266 000-step accumulation chain of a 256 x 256 image pair into a two-level sum (error of a distance 1.8e-5 -> ~1e-6).
 // ---------------------------------------------------------------------------------------------
-constexpr int kClusters = 8, kSuperN = 4, kSuperQ = 8;
-constexpr int kSegSlices = 2048;                 // 128 Ki halves of K per segment
-constexpr size_t kTotalsPerWg = 8 * 32 * 64 * sizeof(v4f);     // 256 KiB: 8 waves x 32 accumulator tiles x 64 lanes x 4 floats
-
-__device__ __forceinline__ void cluster_meet(unsigned *counter, unsigned target)
-{
-    // one lane arrives and polls; the counter only orders time (L2 sharing), no memory is handed over
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(counter, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        for (int spin = 0; spin < 40000; ++spin) {
-            if ((int)(__hip_atomic_load(counter, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0) break;
-            __builtin_amdgcn_s_sleep(32);
-        }
-    }
-    __syncthreads();
-}
+// (kClusters, kSuperN, kSuperQ, kSegSlices, kTotalsPerWg, cluster_meet: gl_feat_pair.h)
 
 __global__ void __launch_bounds__(512, 2)
 feat_knn_h1c_kernel(const char *__restrict__ bank, const float *__restrict__ bank_norm, int64_t n_rows, int64_t index_base,
@@ -1765,14 +1748,7 @@ int gl_feat_knn_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *ba
     const bool clustered = variant == 3 && members >= kSuperN * kSuperQ;
     if (clustered || variant == 3 || variant == 5) {
         const int grid = clustered ? kClusters * members : (ctx->num_cu > 0 ? ctx->num_cu : 256);
-        const size_t need = 4096 + (size_t)grid * kTotalsPerWg;
-        if (ctx->pair_scratch_bytes < need) {
-            GL_HIP(hipStreamSynchronize(ctx->stream));
-            (void)hipFree(ctx->pair_scratch);
-            ctx->pair_scratch = nullptr; ctx->pair_scratch_bytes = 0;
-            GL_HIP(gl_device_alloc(ctx, (void **)&ctx->pair_scratch, need));
-            ctx->pair_scratch_bytes = need;
-        }
+        if (const int rc = reserve_pair_scratch(ctx, grid)) return rc;
         GL_ONCE_PER_DEVICE(ctx, \
             GL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(feat_knn_h1c_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
             GL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(feat_knn_h1s_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, lds)););

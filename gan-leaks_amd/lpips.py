@@ -290,8 +290,8 @@ def preferred_bank_rows(max_rows, n_queries):
     return best
 
 
-def feat_knn_keys(bank, queries, n_rows=None, keys=None):
-    ctx = bank.ctx
+def _search_pair_roles(bank, queries, who):
+    """the row-format and layout checks every pairwise call over two FeatureBanks makes; returns their roles"""
     roles = (getattr(bank, "role", None), getattr(queries, "role", None))
     fmts = (getattr(bank, "fmt", None), getattr(queries, "fmt", None))
     if fmts[0] != fmts[1]:
@@ -299,9 +299,15 @@ def feat_knn_keys(bank, queries, n_rows=None, keys=None):
     if queries.K != bank.K:
         raise ValueError("feature lengths differ: %d vs %d" % (queries.K, bank.K))
     if fmts[0] != "lattice" and roles not in ((None, None), ("bank", "query")):
-        raise ValueError("feat_knn_keys needs two split FeatureBanks or search rows of roles ('bank', 'query'); got %r" % (roles,))
+        raise ValueError("%s needs two split FeatureBanks or search rows of roles ('bank', 'query'); got %r" % (who, roles))
     if fmts[0] == "lattice" and None in roles:
-        raise ValueError("feat_knn_keys: lattice rows on one side, split rows on the other")
+        raise ValueError("%s: lattice rows on one side, split rows on the other" % who)
+    return roles
+
+
+def feat_knn_keys(bank, queries, n_rows=None, keys=None):
+    ctx = bank.ctx
+    roles = _search_pair_roles(bank, queries, "feat_knn_keys")
     n_rows = bank.n if n_rows is None else int(n_rows)
     if keys is None:
         keys = ctx.empty((max(queries.n, 1),), np.uint64)
@@ -313,6 +319,61 @@ def feat_knn_keys(bank, queries, n_rows=None, keys=None):
         check(ctx.lib.gl_feat_knn(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, bank.index_base, _p(queries.V.ptr),
                                   _p(queries.norms.ptr), queries.n, bank.K, _p(keys.ptr)))
     return keys
+
+
+def feat_count(bank, queries, thr, n_rows=None, counts=None):
+    """epsilon-ball counts under the distance feat_knn_keys searches: counts DeviceArray [Q, T] (uint64),
+    counts[q, t] += #{ n < n_rows : D32(q, n) <= thr[t] }, D32 the float32 distance feat_knn_keys packs into its key for that pair, bit for
+    bit (same kernel up to the epilogue).  thr: 1..16 ascending float32 values, +inf allowed; negative ones, which no distance meets, leave
+    their columns untouched.  `counts` from an earlier call (another chunk of the bank) is added to.  Row formats and layouts as
+    feat_knn_keys.  Asynchronous."""
+    from .attack import GL_COUNT_MAX_T, new_counts
+    ctx = bank.ctx
+    roles = _search_pair_roles(bank, queries, "feat_count")
+    with np.errstate(over="ignore"):
+        thr = np.ascontiguousarray(np.atleast_1d(thr), np.float32)
+    if thr.ndim != 1 or not 1 <= len(thr) <= GL_COUNT_MAX_T:
+        raise ValueError("feat_count needs 1..%d thresholds, got shape %r" % (GL_COUNT_MAX_T, thr.shape))
+    if np.any(np.isnan(thr)) or np.any(thr[1:] < thr[:-1]):
+        raise ValueError("feat_count needs ascending thresholds without NaN, got %r" % (thr.tolist(),))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if counts is None:
+        counts = new_counts(ctx, queries.n, len(thr))
+    elif tuple(counts.shape) != (max(queries.n, 1), len(thr)) or counts.dtype != np.dtype(np.uint64):
+        raise ValueError("feat_count(counts=...): needs uint64 counters of shape %r" % ((max(queries.n, 1), len(thr)),))
+    skip = int(np.count_nonzero(thr < 0))                 # a prefix: thr is ascending
+    live = thr[skip:]
+    if len(live) == 0:
+        return counts
+    if roles[0]:
+        check(ctx.lib.gl_feat_count_h1_scaled(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr), queries.n,
+                                              bank.K, bank.scale, live.ctypes.data_as(_p), len(live), skip, len(thr), _p(counts.ptr)))
+    else:
+        check(ctx.lib.gl_feat_count(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr), queries.n, bank.K,
+                                    live.ctypes.data_as(_p), len(live), skip, len(thr), _p(counts.ptr)))
+    return counts
+
+
+PAIR_DIST_MAX_BYTES = 1 << 30
+
+
+def feat_pair_dist(bank, queries, n_rows=None):
+    """the distance matrix itself, float32 [Q, n]: M[q, n] = D32(q, n) over bank rows [0, n_rows), the values feat_knn_keys minimises and
+    feat_count counts (M.min(axis=1) is the search's distance, bit for bit).  For small cases -- the histogram a radius is chosen from, a
+    check of the per-pair values: ValueError when the matrix would exceed 1 GiB.  Row formats and layouts as feat_knn_keys."""
+    ctx = bank.ctx
+    roles = _search_pair_roles(bank, queries, "feat_pair_dist")
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if queries.n * n_rows * 4 > PAIR_DIST_MAX_BYTES:
+        raise ValueError("a %d x %d distance matrix exceeds 1 GiB; feat_pair_dist is for small cases (feat_count counts without storing)" % (queries.n, n_rows))
+    out = ctx.empty((max(queries.n, 1), max(n_rows, 1)), np.float32)
+    if roles[0]:
+        check(ctx.lib.gl_feat_pair_dist_h1_scaled(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr), queries.n,
+                                                  bank.K, bank.scale, _p(out.ptr), max(n_rows, 1)))
+    else:
+        check(ctx.lib.gl_feat_pair_dist(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr), queries.n, bank.K,
+                                        _p(out.ptr), max(n_rows, 1)))
+    return out.numpy()[:queries.n, :n_rows]
 
 
 def rows_dist(a, g):

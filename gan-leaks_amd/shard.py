@@ -278,12 +278,15 @@ class DeviceGroup:
 
         return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call)
 
-    def ball_counts(self, queries, make_generator=None, z=None, bank=None, eps=None, batch_size=64, weights=None, **generate_kwargs):
+    def ball_counts(self, queries, make_generator=None, z=None, bank=None, eps=None, batch_size=64, weights=None, distance="l2", make_lpips=None,
+                    **generate_kwargs):
         """attack.ball_counts over the group's contexts: rank r counts over rows [bounds[r], bounds[r+1]) of the bank (handed over or
         generated, as in attack_on_devices), the [Q, T] counters are summed across the ranks (allreduce_sum_counts, or on the host where RCCL
         cannot form the communicator).  int64 [Q, T], identical to the single-device result.  The queries are prepared once per context and
-        shared with attack(distance='l2') on the same array."""
+        shared with attack() under the same distance on the same array.  distance, make_lpips: as in attack_on_devices."""
         from .attack import _check_eps, ball_counts
+        if distance not in ("l2", "l2-lpips"):
+            raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
         if eps is None:
             raise ValueError("needs eps")
         eps = _check_eps(eps)
@@ -296,9 +299,9 @@ class DeviceGroup:
             return lambda counts: ctx.to_device(host.merge(rank, counts.numpy(), op="sum"))
 
         def call(prepared, shard, ctx, reduce_fn, model, lo):
-            return ball_counts(prepared, shard, eps, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, index_base=lo)
+            return ball_counts(prepared, shard, eps, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, index_base=lo, distance=distance, lpips=model)
 
-        return self._run(queries, make_generator, z, bank, "l2", batch_size, None, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
+        return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
 
     def _run(self, queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call):
         """the worker scaffolding of one sharded job: a host thread per context, the fallible setup before a rendezvous, the failure vote.
@@ -430,8 +433,9 @@ def attack_on_devices(queries, make_generator=None, z=None, devices=None, distan
         return group.attack(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, k, **generate_kwargs)
 
 
-def ball_counts_on_devices(queries, make_generator=None, z=None, devices=None, eps=None, batch_size=64, weights=None, bank=None, **generate_kwargs):
+def ball_counts_on_devices(queries, make_generator=None, z=None, devices=None, eps=None, batch_size=64, weights=None, bank=None, distance="l2",
+                           make_lpips=None, **generate_kwargs):
     """attack.ball_counts sharded over a DeviceGroup built for the call (arguments as attack_on_devices): int64 [Q, T], identical to the
     single-device counts."""
     with DeviceGroup(devices) as group:
-        return group.ball_counts(queries, make_generator, z, bank, eps, batch_size, weights, **generate_kwargs)
+        return group.ball_counts(queries, make_generator, z, bank, eps, batch_size, weights, distance, make_lpips, **generate_kwargs)

@@ -90,6 +90,7 @@ int gl_event_elapsed_ms(void *start, void *stop, float *out_ms);   /* synchronis
 #define GL_PROF_FEAT_KNN 4      /* fp32-MFMA pairwise |V_q - V_n|^2 + argmin (l2-lpips) */
 #define GL_PROF_TOPK_SELECT 5   /* top-K: selection over the stored S values + list merge (the pairwise kernel itself reports as GL_PROF_L2_KNN) */
 #define GL_PROF_L2_COUNT 6      /* int8-MFMA pairwise L2 + epsilon-ball counts (gl_l2_count_i8*) */
+#define GL_PROF_FEAT_COUNT 7    /* fp16-MFMA pairwise l2-lpips distance + epsilon-ball counts / stored matrix (gl_feat_count*, gl_feat_pair_dist*) */
 int gl_prof_enable(gl_ctx *ctx, int on);
 int gl_prof_read(gl_ctx *ctx, int tag, double *out_total_ms, int64_t *out_launches);
 int gl_prof_reset(gl_ctx *ctx);
@@ -388,6 +389,32 @@ int gl_feat_knn_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *ba
                           const float *query_norm_dev, int64_t nq, int64_t K1, uint64_t *keys_dev, float row_scale);
 int gl_feat_knn_h1(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, int64_t index_base, const void *query_V16_dev,
                    const float *query_norm_dev, int64_t nq, int64_t K1, uint64_t *keys_dev);
+/* ---- epsilon-ball counts and the distance matrix under 0.2 LPIPS + L2, the distance fbb.main hard-wires (attack_models/fbb.py:148,
+ * Loss('l2-lpips'), attack_models/utils.py:166-176).  The kernels are the searches above with another epilogue -- same main loop, K segments and
+ * order of the segment totals -- so the fp32 value they reduce,
+ *     D32(q, n) = fmaxf(fmaf(-2 / row_scale^2, dot(q, n), |q|^2 + |n|^2), 0),
+ * is bit for bit the distance gl_feat_knn_h1_scaled / gl_feat_knn pack into keys[q] for that pair (what gl_keys_unpack_f32 returns).
+ *
+ * gl_feat_count_h1_scaled (fp16 search rows, either layout, row-major or K-blocked) / gl_feat_count (split rows):
+ *     counts_dev[q * pitch + col0 + t] += #{ n in [0, n_rows) : D32(q, n) <= thr_host[t] },  t < n_thr
+ * thr_host: n_thr (1..GL_COUNT_MAX_T) fp32 thresholds in HOST memory, ascending (equal neighbours and +inf allowed), none negative or NaN -- a
+ * caller with negative radii leaves their columns out (nothing meets them) and passes the rest through col0.  counts_dev is a [nq][pitch] uint64
+ * table of gl_counts_init (col0 + n_thr <= pitch <= GL_COUNT_MAX_T); gl_counts_add is the cross-shard sum.  Accumulates, so a streamed bank is
+ * counted chunk by chunk; counting the same rows twice counts them twice.  No bank index is involved.  Row, norm, size and scale arguments and
+ * their checks as gl_feat_knn_h1_scaled / gl_feat_knn (K1 % 64 == 0, K % 32 == 0, rows 16-byte aligned, K-blocked rows at a multiple of 256 rows of
+ * their buffer); n_rows == 0 or nq == 0 is GL_OK.  One kernel, no pairwise value is written to memory; the counts do not depend on tile position,
+ * chunking, query slicing, sharding or on which of the two persistent kernels the device gets.  Asynchronous on the context's stream. */
+int gl_feat_count_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,
+                            const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, const float *thr_host, int n_thr, int col0, int pitch,
+                            uint64_t *counts_dev);
+int gl_feat_count(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev, const float *query_norm_dev,
+                  int64_t nq, int64_t K, const float *thr_host, int n_thr, int col0, int pitch, uint64_t *counts_dev);
+/* out_dev[q * ld + n] = D32(q, n) for q < nq, n < n_rows (ld >= n_rows floats per query): the matrix itself, for small cases -- the distance
+ * histogram a radius is chosen from, and an exact handle on the per-pair values (its row minimum is the search's distance). */
+int gl_feat_pair_dist_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,
+                                const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, float *out_dev, int64_t ld);
+int gl_feat_pair_dist(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev,
+                      const float *query_norm_dev, int64_t nq, int64_t K, float *out_dev, int64_t ld);
 /* mean((y-x)^2) + argmin for ARBITRARY fp32 rows on the matrix cores (an alternative to the bit-reproducible VALU path gl_l2_knn_f32; ~15-60x
  * faster; distances agree to ~3e-6 * mean(x^2), i.e. ~1e-6 absolute for rows in [-1,1]): rows are stored as hi + lo halves of x * 2^e with a per-row power of two,
  * dist = |y|^2/d + |x|^2/d - 2 y.x/d with three fp16 MFMAs per product and fp32 accumulation.  V_dev: [n][gl_rows_split_dim(d)] 4-byte slots,

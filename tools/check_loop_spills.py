@@ -5,6 +5,9 @@ scratch reload and an `s_waitcnt vmcnt(0)` per K slice, which drains the LDS-DMA
 that the 256-channel tile never runs was added to its epilogue (round 2).  tests/test_loop_spills.py asserts zero for the kernels below.
 
     python tools/check_loop_spills.py            one line per kernel; exit status 1 if any count is non-zero
+    python tools/check_loop_spills.py --kernels gl_feat_count.hip:feat_pairs_h1_kernelILi0ELb1E,... [--pipelined file:name,...]
+                                                 the same checks for the kernels named instead of the lists below: --kernels counts spills inside
+                                                 the K loop, --pipelined checks the hand-placed fragment reads of a gl_pair256.h kernel
 """
 import os
 import re
@@ -104,10 +107,32 @@ def inflight_hazards(asm, needle):
     return reads, bad
 
 
-def main():
+def _by_file(text):
+    """'file:name,file:name' -> {file: [names]}"""
+    out = {}
+    for item in filter(None, (text or "").split(",")):
+        src, _, needle = item.partition(":")
+        if not src or not needle:
+            raise SystemExit("expected file:name, got %r" % item)
+        out.setdefault(src, []).append(needle)
+    return out
+
+
+def main(argv=None):
+    import argparse
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--kernels", default=None, help="file:name,... -- count K-loop spills of these kernels instead of the built-in list")
+    ap.add_argument("--pipelined", default=None, help="file:name,... -- check the in-flight fragment reads of these kernels instead of the built-in list")
+    args = ap.parse_args(argv)
+    hot, pipelined = HOT, PIPELINED
+    if args.kernels is not None or args.pipelined is not None:
+        pipelined = _by_file(args.pipelined)
+        hot = _by_file(args.kernels)
+        for src in pipelined:
+            hot.setdefault(src, [])
     bad = 0
     with tempfile.TemporaryDirectory() as tmp:
-        for src, needles in HOT.items():
+        for src, needles in hot.items():
             out = os.path.join(tmp, src + ".s")
             cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-gpu-rdc", "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out]
             subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
@@ -117,7 +142,7 @@ def main():
                 print("%-20s %-52s %s" % (src, n, "not found" if c is None else "%d scratch instructions inside the K loop" % c))
                 if c is None or c > 0:
                     bad += 1
-            for n in PIPELINED.get(src, []):
+            for n in pipelined.get(src, []):
                 r = inflight_hazards(asm, n)
                 if r is None:
                     print("%-20s %-52s not found" % (src, n))

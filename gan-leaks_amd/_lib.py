@@ -148,6 +148,9 @@ SIGNATURES = {
     "gl_feat_count": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _i, _i, _p]),
     "gl_feat_pair_dist_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _i64]),
     "gl_feat_pair_dist": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i64]),
+    "gl_feat_topk_h1_scaled": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, ctypes.c_float, _i, _p]),
+    "gl_feat_topk": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _i, _p]),
+    "gl_topk_unpack_f32": (_i, [_p, _p, _i64, _i, _p, _p]),
     "gl_feat_rows_dist": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64, _p, _p]),
     "gl_comm_unique_id": (_i, [_p]),
     "gl_comm_init_rank": (_i, [_p, _p, _i, _i, _pp]),

@@ -318,6 +318,15 @@ def unpack_topk(ctx, keys, nq, k, d, kind="u8"):
     return dist.numpy()[:nq], idx.numpy()[:nq]
 
 
+def unpack_topk_f32(ctx, keys, nq, k):
+    """[Q, k] keys of lpips.feat_topk_keys (float bits << 32 | index) -> (dist float32 [Q, k], idx int64 [Q, k]); an empty slot gives
+    +inf and -1"""
+    dist = ctx.empty((max(nq, 1), k), np.float32)
+    idx = ctx.empty((max(nq, 1), k), np.int64)
+    check(ctx.lib.gl_topk_unpack_f32(ctx.handle, _p(keys.ptr), nq, k, _p(dist.ptr), _p(idx.ptr)))
+    return dist.numpy()[:nq], idx.numpy()[:nq]
+
+
 def set_topk_workspace(ctx, nbytes):
     """bytes of pairwise distances one slice of a top-k search may keep on the device (0: the default, 1 GiB).  The result does not
     depend on it; tests use it to force the slicing."""
@@ -595,12 +604,15 @@ def _lpips_resident_rows(queries, bank, prepared, model, index_base):
     return fb, fq
 
 
-def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath=None, index_base=0, count_thr=None):
+def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath=None, index_base=0, count_thr=None, topk=None):
     """bank rows [0, n_rows) pass through HBM in chunks of at most `chunk_bytes` of prepared rows (int8 rows for 'l2', feature
     rows for 'l2-lpips'); the packed keys accumulate the minimum across chunks (atomicMin), so the result is the one the
     resident form gives.  `bank` is a GeneratedBank or a host array / DeviceArray of images (`index_base`: global index of its row 0).
     count_thr ('l2-lpips' only; ascending float32 thresholds): the same stream with lpips.feat_count in place of the search -- the [Q, T]
-    counters accumulate across chunks, reduce_fn is the cross-shard sum, and the result is the host array of counts, uint64 [Q, T]."""
+    counters accumulate across chunks, reduce_fn is the cross-shard sum, and the result is the host array of counts, uint64 [Q, T].
+    topk ('l2-lpips' only; 1..32): the same stream with lpips.feat_topk_keys -- the [Q, topk] key lists fold chunk after chunk, reduce_fn is
+    the cross-shard merge, the result (dist [Q, topk], idx [Q, topk]).  Lists, unlike a minimum or a count, must see every row once: when an
+    off-lattice chunk makes the stream start over in the hi / lo layout, the lists start over from gl_topk_init with it."""
     generated = getattr(bank, "kind", None) == "generated"
     base = bank.index_base if generated else int(index_base)
 
@@ -615,6 +627,13 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
             if reduce_fn is not None:
                 counts = reduce_fn(counts)
             return counts.numpy()[:nq]
+        if topk is not None:
+            if keys is None:
+                keys = ctx.empty((max(nq, 1), topk), np.uint64)
+                check(ctx.lib.gl_topk_init(ctx.handle, _p(keys.ptr), nq, topk))
+            if reduce_fn is not None:
+                keys = reduce_fn(keys)
+            return unpack_topk_f32(ctx, keys, nq, topk)
         if keys is None:                 # a shard without rows still takes part in the reduction
             keys = ctx.empty((max(nq, 1),), np.uint64)
             check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), nq))
@@ -630,7 +649,7 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
             per_q = _feature_row_bytes(ctx, model, queries)
             q_step = max(1, int(_query_budget_bytes(chunk_bytes, ctx) // per_q))
             if len(queries) > q_step:
-                parts = [_attack_streamed(queries[a:a + q_step], bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath, index_base, count_thr)
+                parts = [_attack_streamed(queries[a:a + q_step], bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath, index_base, count_thr, topk)
                          for a in range(0, len(queries), q_step)]
                 if count_thr is not None:
                     return np.concatenate(parts)
@@ -644,7 +663,7 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
             step = max(1, int(chunk_bytes // (fq.K * (2 if fq.role else 4))))
             if fq.role:
                 step = _lp.preferred_bank_rows(step, fq.n)
-            keys, buf, ok = None, None, True
+            keys, buf, ok = None, None, True         # (key lists of an abandoned layout are dropped here: nothing of them survives)
             for lo in range(0, n_rows, step):
                 hi = min(lo + step, n_rows)
                 try:
@@ -654,7 +673,10 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
                         raise
                     ok = False
                     break
-                keys = _lp.feat_knn_keys(buf, fq, keys=keys) if count_thr is None else _lp.feat_count(buf, fq, count_thr, counts=keys)
+                if topk is not None:
+                    keys = _lp.feat_topk_keys(buf, fq, topk, keys=keys)
+                else:
+                    keys = _lp.feat_knn_keys(buf, fq, keys=keys) if count_thr is None else _lp.feat_count(buf, fq, count_thr, counts=keys)
                 ctx.sync()
             if ok:
                 return finish(keys, fq.n, fq.K, "f32")
@@ -753,6 +775,56 @@ def _ball_counts_lpips(queries, bank, e32, batch_size, ctx, reduce_fn, model, ch
     out = np.empty((len(host), len(thr)), np.int64)
     out[:, order] = host.astype(np.int64)
     return out
+
+
+def nearest_neighbours(queries, bank, k, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, index_base=0):
+    """the k nearest bank samples of every query: custom_knn (attack_models/fbb.py:73-88) keeping the args.K nearest samples (fbb.py:32)
+    under either distance of attack(), 'l2-lpips' -- the one fbb.main hard-wires (fbb.py:148) -- by default.
+
+    returns (dist float32 [Q, k], idx int64 [Q, k]), per query ordered by (distance, global index); column 0 is attack()'s result.
+    distance='l2': attack(..., distance='l2', k=k) as it is (exact-integer L2; see there).  attack(k=) is the older spelling and stays
+              exact-integer only: attack(..., distance='l2-lpips', k=) keeps raising NotImplementedError, this function is the way in.
+    distance='l2-lpips': the k smallest keys float_bits(D32(q, n)) << 32 | n over n < n_eff, D32 the float32 distance
+              attack(..., distance='l2-lpips') minimises, ball_counts(..., distance='l2-lpips') counts and pair_distances stores, bit for
+              bit (the search kernel with a storing epilogue, then the selection of the exact-integer top-k).  So the lists equal a stable
+              argsort of pair_distances' rows, ball_counts(eps=dist[q, j])[q] >= j + 1, and they do not depend on chunking, query slicing,
+              sharding or prepared rows.  Accepts what attack(distance='l2-lpips') accepts: u8 or float images (off-lattice floats put both
+              sides in the hi / lo layout), prepared FeatureBanks on either side, a GeneratedBank; banks beyond `chunk_bytes` are streamed
+              and the lists fold chunk after chunk, query sets beyond the query budget go in slices.
+    n_eff   : attack()'s rule, (N // batch_size) * batch_size unless the bank is a shard (index_base != 0 or reduce_fn given); k > n_eff on
+              an unsharded call and a bank without a full batch raise ValueError.
+    reduce_fn: optional callable(keys DeviceArray [Q, k] uint64) -> DeviceArray, the cross-shard merge (shard.allreduce_topk_keys; on host
+              arrays shard.merge_topk_host)."""
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    k = _check_k(k)                          # before any Context: these checks run without a GPU
+    if distance == "l2":
+        return attack(queries, bank, distance="l2", batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, chunk_bytes=chunk_bytes,
+                      index_base=index_base, k=k)
+    from . import lpips as _lp
+    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
+    if reduce_fn is None and index_base == 0 and k > n_rows:
+        raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_rows))
+    model = lpips
+    if model is None and not (prepared and getattr(queries, "kind", None) == "feat"):      # prepared rows on both sides need no VGG16
+        model = _lp.default_model()
+    if not prepared:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
+            need = chunk_bytes + 1
+        else:
+            per_img = _feature_row_bytes(ctx, model, bank)
+            need = per_img * n_rows
+            if getattr(queries, "kind", None) != "feat" and len(queries) * per_img > chunk_bytes:
+                need = chunk_bytes + 1       # the query rows alone exceed a chunk: streamed form (queries resident or in slices)
+        if need > chunk_bytes:
+            return _attack_streamed(queries, bank, n_rows, "l2-lpips", ctx, reduce_fn, model, chunk_bytes, None, index_base, topk=k)
+        bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
+    fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
+    keys = _lp.feat_topk_keys(fb, fq, k, n_rows)
+    if reduce_fn is not None:
+        keys = reduce_fn(keys)
+    return unpack_topk_f32(ctx, keys, fq.n, k)
 
 
 def pair_distances(queries, bank, distance="l2-lpips", batch_size=64, lpips=None):

@@ -12,10 +12,18 @@
 //          Integer adds commute, and D32 of a pair does not depend on where in a tile, a chunk or a shard the pair sits (every accumulator
 //          sees the same K order): the counts are functions of the multiset of D32 values.
 // EPI = 1: out[q * ld + n] = D32(q, n).
+// EPI = 2: the bit pattern of D32(q, n) into the piece layout gl_topk.hip's selection reads, pieces[((n >> 2) * nq + q) * 4 + (n & 3)]: the
+//          top-K nearest neighbours under l2-lpips (gl_feat_topk*) are the k smallest keys float_bits(D32) << 32 | global index.
+//          D32 >= +0: fmaxf(., 0) never yields -0 here, because -2 inv_s2 acc and qn + bn cannot both be -0 (norms are sums of squares, and
+//          (+0) + (+0) = +0), so an exactly cancelling fmaf gives +0 under round-to-nearest.  Unsigned comparison of the bits of non-negative
+//          floats is float comparison, so the order of the keys is the order of (D32, index): column 0 is the search's key.  D32 is never
+//          NaN after fmaxf, so 0xFFFFFFFF never occurs in the top half and ~0 stays the empty slot.  As D32 of a pair does not depend on
+//          where the pair sits, neither does the set of keys: the lists need no rescoring and do not depend on tile, slice, chunk or shard.
 #include "gl_conv.h"
 #include "gl_count_epi.h"
 #include "gl_feat_pair.h"
 #include "gl_pair256.h"
+#include "gl_topk_sel.h"
 #include <cmath>
 
 using namespace gl_feat_pair;
@@ -31,10 +39,16 @@ template <> struct pair_sink<1> {
     float *dist;                     // [nq][ld]
     int64_t ld;
 };
+template <> struct pair_sink<2> {
+    unsigned *pieces;                // [ceil(n_rows / 4)][nq][4], n_rows and nq the kernel's (one slice)
+};
 
 // The epilogue of one tile.  acc holds the dot products of the lane's NI x 4 tiles of 16 x 16 (column = query qcol0 + j * 16 + (lane & 15) of
 // the tile, row = bank row nbase + i * 16 + r); D32 replaces them in place, so that no norm stays live next to the accumulators.
 // Every thread of the workgroup must call this (EPI = 0 has barriers and uses smem).
+// EPI = 2: acc[i][j] is 4 consecutive bank rows (from a multiple of 4) of one query = one piece, a 16-byte store; the 16 lanes of a column
+// group are 16 consecutive queries = 256 contiguous bytes.  Pieces whose first row is past n_rows are not written; rows past n_rows inside a
+// written piece hold whatever the clamped operands gave (the selection masks n < n_rows).
 template <int EPI, int NI>
 __device__ __forceinline__ void finish_tile(v4f (&acc)[NI][4], const float *__restrict__ bank_norm, int64_t n_rows, int64_t nbase,
                                             const float *__restrict__ query_norm, int64_t nq, int64_t q0, int qcol0, int tile_q, float inv_s2,
@@ -60,6 +74,16 @@ __device__ __forceinline__ void finish_tile(v4f (&acc)[NI][4], const float *__re
     if constexpr (EPI == 0) {
         auto s_of = [&](int i, int j, int r) -> float { return acc[i][j][r]; };
         gl_count::count_epilogue<NI, float>(s_of, n_left, q0, qcol0, q_left, tile_q, sink.a, sink.counts, smem, lane);
+    } else if constexpr (EPI == 2) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const int ql = qcol0 + j * 16 + frow;
+            if (ql >= q_left) continue;
+            unsigned *col = sink.pieces + ((nbase >> 2) * nq + q0 + ql) * 4;
+#pragma unroll
+            for (int i = 0; i < NI; ++i)
+                if (i * 16 < n_left) *reinterpret_cast<v4f *>(col + (int64_t)i * 16 * nq) = acc[i][j];      // (i * 16 / 4) pieces rows further: 4 nq * 4 values
+        }
     } else {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -292,6 +316,13 @@ int make_dist_sink(const char *fn, float *out, int64_t ld, int64_t n_rows, bool 
     return GL_OK;
 }
 
+// the dispatch of gl_feat_knn_h1_scaled: clusters on a whole MI355X, the cluster-free persistent form on a device with fewer compute units
+// (tuning builds: GL_PAIR_VARIANT=5 forces the latter).  Either way the same bits.
+bool h1_clustered(const gl_ctx *ctx, int64_t K1)
+{
+    return (gl_vrow_blocked(K1) || gl_tuning_int("GL_PAIR_VARIANT", 3) != 5) && ctx->num_cu / kClusters >= kSuperN * kSuperQ;
+}
+
 template <int EPI>
 int launch_h1(const char *fn, gl_ctx *ctx, const void *bank, const float *bank_norm, int64_t n_rows, const void *query, const float *query_norm, int64_t nq,
               int64_t K1, float row_scale, const pair_sink<EPI> &sink)
@@ -300,11 +331,9 @@ int launch_h1(const char *fn, gl_ctx *ctx, const void *bank, const float *bank_n
     const float inv_s2 = 1.0f / (row_scale * row_scale);
     const int64_t q_tiles = gl_ceil_div(nq, GT), n_tiles = gl_ceil_div(n_rows, GT);
     const int lds = 4 * GOPER;
-    // the dispatch of gl_feat_knn_h1_scaled: clusters on a whole MI355X, the cluster-free persistent form on a device with fewer compute units
-    // (tuning builds: GL_PAIR_VARIANT=5 forces the latter).  Either way the same bits.
     const int blocked = gl_vrow_blocked(K1) ? 1 : 0;
     const int members = ctx->num_cu / kClusters;
-    const bool clustered = (blocked || gl_tuning_int("GL_PAIR_VARIANT", 3) != 5) && members >= kSuperN * kSuperQ;
+    const bool clustered = h1_clustered(ctx, K1);
     const int grid = clustered ? kClusters * members : (ctx->num_cu > 0 ? ctx->num_cu : 256);
     if (const int rc = reserve_pair_scratch(ctx, grid)) return rc;
     GL_ONCE_PER_DEVICE(ctx, \
@@ -337,6 +366,70 @@ int launch_split(gl_ctx *ctx, const float *bank, const float *bank_norm, int64_t
     hipLaunchKernelGGL((feat_pairs_split_kernel<EPI>), dim3((unsigned)(q_tiles * n_tiles)), dim3(256), lds, ctx->stream, reinterpret_cast<const char *>(bank),
                        bank_norm, n_rows, reinterpret_cast<const char *>(query), query_norm, nq, K, (int)q_tiles, (int)n_tiles, 1.0f / (kVScale * kVScale), sink);
     GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+// gl_feat_topk*: slices of queries x bank rows whose D32 pieces fit the top-K workspace, each a launch of the pair kernel (EPI = 2) followed
+// by gl_topk.hip's selection and merge into the slice's rows of the lists.  H1: fp16 search rows (256 x 256 tile), else split rows (128 x 128).
+template <bool H1>
+int feat_topk_impl(const char *fn, gl_ctx *ctx, const void *bank, const float *bank_norm, int64_t n_rows, int64_t index_base, const void *query,
+                   const float *query_norm, int64_t nq, int64_t K, float row_scale, int k, uint64_t *topk)
+{
+    gl_make_current(ctx);
+    if (const int rc = check_rows(fn, ctx, bank, bank_norm, n_rows, query, query_norm, nq, K, H1 ? 64 : 32)) return rc;
+    GL_REQUIRE(k >= 1 && k <= GL_TOPK_MAX, "%s: k=%d outside [1, %d]", fn, k, GL_TOPK_MAX);
+    GL_REQUIRE(index_base >= 0 && index_base + n_rows <= (1ll << 32), "%s: global index does not fit the 32 index bits of a key", fn);
+    if (H1) GL_REQUIRE(row_scale > 0.0f && std::isfinite(row_scale), "%s: the row scale must be positive", fn);
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    GL_REQUIRE(topk, "%s: NULL key lists", fn);
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(topk) & 7) == 0, "%s: the key lists must be 8-byte aligned", fn);
+
+    // slices: qs queries x rs bank rows of D32 within the budget, whole tiles (or the whole extent), never below one tile.  The clustered
+    // kernel hands out super-tiles of 1024 bank rows x 2048 queries and every slice is a launch of its own: whole super-tiles when they fit.
+    const int64_t tile = H1 ? GT : FT;
+    const bool clustered = H1 && h1_clustered(ctx, K);
+    const int64_t sup_q = (int64_t)kSuperQ * GT, sup_n = (int64_t)kSuperN * GT;
+    const int64_t budget = (int64_t)gl_topk_workspace_budget(ctx);
+    int64_t qs = budget / (tile * 4) / tile * tile;
+    if (qs < tile) qs = tile;
+    if (qs > GL_TOPK_MAX_QUERY_SLICE) qs = GL_TOPK_MAX_QUERY_SLICE;
+    if (qs >= nq) qs = nq;
+    else if (clustered && qs >= sup_q) qs = qs / sup_q * sup_q;
+    int64_t rs = budget / (qs * 4) / tile * tile;
+    if (clustered && rs >= sup_n) rs = rs / sup_n * sup_n;
+    if (rs < tile) rs = tile;
+    if (rs > n_rows) rs = n_rows;
+    const int64_t groups = gl_ceil_div(rs, 4);
+    const int64_t segs = gl_topk_segments(qs, rs);
+
+    gl_scratch_guard mem{ctx};
+    int rc = gl_malloc(ctx, (size_t)(groups * qs * 16), &mem.p[0]);
+    if (rc != GL_OK) return rc;
+    rc = gl_malloc(ctx, (size_t)(segs * qs * k * 8), &mem.p[1]);
+    if (rc != GL_OK) return rc;
+    pair_sink<2> sink;
+    sink.pieces = static_cast<unsigned *>(mem.p[0]);
+    unsigned long long *lists = static_cast<unsigned long long *>(mem.p[1]);
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(topk);
+    // a slice starts at a multiple of the tile; K-blocked rows are whole blocks of 256 rows x K halves, so that is row * K * 2 bytes for them too
+    const int64_t row_bytes = H1 ? K * 2 : K * 4;
+
+    for (int64_t q_lo = 0; q_lo < nq; q_lo += qs) {
+        const int64_t nqs = nq - q_lo < qs ? nq - q_lo : qs;
+        const char *qrows = static_cast<const char *>(query) + q_lo * row_bytes;
+        for (int64_t r_lo = 0; r_lo < n_rows; r_lo += rs) {
+            const int64_t nrs = n_rows - r_lo < rs ? n_rows - r_lo : rs;
+            const char *brows = static_cast<const char *>(bank) + r_lo * row_bytes;
+            if constexpr (H1)
+                rc = launch_h1<2>(fn, ctx, brows, bank_norm + r_lo, nrs, qrows, query_norm + q_lo, nqs, K, row_scale, sink);
+            else
+                rc = launch_split<2>(ctx, reinterpret_cast<const float *>(brows), bank_norm + r_lo, nrs, reinterpret_cast<const float *>(qrows),
+                                     query_norm + q_lo, nqs, K, sink);
+            if (rc != GL_OK) return rc;
+            rc = gl_topk_select_merge(ctx, mem.p[0], 4, nrs, nqs, k, 32, index_base + r_lo, dst + q_lo * k, lists, segs);
+            if (rc != GL_OK) return rc;
+        }
+    }
     return GL_OK;
 }
 
@@ -391,6 +484,20 @@ int gl_feat_pair_dist(gl_ctx *ctx, const float *bank_V_dev, const float *bank_no
     if (const int rc = make_dist_sink(fn, out_dev, ld, n_rows, n_rows > 0 && nq > 0, sink)) return rc;
     if (n_rows == 0 || nq == 0) return GL_OK;
     return launch_split<1>(ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, sink);
+}
+
+int gl_feat_topk_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, int64_t index_base,
+                           const void *query_V16_dev, const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, int k, uint64_t *topk_keys_dev)
+{
+    return feat_topk_impl<true>("gl_feat_topk_h1_scaled", ctx, bank_V16_dev, bank_norm_dev, n_rows, index_base, query_V16_dev, query_norm_dev, nq, K1,
+                                row_scale, k, topk_keys_dev);
+}
+
+int gl_feat_topk(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, int64_t index_base, const float *query_V_dev,
+                 const float *query_norm_dev, int64_t nq, int64_t K, int k, uint64_t *topk_keys_dev)
+{
+    return feat_topk_impl<false>("gl_feat_topk", ctx, bank_V_dev, bank_norm_dev, n_rows, index_base, query_V_dev, query_norm_dev, nq, K, 1.0f, k,
+                                 topk_keys_dev);
 }
 
 }  // extern "C"

@@ -17,6 +17,7 @@
 // slices itself and the slice shape does not depend on k.
 #include "gl_common.h"
 #include "gl_pair256.h"
+#include "gl_topk_sel.h"
 #include <type_traits>
 
 namespace {
@@ -30,7 +31,7 @@ constexpr int THREADS = 256;
 constexpr int OPER_BYTES = TILE_N * TILE_K;
 constexpr int BT = 256;     // rows per operand of the 256 x 256 tile
 constexpr size_t DEFAULT_BUDGET = (size_t)1 << 30;
-constexpr int64_t MAX_QUERY_SLICE = 65536;   // bounds the per-segment lists next to the S pieces
+constexpr int64_t MAX_QUERY_SLICE = GL_TOPK_MAX_QUERY_SLICE;
 constexpr int SEL_THREADS = 128;
 constexpr int64_t SEL_TARGET_THREADS = 262144;   // 256 CUs x 1024 selection threads
 
@@ -323,11 +324,55 @@ __global__ void __launch_bounds__(256) topk_unpack_kernel(const uint64_t *__rest
     idx[i] = (int64_t)(key & ((1ull << shift) - 1ull));
 }
 
-struct scratch_guard {       // gl_free on every way out
-    gl_ctx *ctx;
-    void *p[2] = {nullptr, nullptr};
-    ~scratch_guard() { for (void *q : p) if (q) (void)gl_free(ctx, q); }
-};
+// keys of the l2-lpips top-K (gl_feat_topk*): float bits << 32 | global index
+__global__ void __launch_bounds__(256) topk_unpack_f32_kernel(const uint64_t *__restrict__ keys, int64_t count, float *__restrict__ dist,
+                                                              int64_t *__restrict__ idx)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= count) return;
+    const uint64_t key = keys[i];
+    if (key == ~0ull) {
+        dist[i] = __builtin_inff();
+        idx[i] = -1;
+        return;
+    }
+    dist[i] = __uint_as_float((unsigned)(key >> 32));
+    idx[i] = (int64_t)(key & 0xFFFFFFFFull);
+}
+
+}  // namespace
+
+size_t gl_topk_workspace_budget(const gl_ctx *ctx) { return ctx->topk_budget ? ctx->topk_budget : DEFAULT_BUDGET; }
+
+int64_t gl_topk_segments(int64_t qs, int64_t rs)
+{
+    const int64_t groups = gl_ceil_div(rs, 4);
+    int64_t segs = gl_ceil_div(SEL_TARGET_THREADS, qs);
+    if (segs > groups / 16) segs = groups / 16;
+    if (segs > 64) segs = 64;
+    if (segs < 1) segs = 1;
+    return segs;
+}
+
+int gl_topk_select_merge(gl_ctx *ctx, const void *pieces, int elem, int64_t nrs, int64_t nqs, int k, int shift, int64_t index0,
+                         unsigned long long *dst, unsigned long long *lists, int64_t segs)
+{
+    gl_prof_scope prof_(ctx, GL_PROF_TOPK_SELECT);
+    const dim3 sel_grid((unsigned)gl_ceil_div(nqs, SEL_THREADS), (unsigned)segs);
+    const size_t sel_lds = (size_t)SEL_THREADS * k * 8;
+    if (elem == 8)
+        hipLaunchKernelGGL(topk_select_kernel<unsigned long long>, sel_grid, dim3(SEL_THREADS), sel_lds, ctx->stream,
+                           static_cast<const unsigned long long *>(pieces), nrs, nqs, k, shift, index0, dst, lists);
+    else
+        hipLaunchKernelGGL(topk_select_kernel<unsigned>, sel_grid, dim3(SEL_THREADS), sel_lds, ctx->stream, static_cast<const unsigned *>(pieces),
+                           nrs, nqs, k, shift, index0, dst, lists);
+    GL_LAUNCH_CHECK();
+    hipLaunchKernelGGL(topk_merge_kernel, dim3(sel_grid.x), dim3(SEL_THREADS), sel_lds, ctx->stream, dst, lists, nqs * k, nqs, k, segs);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+namespace {
 
 template <typename NT>
 int topk_impl(const char *fn, gl_ctx *ctx, const int8_t *bank, const NT *bank_norm, int64_t n_rows, int64_t index_base, const int8_t *query,
@@ -356,7 +401,7 @@ int topk_impl(const char *fn, gl_ctx *ctx, const int8_t *bank, const NT *bank_no
     const int64_t elem = big ? 8 : 4;
 
     // slices: qs queries x rs bank rows of S values within the budget, both multiples of the tile (or the whole extent)
-    const int64_t budget = (int64_t)(ctx->topk_budget ? ctx->topk_budget : DEFAULT_BUDGET);
+    const int64_t budget = (int64_t)gl_topk_workspace_budget(ctx);
     int64_t qs = budget / (tile * elem) / tile * tile;
     if (qs < tile) qs = tile;
     if (qs > MAX_QUERY_SLICE) qs = MAX_QUERY_SLICE;
@@ -365,12 +410,9 @@ int topk_impl(const char *fn, gl_ctx *ctx, const int8_t *bank, const NT *bank_no
     if (rs < tile) rs = tile;
     if (rs > n_rows) rs = n_rows;
     const int64_t groups = gl_ceil_div(rs, 4);
-    int64_t segs = gl_ceil_div(SEL_TARGET_THREADS, qs);
-    if (segs > groups / 16) segs = groups / 16;
-    if (segs > 64) segs = 64;
-    if (segs < 1) segs = 1;
+    const int64_t segs = gl_topk_segments(qs, rs);
 
-    scratch_guard mem{ctx};
+    gl_scratch_guard mem{ctx};
     int rc = gl_malloc(ctx, (size_t)(groups * qs * 4 * elem), &mem.p[0]);
     if (rc != GL_OK) return rc;
     rc = gl_malloc(ctx, (size_t)(segs * qs * k * 8), &mem.p[1]);
@@ -414,18 +456,7 @@ int topk_impl(const char *fn, gl_ctx *ctx, const int8_t *bank, const NT *bank_no
                 }
                 GL_LAUNCH_CHECK();
             }
-            gl_prof_scope prof_(ctx, GL_PROF_TOPK_SELECT);
-            const dim3 sel_grid((unsigned)gl_ceil_div(nqs, SEL_THREADS), (unsigned)segs);
-            const size_t sel_lds = (size_t)SEL_THREADS * k * 8;
-            if (big)
-                hipLaunchKernelGGL(topk_select_kernel<unsigned long long>, sel_grid, dim3(SEL_THREADS), sel_lds, ctx->stream,
-                                   static_cast<const unsigned long long *>(mem.p[0]), nrs, nqs, k, shift, index_base + r_lo, qdst, lists);
-            else
-                hipLaunchKernelGGL(topk_select_kernel<unsigned>, sel_grid, dim3(SEL_THREADS), sel_lds, ctx->stream, static_cast<const unsigned *>(mem.p[0]),
-                                   nrs, nqs, k, shift, index_base + r_lo, qdst, lists);
-            GL_LAUNCH_CHECK();
-            hipLaunchKernelGGL(topk_merge_kernel, dim3(sel_grid.x), dim3(SEL_THREADS), sel_lds, ctx->stream, qdst, lists, nqs * k, nqs, k, segs);
-            GL_LAUNCH_CHECK();
+            if (const int rc = gl_topk_select_merge(ctx, mem.p[0], (int)elem, nrs, nqs, k, shift, index_base + r_lo, qdst, lists, segs)) return rc;
         }
     }
     return GL_OK;
@@ -495,6 +526,19 @@ int gl_topk_unpack(gl_ctx *ctx, const uint64_t *topk_keys_dev, int64_t nq, int k
     else
         hipLaunchKernelGGL(topk_unpack_kernel<false>, grid, dim3(256), 0, ctx->stream, topk_keys_dev, count, 4.0 / (65025.0 * (double)d), gl_l2_key_shift(d),
                            dist_dev, idx_dev);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_topk_unpack_f32(gl_ctx *ctx, const uint64_t *topk_keys_dev, int64_t nq, int k, float *dist_dev, int64_t *idx_dev)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && nq >= 0, "gl_topk_unpack_f32: bad ctx/nq");
+    GL_REQUIRE(k >= 1 && k <= GL_TOPK_MAX, "gl_topk_unpack_f32: k=%d outside [1, %d]", k, GL_TOPK_MAX);
+    if (nq == 0) return GL_OK;
+    GL_REQUIRE(topk_keys_dev && dist_dev && idx_dev, "gl_topk_unpack_f32: NULL device pointer");
+    const int64_t count = nq * k;
+    hipLaunchKernelGGL(topk_unpack_f32_kernel, dim3((unsigned)gl_ceil_div(count, 256)), dim3(256), 0, ctx->stream, topk_keys_dev, count, dist_dev, idx_dev);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }

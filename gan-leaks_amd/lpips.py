@@ -354,6 +354,31 @@ def feat_count(bank, queries, thr, n_rows=None, counts=None):
     return counts
 
 
+def feat_topk_keys(bank, queries, k, n_rows=None, keys=None):
+    """the k nearest bank rows of every query under the distance feat_knn_keys searches: DeviceArray [Q, k] (uint64), ascending per query,
+    the k smallest keys float_bits(D32(q, n)) << 32 | global index over bank rows [0, n_rows), ~0 in empty slots; D32 is the float32
+    distance feat_knn_keys packs into its key for that pair, bit for bit (same kernel up to the epilogue), so column 0 is feat_knn_keys'
+    key.  `keys` from an earlier call (another chunk of the bank) is folded in; an index may be folded in once only.  Row formats and
+    layouts as feat_knn_keys.  Unpack with attack.unpack_topk_f32."""
+    from .attack import _check_k
+    ctx = bank.ctx
+    k = _check_k(k)
+    roles = _search_pair_roles(bank, queries, "feat_topk_keys")
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if keys is None:
+        keys = ctx.empty((max(queries.n, 1), k), np.uint64)
+        check(ctx.lib.gl_topk_init(ctx.handle, _p(keys.ptr), queries.n, k))
+    elif tuple(keys.shape) != (max(queries.n, 1), k) or keys.dtype != np.dtype(np.uint64):
+        raise ValueError("feat_topk_keys(keys=...): needs uint64 key lists of shape %r" % ((max(queries.n, 1), k),))
+    if roles[0]:
+        check(ctx.lib.gl_feat_topk_h1_scaled(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, bank.index_base, _p(queries.V.ptr),
+                                             _p(queries.norms.ptr), queries.n, bank.K, bank.scale, k, _p(keys.ptr)))
+    else:
+        check(ctx.lib.gl_feat_topk(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, bank.index_base, _p(queries.V.ptr),
+                                   _p(queries.norms.ptr), queries.n, bank.K, k, _p(keys.ptr)))
+    return keys
+
+
 PAIR_DIST_MAX_BYTES = 1 << 30
 
 

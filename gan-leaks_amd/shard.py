@@ -303,6 +303,35 @@ class DeviceGroup:
 
         return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
 
+    def nearest_neighbours(self, queries, make_generator=None, z=None, bank=None, k=None, batch_size=64, weights=None, distance="l2-lpips",
+                           make_lpips=None, **generate_kwargs):
+        """attack.nearest_neighbours over the group's contexts: rank r keeps the k nearest rows of [bounds[r], bounds[r+1]) of the bank
+        (handed over or generated, as in attack_on_devices), the [Q, k] key lists are merged across the ranks (allreduce_topk_keys, or on the
+        host where RCCL cannot form the communicator).  (dist float32 [Q, k], idx int64 [Q, k]), identical to the single-device result.
+        distance 'l2-lpips' (default) or 'l2'; make_lpips as in attack_on_devices."""
+        from .attack import _check_k, nearest_neighbours
+        if distance not in ("l2", "l2-lpips"):
+            raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+        if k is None:
+            raise ValueError("needs k")
+        k = _check_k(k)
+
+        def validate(n_eff):
+            if k > n_eff:
+                raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_eff))
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            if comms is not None:
+                return lambda keys: allreduce_topk_keys(keys, k, comm=comms[rank])
+            if self.world == 1:
+                return None
+            return lambda keys: ctx.to_device(host.merge(rank, keys.numpy(), k))
+
+        def call(prepared, shard, ctx, reduce_fn, model, lo):
+            return nearest_neighbours(prepared, shard, k, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, lpips=model, index_base=lo)
+
+        return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call)
+
     def _run(self, queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call):
         """the worker scaffolding of one sharded job: a host thread per context, the fallible setup before a rendezvous, the failure vote.
         validate(n_eff) checks the job's own arguments; reduce_fn_for(rank, ctx, comms, host) gives the rank's cross-shard reduction;
@@ -439,3 +468,11 @@ def ball_counts_on_devices(queries, make_generator=None, z=None, devices=None, e
     single-device counts."""
     with DeviceGroup(devices) as group:
         return group.ball_counts(queries, make_generator, z, bank, eps, batch_size, weights, distance, make_lpips, **generate_kwargs)
+
+
+def nearest_neighbours_on_devices(queries, make_generator=None, z=None, devices=None, k=None, batch_size=64, weights=None, bank=None,
+                                  distance="l2-lpips", make_lpips=None, **generate_kwargs):
+    """attack.nearest_neighbours sharded over a DeviceGroup built for the call (arguments as attack_on_devices):
+    (dist float32 [Q, k], idx int64 [Q, k]), identical to the single-device lists."""
+    with DeviceGroup(devices) as group:
+        return group.nearest_neighbours(queries, make_generator, z, bank, k, batch_size, weights, distance, make_lpips, **generate_kwargs)

@@ -415,6 +415,27 @@ int gl_feat_pair_dist_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const flo
                                 const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, float *out_dev, int64_t ld);
 int gl_feat_pair_dist(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev,
                       const float *query_norm_dev, int64_t nq, int64_t K, float *out_dev, int64_t ld);
+/* ---- the K nearest bank rows of every query under 0.2 LPIPS + L2: custom_knn (attack_models/fbb.py:73-88) under the distance fbb.main
+ * hard-wires (fbb.py:148) keeping the args.K nearest samples (fbb.py:32) instead of one.  Row q of topk_keys_dev ([nq][k] keys of gl_topk_init,
+ * 1 <= k <= GL_TOPK_MAX) becomes the k smallest of what it held and the keys
+ *     float_bits(D32(q, n)) << 32 | (index_base + n),  n < n_rows,
+ * D32 as above: the bits gl_feat_knn_h1_scaled / gl_feat_knn pack for that pair, so column 0 is their key and the lists are ordered by
+ * (D32, global index) -- D32 >= +0, where the order of the bit patterns is the order of the floats.  A function of the set of keys alone: no
+ * dependence on tile, slicing, chunking or sharding, and gl_topk_merge folds the lists of other shards.  Accumulates across calls like
+ * gl_l2_topk_i8 and like it is not idempotent: a global index may be folded in at most once.  index_base >= 0, index_base + n_rows <= 2^32.
+ * Row, norm, size and scale arguments and their checks as gl_feat_count_h1_scaled / gl_feat_count; n_rows == 0 or nq == 0 is GL_OK.
+ * The pair kernels run once whatever k is, storing D32 of one slice of queries x bank rows (whole tiles: 256 for fp16 rows, 128 for split rows;
+ * whole super-tiles of 1024 x 2048 on the clustered kernel when they fit) in a workspace from gl_malloc of at most 1 GiB
+ * (gl_topk_set_workspace); the selection of gl_l2_topk_i8 keeps the k smallest keys.  Reports as GL_PROF_FEAT_COUNT (pairs) and
+ * GL_PROF_TOPK_SELECT (selection).  Synchronises when it returns its workspace (gl_free). */
+int gl_feat_topk_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, int64_t index_base,
+                           const void *query_V16_dev, const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, int k,
+                           uint64_t *topk_keys_dev);
+int gl_feat_topk(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, int64_t index_base, const float *query_V_dev,
+                 const float *query_norm_dev, int64_t nq, int64_t K, int k, uint64_t *topk_keys_dev);
+/* [nq][k] keys of gl_feat_topk* -> dist_dev [nq][k] fp32 = the float whose bits are key >> 32, idx_dev [nq][k] int64 = key & 0xFFFFFFFF
+ * (gl_keys_unpack_f32 per slot); an empty slot gives +inf and -1. */
+int gl_topk_unpack_f32(gl_ctx *ctx, const uint64_t *topk_keys_dev, int64_t nq, int k, float *dist_dev, int64_t *idx_dev);
 /* mean((y-x)^2) + argmin for ARBITRARY fp32 rows on the matrix cores (an alternative to the bit-reproducible VALU path gl_l2_knn_f32; ~15-60x
  * faster; distances agree to ~3e-6 * mean(x^2), i.e. ~1e-6 absolute for rows in [-1,1]): rows are stored as hi + lo halves of x * 2^e with a per-row power of two,
  * dist = |y|^2/d + |x|^2/d - 2 y.x/d with three fp16 MFMAs per product and fp32 accumulation.  V_dev: [n][gl_rows_split_dim(d)] 4-byte slots,

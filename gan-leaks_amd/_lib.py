@@ -89,6 +89,8 @@ SIGNATURES = {
     "gl_counts_add": (_i, [_p, _p, _p, _i64, _i, _i64]),
     "gl_l2_rows_u8": (_i, [_p, _p, _i64, _p, _i64, _i64, _p]),
     "gl_l2_knn_f32": (_i, [_p, _p, _i64, _i64, _p, _i64, _i64, _p]),
+    "gl_l2_topk_f32": (_i, [_p, _p, _i64, _i64, _p, _i64, _i64, _i, _p]),
+    "gl_l2_count_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p, _i, _p]),
     "gl_keys_unpack_f32": (_i, [_p, _p, _i64, _p, _p]),
     "gl_l2_rows_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p]),
     "gl_fbb_knn_l2_host": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64, _p, _p]),

@@ -273,6 +273,21 @@ def unpack_keys(ctx, keys, nq, d, kind="u8"):
 GL_TOPK_MAX = 32
 
 
+class _OffLattice(NotImplementedError):
+    """what the exact-integer top-k / ball counts raise for rows that are on neither lattice (or on different ones): the refusal callers
+    without float_path='exact' see, and the signal on which those with it start over on fp32 rows"""
+
+
+def _check_rows_float_path(value):
+    """the float_path keyword of ball_counts / nearest_neighbours: None (exact-integer only, as ever) or 'exact'.  Needs no GPU."""
+    if value is None or value == "exact":
+        return value
+    if value == "mfma":
+        raise NotImplementedError("float_path='mfma' distances depend on the launch (the split-fp16 search is not launch-invariant): "
+                                  "top-k and ball counts on fp32 rows exist for float_path='exact' only")
+    raise ValueError("float_path must be None or 'exact', got %r" % (value,))
+
+
 def _check_k(k):
     if isinstance(k, bool) or not isinstance(k, (int, np.integer)):
         raise TypeError("k must be an integer, got %r" % (k,))
@@ -288,13 +303,13 @@ def topk_keys(bank, queries, k, n_rows=None, keys=None):
     ctx = bank.ctx
     k = _check_k(k)
     if bank.kind not in ("u8", "int"):
-        raise NotImplementedError("top-k needs rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
+        raise _OffLattice("top-k needs rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
     if not isinstance(queries, Bank):
         queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind=bank.kind, norms64=bank.wide)
     if queries.d != bank.d:
         raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
     if queries.kind != bank.kind:
-        raise NotImplementedError("top-k needs queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" % (queries.kind, bank.kind))
+        raise _OffLattice("top-k needs queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" % (queries.kind, bank.kind))
     if queries.wide != bank.wide:
         raise ValueError("the query Bank has %s row norms, the bank %s: prepare both with the same norms64" %
                          ("int64" if queries.wide else "int32", "int64" if bank.wide else "int32"))
@@ -356,7 +371,7 @@ def _attack_topk(queries, bank, k, batch_size, ctx, reduce_fn, chunk_bytes, inde
         raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_rows))
     fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
     if fq.kind == "f32":
-        raise NotImplementedError(unsupported + "the queries are off both lattices")
+        raise _OffLattice(unsupported + "the queries are off both lattices")
     keys = None
     if prepared:
         keys, _, _ = topk_keys(bank, fq, k, n_rows)
@@ -375,11 +390,11 @@ def _attack_topk(queries, bank, k, batch_size, ctx, reduce_fn, chunk_bytes, inde
             hi = min(lo + step, n_rows)
             chunk = rows(lo, hi)
             if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
-                raise NotImplementedError(unsupported + "the queries are an integer table, the bank 8-bit image codes")
+                raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
             try:
                 b = Bank.from_images(chunk, ctx, index_base=base + lo, force_kind=fq.kind, norms64=fq.wide)
             except ValueError as e:
-                raise NotImplementedError(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
+                raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
             keys, _, _ = topk_keys(b, fq, k, keys=keys)
             ctx.sync()
     if keys is None:                         # a shard without rows still takes part in the reduction
@@ -468,13 +483,13 @@ def count_balls(bank, queries, thr, n_rows=None, counts=None):
     ('u8' / 'int', either norm width).  Asynchronous."""
     ctx = bank.ctx
     if bank.kind not in ("u8", "int"):
-        raise NotImplementedError("ball counts need rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
+        raise _OffLattice("ball counts need rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
     if not isinstance(queries, Bank):
         queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind=bank.kind, norms64=bank.wide)
     if queries.d != bank.d:
         raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
     if queries.kind != bank.kind:
-        raise NotImplementedError("ball counts need queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" %
+        raise _OffLattice("ball counts need queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" %
                                   (queries.kind, bank.kind))
     if queries.wide != bank.wide:
         raise ValueError("the query Bank has %s row norms, the bank %s: prepare both with the same norms64" %
@@ -496,7 +511,8 @@ def new_counts(ctx, nq, n_thr):
     return counts
 
 
-def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0, distance="l2", lpips=None):
+def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0, distance="l2", lpips=None,
+                float_path=None, _layout=None):
     """how many bank samples lie within eps of every query: the Monte-Carlo / eps-ball membership score (Hilprecht et al., PoPETs 2019) is
     counts / n_eff, over the bank and the distance attack() searches: 'l2' (the default) or 'l2-lpips'.
 
@@ -506,7 +522,15 @@ def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chu
               reduce_fn given) -- attack()'s rule.  So counts[q, t] >= 1  <=>  attack()'s distance of q is <= eps[t].
     queries, bank, batch_size, ctx, chunk_bytes, index_base: as attack(..., distance='l2', k=...): images (numpy / torch / DeviceArray), a
               prepared `Bank`, a `GeneratedBank`; banks beyond `chunk_bytes` are streamed and the counters accumulate across the chunks.
-              Exact-integer L2 only: rows off both lattices raise NotImplementedError (the fp32 paths hold rounded distances).
+              Exact-integer L2 unless float_path='exact': rows off both lattices raise NotImplementedError.
+    float_path: None (default: as above; $GANLEAKS_FLOAT_PATH is not consulted) or 'exact': as soon as either side is on neither lattice (or
+              the two are on different ones) the WHOLE call runs on fp32 rows -- 8-bit codes and integer tables decoded as Bank.as_f32()
+              decodes them -- and counts[q, t] = #{ n < n_eff : D32(q, n) <= float32(eps[t]) } with D32 the fixed-order float32 distance
+              attack(..., float_path='exact') minimises, bit for bit (gl_l2_count_f32: that search's K loop with a counting epilogue; a
+              function of the two rows alone, so nothing depends on chunking, prepared rows or sharding).  Counters of an exact-integer pass
+              over earlier chunks are dropped and the stream starts over, because dist32(S) and D32 differ in the last bit.  Inputs on one
+              lattice take the exact-integer path, unchanged.  The shards of one sharded call must agree on the layout (DeviceGroup sees to
+              it).  'mfma' raises NotImplementedError (not launch-invariant), anything else ValueError.
     reduce_fn: optional callable(counts DeviceArray [Q, T] uint64) -> DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts).
     distance='l2-lpips' (0.2 * LPIPS + L2, the reference's fbb distance: attack_models/fbb.py:148, utils.py:166-176; `lpips`: the LpipsModel,
               default lpips.default_model()): counts[q, t] = #{ n < n_eff : D32(q, n) <= float32(eps[t]) } with D32 the float32 distance
@@ -517,8 +541,21 @@ def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chu
     if distance not in ("l2", "l2-lpips"):
         raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
     e32 = _check_eps(eps)                    # before any Context: these checks run without a GPU
+    float_path = _check_rows_float_path(float_path)
     if distance == "l2-lpips":
         return _ball_counts_lpips(queries, bank, e32, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base)
+    if float_path is None:
+        return _ball_counts_l2(queries, bank, e32, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    if _layout != "f32":
+        try:
+            return _ball_counts_l2(queries, bank, e32, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+        except _OffLattice:
+            pass                             # nothing of the integer pass survives: the fp32 rows start over
+    return _float_rows(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base, eps=e32)
+
+
+def _ball_counts_l2(queries, bank, e32, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """ball_counts(distance='l2') on the exact-integer path"""
     unsupported = "ball counts are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
     if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
         raise NotImplementedError(unsupported + "got LPIPS feature rows")
@@ -535,10 +572,10 @@ def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chu
     if n_rows == 0 and reduce_fn is None:
         raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
     if prepared and bank.kind == "f32":
-        raise NotImplementedError(unsupported + "the bank is off both lattices")
+        raise _OffLattice(unsupported + "the bank is off both lattices")
     fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
     if fq.kind == "f32":
-        raise NotImplementedError(unsupported + "the queries are off both lattices")
+        raise _OffLattice(unsupported + "the queries are off both lattices")
     # the library sees the thresholds sorted; the columns are put back in the caller's order at the end
     thr = eps_to_ssd(e32, fq.d, fq.kind)
     order = np.argsort(thr, kind="stable")
@@ -560,16 +597,136 @@ def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chu
             hi = min(lo + step, n_rows)
             chunk = rows(lo, hi)
             if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
-                raise NotImplementedError(unsupported + "the queries are an integer table, the bank 8-bit image codes")
+                raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
             try:
                 b = Bank.from_images(chunk, ctx, index_base=base + lo, force_kind=fq.kind, norms64=fq.wide)
             except ValueError as e:
-                raise NotImplementedError(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
+                raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
             count_balls(b, fq, thr[order], counts=counts)
             ctx.sync()
     if reduce_fn is not None:                # (a shard without rows takes part with zeros)
         counts = reduce_fn(counts)
     host = counts.numpy()[:fq.n]
+    out = np.empty((fq.n, len(thr)), np.int64)
+    out[:, order] = host.astype(np.int64)
+    return out
+
+
+def host_rows_kind(rows):
+    """the Bank kind Bank.from_images would give a HOST array (numpy / CPU torch), by numpy alone: 'u8' (8-bit codes, or floats on the image
+    lattice fl32(2*(u/255.)-1)), 'int' (floats equal to an integer 0..255) or 'f32'.  For callers that must settle the layout of a sharded
+    float_path='exact' call before any shard starts (DeviceGroup)."""
+    if _is_torch(rows):
+        rows = rows.numpy()
+    rows = np.asarray(rows)
+    if rows.dtype == np.uint8:
+        return "u8"
+    if rows.dtype.kind != "f":
+        raise TypeError("images must be uint8 or float, got %r" % (rows.dtype,))
+    u = np.arange(256, dtype=np.float64)
+    flat = rows.reshape(len(rows), -1)
+    step = max(1, (1 << 24) // max(flat.shape[1], 1))
+    for kind, lut in (("u8", (2.0 * (u / 255.0) - 1.0).astype(np.float32)), ("int", u.astype(np.float32))):
+        if all(np.isin(flat[lo:lo + step].astype(np.float32, copy=False), lut).all() for lo in range(0, len(flat), step)):
+            return kind
+    return "f32"
+
+
+def topk_keys_f32(bank, queries, k, n_rows=None, keys=None):
+    """topk_keys for 'f32' Banks: the k smallest keys float_bits(D32) << 32 | global index over bank rows [0, n_rows), folded into `keys`
+    (gl_l2_topk_f32).  DeviceArray [Q, k] uint64; unpack with unpack_topk_f32."""
+    ctx = bank.ctx
+    k = _check_k(k)
+    if bank.kind != "f32" or queries.kind != "f32":
+        raise ValueError("topk_keys_f32 takes 'f32' Banks (Bank.as_f32()), got %r queries, %r bank" % (queries.kind, bank.kind))
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if keys is None:
+        keys = ctx.empty((max(queries.n, 1), k), np.uint64)
+        check(ctx.lib.gl_topk_init(ctx.handle, _p(keys.ptr), queries.n, k))
+    check(ctx.lib.gl_l2_topk_f32(ctx.handle, _p(bank.rows_f32.ptr), n_rows, bank.index_base, _p(queries.rows_f32.ptr), queries.n, bank.d, k,
+                                 _p(keys.ptr)))
+    return keys
+
+
+def count_balls_f32(bank, queries, thr, n_rows=None, counts=None):
+    """count_balls for 'f32' Banks: counts[q, t] += #{ n < n_rows : D32(q, n) <= thr[t] } for the ascending float32 radii `thr`
+    (gl_l2_count_f32).  DeviceArray [Q, T] uint64.  Asynchronous."""
+    ctx = bank.ctx
+    if bank.kind != "f32" or queries.kind != "f32":
+        raise ValueError("count_balls_f32 takes 'f32' Banks (Bank.as_f32()), got %r queries, %r bank" % (queries.kind, bank.kind))
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    thr = np.ascontiguousarray(thr, np.float32)
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if counts is None:
+        counts = new_counts(ctx, queries.n, len(thr))
+    check(ctx.lib.gl_l2_count_f32(ctx.handle, _p(bank.rows_f32.ptr), n_rows, _p(queries.rows_f32.ptr), queries.n, bank.d, thr.ctypes.data_as(_p),
+                                  len(thr), _p(counts.ptr)))
+    return counts
+
+
+def _float_rows(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base, k=None, eps=None):
+    """nearest_neighbours / ball_counts (distance='l2', float_path='exact') with every row in fp32: 8-bit codes and integer tables decoded,
+    floats as they are.  The bank passes through HBM in chunks of at most `chunk_bytes` of fp32 rows (one chunk when it fits), every chunk
+    folds into the same [Q, k] lists (k given) or adds to the same [Q, T] counters (eps: float32 radii in the caller's order)."""
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError("distance='l2' takes images or tables; got LPIPS feature rows")
+    prepared = isinstance(bank, Bank)
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx = bank.ctx
+        base = bank.index_base
+    else:
+        ctx = ctx or Context.get()
+        base = int(index_base)
+    shard = reduce_fn is not None or base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    if k is not None and not shard and k > n_rows:
+        raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_rows))
+    fq = queries.as_f32() if isinstance(queries, Bank) else Bank.from_images(queries, ctx, force_kind="f32")
+    if eps is not None:
+        # the library sees the radii sorted; the columns are put back in the caller's order at the end
+        order = np.argsort(eps, kind="stable")
+        thr = np.ascontiguousarray(eps[order])
+    acc = None                               # the key lists or the counters
+
+    def fold(b, n):
+        return topk_keys_f32(b, fq, k, n, acc) if k is not None else count_balls_f32(b, fq, thr, n, acc)
+
+    if prepared:
+        acc = fold(bank.as_f32(), n_rows)
+    else:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (4 * fq.d)))
+
+        def rows(lo, hi):
+            if generated:
+                return bank.rows(lo, hi)
+            if isinstance(bank, DeviceArray):
+                return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+            return bank[lo:hi]
+
+        for lo in range(0, n_rows, step):
+            hi = min(lo + step, n_rows)
+            b = Bank.from_images(rows(lo, hi), ctx, index_base=base + lo, force_kind="f32")
+            acc = fold(b, b.n)
+            ctx.sync()
+    if k is not None:
+        if acc is None:                      # a shard without rows still takes part in the reduction
+            acc = ctx.empty((max(fq.n, 1), k), np.uint64)
+            check(ctx.lib.gl_topk_init(ctx.handle, _p(acc.ptr), fq.n, k))
+        if reduce_fn is not None:
+            acc = reduce_fn(acc)
+        return unpack_topk_f32(ctx, acc, fq.n, k)
+    if acc is None:
+        acc = new_counts(ctx, fq.n, len(thr))
+    if reduce_fn is not None:
+        acc = reduce_fn(acc)
+    host = acc.numpy()[:fq.n]
     out = np.empty((fq.n, len(thr)), np.int64)
     out[:, order] = host.astype(np.int64)
     return out
@@ -777,13 +934,24 @@ def _ball_counts_lpips(queries, bank, e32, batch_size, ctx, reduce_fn, model, ch
     return out
 
 
-def nearest_neighbours(queries, bank, k, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, index_base=0):
+def nearest_neighbours(queries, bank, k, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, index_base=0,
+                       float_path=None, _layout=None):
     """the k nearest bank samples of every query: custom_knn (attack_models/fbb.py:73-88) keeping the args.K nearest samples (fbb.py:32)
     under either distance of attack(), 'l2-lpips' -- the one fbb.main hard-wires (fbb.py:148) -- by default.
 
     returns (dist float32 [Q, k], idx int64 [Q, k]), per query ordered by (distance, global index); column 0 is attack()'s result.
     distance='l2': attack(..., distance='l2', k=k) as it is (exact-integer L2; see there).  attack(k=) is the older spelling and stays
               exact-integer only: attack(..., distance='l2-lpips', k=) keeps raising NotImplementedError, this function is the way in.
+    float_path (distance='l2'): None (default: as above, rows off both lattices raise NotImplementedError; $GANLEAKS_FLOAT_PATH is not
+              consulted) or 'exact': as soon as either side is on neither lattice (or the two are on different ones) the WHOLE call runs on
+              fp32 rows -- 8-bit codes and integer tables decoded as Bank.as_f32() decodes them -- and the lists are the k smallest keys
+              float_bits(D32(q, n)) << 32 | n, D32 the fixed-order float32 distance attack(..., float_path='exact') minimises, bit for bit
+              (gl_l2_topk_f32: that search's K loop with a storing epilogue).  D32 is a function of the two rows alone, so the lists equal a
+              stable argsort of the distance matrix, column 0 is attack(float_path='exact'), ball_counts(eps=dist[q, j],
+              float_path='exact')[q] >= j + 1, and nothing depends on tile, workspace slice, chunking, prepared rows or shards.  Lists of an
+              exact-integer pass over earlier chunks are dropped and the stream starts over.  Inputs on one lattice take the exact-integer
+              path, unchanged.  The shards of one sharded call must agree on the layout (DeviceGroup sees to it).  'mfma' raises
+              NotImplementedError (not launch-invariant), anything else ValueError.
     distance='l2-lpips': the k smallest keys float_bits(D32(q, n)) << 32 | n over n < n_eff, D32 the float32 distance
               attack(..., distance='l2-lpips') minimises, ball_counts(..., distance='l2-lpips') counts and pair_distances stores, bit for
               bit (the search kernel with a storing epilogue, then the selection of the exact-integer top-k).  So the lists equal a stable
@@ -798,9 +966,16 @@ def nearest_neighbours(queries, bank, k, distance="l2-lpips", batch_size=64, ctx
     if distance not in ("l2", "l2-lpips"):
         raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
     k = _check_k(k)                          # before any Context: these checks run without a GPU
+    float_path = _check_rows_float_path(float_path)
     if distance == "l2":
-        return attack(queries, bank, distance="l2", batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, chunk_bytes=chunk_bytes,
-                      index_base=index_base, k=k)
+        if float_path is None or _layout != "f32":
+            try:
+                return attack(queries, bank, distance="l2", batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, chunk_bytes=chunk_bytes,
+                              index_base=index_base, k=k)
+            except _OffLattice:
+                if float_path is None:
+                    raise
+        return _float_rows(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base, k=k)
     from . import lpips as _lp
     prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
     if reduce_fn is None and index_base == 0 and k > n_rows:

@@ -6,8 +6,12 @@ unchanged.  All K neighbours come from ONE pass over the bank (ganleaks_amd.atta
 
     python -m ganleaks_amd.attack_models.knn --syn_data_path ... --pos_data_dir ... --neg_data_dir ... [--K k] [--distance {l2,l2-lpips}]
 
+--syn_data_path, --pos_data_dir, --neg_data_dir: a folder of PNG files (8-bit codes), or a file of floats (bank_io.load_rows): an .npz with
+                img_r01 [N,H,W,C] in [0, 1] (VAEGAN's generated.npz; must be --resolution sized), or a 2-D .npy table (medGAN's
+                synthetic.npy; --distance l2 only)
 --K             1..32 (default 5, fbb.py:32)
---distance      l2: Loss('l2'), attack_models/utils.py:161-164, exact-integer L2 on the int8 matrix cores.
+--distance      l2: Loss('l2'), attack_models/utils.py:161-164, exact-integer L2 on the int8 matrix cores; rows off both lattices (float
+                images, continuous tables) in the fixed-order float32 arithmetic of attack(float_path='exact').
                 l2-lpips: 0.2 * LPIPS + L2, the distance fbb.main hard-wires (fbb.py:148, utils.py:166-176): the l2-lpips search kernel with
                 a storing epilogue and a selection; weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH as in fbb.py
 Files under ./knn_attack/<exp_name>/:
@@ -25,7 +29,7 @@ import numpy as np
 
 from ..attack import GL_TOPK_MAX, nearest_neighbours, prepare_queries
 from .fbb import shard_devices, update_args  # noqa: F401  (update_args: the YAML overlay of the command line)
-from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, save_files
+from .utils import check_folder, save_files
 
 
 def parse_arguments(argv=None):
@@ -67,25 +71,31 @@ def main(args):
     print("\n".join(lines))
 
     resolution = args.resolution
-    syn_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.syn_data_path, ext='png'), resolution)
-    pos_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.pos_data_dir, ext='png'), resolution)
-    neg_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.neg_data_dir, ext='png'), resolution)
-    both = np.concatenate([pos_query_imgs, neg_query_imgs])
+    from ..bank_io import concat_rows, load_rows
+    syn_imgs = load_rows(args.syn_data_path, resolution)
+    pos_query_imgs = load_rows(args.pos_data_dir, resolution)
+    neg_query_imgs = load_rows(args.neg_data_dir, resolution)
+    both = concat_rows(pos_query_imgs, neg_query_imgs)
     n_pos = len(pos_query_imgs)
+    if distance == "l2-lpips" and (syn_imgs.ndim != 4 or both.ndim != 4):
+        raise SystemExit("--distance l2-lpips needs images; a 2-D table takes --distance l2")
+    float_path = "exact" if distance == "l2" else None
+    floats = syn_imgs.dtype != np.uint8 or both.dtype != np.uint8
 
     devices = shard_devices(args)
     if devices is not None:
         from ..shard import DeviceGroup
         with DeviceGroup(devices) as group:
-            dist, idx = group.nearest_neighbours(both, bank=syn_imgs, k=K, batch_size=args.BATCH_SIZE, distance=distance)
+            dist, idx = group.nearest_neighbours(both, bank=syn_imgs, k=K, batch_size=args.BATCH_SIZE, distance=distance, float_path=float_path)
     else:
         model = None
         if distance == "l2-lpips":
             from ..lpips import default_model
             model = default_model()
         # prepared only when the rows fit the streaming budget; otherwise nearest_neighbours slices the raw queries itself
-        queries = prepare_queries(both, distance, lpips=model)
-        dist, idx = nearest_neighbours(queries, syn_imgs, K, distance=distance, batch_size=args.BATCH_SIZE, lpips=model)
+        # (float images under l2-lpips stay raw too: the search settles the row layout of both sides itself)
+        queries = both if floats and distance == "l2-lpips" else prepare_queries(both, distance, lpips=model)
+        dist, idx = nearest_neighbours(queries, syn_imgs, K, distance=distance, batch_size=args.BATCH_SIZE, lpips=model, float_path=float_path)
 
     dist64 = dist.astype(np.float64)
     loss = dist64.mean(axis=1, keepdims=True)            # K = 1: the distance itself, fbb.py's pos_loss.npy

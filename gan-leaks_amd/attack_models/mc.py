@@ -10,7 +10,11 @@ full-black-box attack, n_eff = (N // BATCH_SIZE) * BATCH_SIZE (fbb.py:77).  All 
     python -m ganleaks_amd.attack_models.mc --syn_data_path ... --pos_data_dir ... --neg_data_dir ... [--eps e1,e2,... | --eps_quantile q1,q2,...]
                                             [--distance {l2,l2-lpips}]
 
---distance      l2 (default): Loss('l2'), attack_models/utils.py:161-164, exact-integer L2 on the int8 matrix cores.
+--syn_data_path, --pos_data_dir, --neg_data_dir: a folder of PNG files (8-bit codes), or a file of floats (bank_io.load_rows): an .npz with
+                img_r01 [N,H,W,C] in [0, 1] (VAEGAN's generated.npz; must be --resolution sized), or a 2-D .npy table (medGAN's
+                synthetic.npy, PCA-projected rows; --distance l2 only)
+--distance      l2 (default): Loss('l2'), attack_models/utils.py:161-164, exact-integer L2 on the int8 matrix cores; rows off both lattices
+                (float images, continuous tables) in the fixed-order float32 arithmetic of attack(float_path='exact').
                 l2-lpips: 0.2 * LPIPS + L2, the distance fbb.main hard-wires (fbb.py:148, utils.py:166-176), counted by the l2-lpips search
                 kernel with a counting epilogue; weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH as in fbb.py
 
@@ -31,7 +35,7 @@ import numpy as np
 
 from ..attack import GL_COUNT_MAX_T, Bank, _budget_bytes, attack, ball_counts, prepare_queries
 from .fbb import shard_devices, update_args  # noqa: F401  (update_args: the YAML overlay of the command line)
-from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, save_files
+from .utils import check_folder, save_files
 
 
 def parse_arguments(argv=None):
@@ -96,11 +100,15 @@ def main(args):
     print("\n".join(lines))
 
     resolution = args.resolution
-    syn_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.syn_data_path, ext='png'), resolution)
-    pos_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.pos_data_dir, ext='png'), resolution)
-    neg_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.neg_data_dir, ext='png'), resolution)
-    both = np.concatenate([pos_query_imgs, neg_query_imgs])
+    from ..bank_io import concat_rows, load_rows
+    syn_imgs = load_rows(args.syn_data_path, resolution)
+    pos_query_imgs = load_rows(args.pos_data_dir, resolution)
+    neg_query_imgs = load_rows(args.neg_data_dir, resolution)
+    both = concat_rows(pos_query_imgs, neg_query_imgs)
     n_pos = len(pos_query_imgs)
+    if distance == "l2-lpips" and (syn_imgs.ndim != 4 or both.ndim != 4):
+        raise SystemExit("--distance l2-lpips needs images; a 2-D table takes --distance l2")
+    floats = syn_imgs.dtype != np.uint8 or both.dtype != np.uint8
     n_eff = (len(syn_imgs) // args.BATCH_SIZE) * args.BATCH_SIZE
     if n_eff == 0:
         raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % args.BATCH_SIZE)
@@ -115,7 +123,8 @@ def main(args):
             from ..lpips import default_model
             if group is None:                        # (a group builds one model per context from the same local files)
                 model = default_model()
-                queries = prepare_queries(both, distance, lpips=model)
+                # (float images stay raw: the search settles the row layout of both sides itself)
+                queries = both if floats else prepare_queries(both, distance, lpips=model)
                 bank = syn_imgs
                 if getattr(queries, "kind", None) == "feat" and n_eff * queries.K * queries.V.dtype.itemsize <= _budget_bytes():
                     # the bank's feature rows are computed once for both passes when they fit the streaming budget
@@ -129,12 +138,16 @@ def main(args):
             queries = prepare_queries(both, "l2")
             d = int(np.prod(syn_imgs.shape[1:], dtype=np.int64))
             # the bank's int8 rows are prepared once for both passes when they fit the streaming budget; otherwise both stream the images
-            bank = Bank.from_images(syn_imgs[:n_eff], queries.ctx, norms64=queries.wide) if 2 * d * n_eff <= _budget_bytes() else syn_imgs
-            nearest = lambda: attack(queries, bank, distance="l2", batch_size=args.BATCH_SIZE)[0]                 # noqa: E731
-            count = lambda eps: ball_counts(queries, bank, eps, batch_size=args.BATCH_SIZE)                         # noqa: E731
+            # (fp32 rows take 4 bytes per value; 8-bit codes are kept next to the int8 rows when float queries will need them decoded)
+            row_bytes = (2 if syn_imgs.dtype == np.uint8 else 4) * d
+            bank = (Bank.from_images(syn_imgs[:n_eff], queries.ctx, norms64=queries.wide, keep_u8=queries.kind == "f32")
+                    if row_bytes * n_eff <= _budget_bytes() else syn_imgs)
+            # float_path='exact' spelt out: the radius read from the nearest distances must be an attained D32 of the counting pass
+            nearest = lambda: attack(queries, bank, distance="l2", batch_size=args.BATCH_SIZE, float_path="exact")[0]   # noqa: E731
+            count = lambda eps: ball_counts(queries, bank, eps, batch_size=args.BATCH_SIZE, float_path="exact")         # noqa: E731
         else:
             nearest = lambda: group.attack(both, bank=syn_imgs, distance="l2", batch_size=args.BATCH_SIZE)[0]      # noqa: E731
-            count = lambda eps: group.ball_counts(both, bank=syn_imgs, eps=eps, batch_size=args.BATCH_SIZE)         # noqa: E731
+            count = lambda eps: group.ball_counts(both, bank=syn_imgs, eps=eps, batch_size=args.BATCH_SIZE, float_path="exact")   # noqa: E731
         if mode == "eps":
             with np.errstate(over="ignore"):
                 eps = np.asarray(values, np.float64).astype(np.float32)

@@ -4,6 +4,8 @@
                   `image_{i}.png` in generation order, 8-bit RGB
   load_png_bank   attack_models/fbb.py:133-135 via utils.get_filepaths_from_dir + read_image: files in sorted
                   path-STRING order (image_10 < image_2), so bank index != generation index; `order` gives the map.
+  load_rows       the one reader of the attack drivers (knn.py, mc.py): a PNG folder as above, or the float files the generators write --
+                  VAEGAN's generated.npz (gan_models/vaegan/sample.py:55-59) and medGAN's synthetic.npy (gan_models/medgan/train.py:311-318)
 """
 from __future__ import annotations
 
@@ -53,3 +55,38 @@ def load_png_bank(data_dir, resolution=64, workers=None):
 def generation_order(paths, prefix="image_"):
     """generation index of every file in the loaded order (inverse of the sorted()-on-strings shuffle)"""
     return np.array([int(os.path.basename(p)[len(prefix):-4]) for p in paths], np.int64)
+
+
+def load_rows(path, resolution=64):
+    """the rows an attack driver searches, from a folder or a file:
+      a directory       -> uint8 [N,3,res,res] 8-bit codes, read as load_png_bank reads them (resized to `resolution`)
+      .npz with img_r01 -> VAEGAN's generated.npz, [N,H,W,C] float in [0, 1]: float32 [N,C,H,W] rows fl32(2 x - 1), the generator's own
+                           range.  H and W must equal `resolution` (floats are not resized): ValueError otherwise
+      a 2-D .npy        -> medGAN's synthetic.npy (or any table): float32 [N,F] as it is"""
+    if os.path.isdir(path):
+        return load_png_bank(path, resolution)[0]
+    ext = os.path.splitext(path)[1].lower()
+    if ext == ".npz":
+        with np.load(path) as f:
+            if "img_r01" not in f.files:
+                raise ValueError("%s holds no 'img_r01' array (found %s)" % (path, ", ".join(f.files)))
+            x = np.asarray(f["img_r01"], np.float32)
+        if x.ndim != 4:
+            raise ValueError("%s: img_r01 must be [N,H,W,C], got shape %r" % (path, x.shape))
+        if x.shape[1] != int(resolution) or x.shape[2] != int(resolution):
+            raise ValueError("%s holds %d x %d images, --resolution is %d; float images are not resized" % (path, x.shape[1], x.shape[2], int(resolution)))
+        return np.ascontiguousarray((np.float32(2.0) * x - np.float32(1.0)).transpose(0, 3, 1, 2))
+    if ext == ".npy":
+        x = np.load(path)
+        if x.ndim != 2 or x.dtype.kind not in "fiub":
+            raise ValueError("%s: expected a 2-D numeric table, got %s %r" % (path, x.dtype, x.shape))
+        return np.ascontiguousarray(x, np.float32)
+    raise ValueError("%s is neither a folder of PNG files, an .npz with img_r01 nor a 2-D .npy table" % (path,))
+
+
+def concat_rows(first, second):
+    """two row sets of load_rows as one query array.  8-bit codes next to floats are decoded first, fl32(2 * (u / 255.) - 1) in float64 as
+    attack_models/utils.py:82 does (what gl_decode_u8 yields), so that both parts mean the same values."""
+    if first.dtype != second.dtype:
+        first, second = [(2.0 * (a.astype(np.float64) / 255.0) - 1.0).astype(np.float32) if a.dtype == np.uint8 else a for a in (first, second)]
+    return np.concatenate([first, second])

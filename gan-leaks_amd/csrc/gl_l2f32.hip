@@ -12,7 +12,9 @@
 // VALU kernel (2 ops per element pair; the matrix cores cannot form y - x before squaring without losing
 // the fp32 difference).  Tile: 64 queries x 64 bank rows per workgroup, 256 threads x (4 x 4) pairs,
 // K slices of 32 floats staged through LDS (row stride 36 floats: conflict-free float4 reads).
-#include "gl_common.h"
+#include "gl_count_epi.h"
+#include "gl_topk_sel.h"
+#include <cmath>
 
 namespace {
 
@@ -33,15 +35,26 @@ __device__ __forceinline__ float4 load_row4(const float *__restrict__ base, int6
     return v;
 }
 
-__global__ void __launch_bounds__(THREADS) l2_knn_f32_kernel(const float *__restrict__ bank, int64_t n_rows, int64_t index_base,
-                                                              const float *__restrict__ query, int64_t nq, int64_t d,
-                                                              unsigned long long *__restrict__ keys, int q_tiles)
+// what an epilogue does with the tile's distances
+template <int EPI> struct f32_sink;
+template <> struct f32_sink<0> {
+    unsigned long long *keys;        // [nq], atomicMin of float_bits(D32) << 32 | index_base + n
+    int64_t index_base;
+};
+template <> struct f32_sink<1> {
+    gl_count::count_args<float> a;
+    unsigned long long *counts;      // [nq][a.pitch]
+};
+template <> struct f32_sink<2> {
+    unsigned *pieces;                // [ceil(n_rows / 4)][nq][4], n_rows and nq the kernel's (one slice)
+};
+
+// The K loop of one 64 x 64 tile, shared by every epilogue: dist[a][b] = D32(query q0 + tq * 4 + a, bank row n0 + tn + 16 * b), the chain of
+// the header comment.  Rows beyond n_rows and queries beyond nq are zero-filled in LDS: their distance is finite and the epilogues mask them.
+// Ends behind a barrier: sq and sb are free when it returns.
+__device__ __forceinline__ void pair_tile_f32(const float *__restrict__ bank, int64_t n_rows, int64_t n0, const float *__restrict__ query, int64_t nq,
+                                              int64_t q0, int64_t d, float *sq, float *sb, int tid, float (&dist)[4][4])
 {
-    __shared__ __attribute__((aligned(16))) float sq[TQ * LDS_STRIDE];
-    __shared__ __attribute__((aligned(16))) float sb[TN * LDS_STRIDE];
-    const int qt = blockIdx.x % q_tiles, nt = blockIdx.x / q_tiles;
-    const int64_t q0 = (int64_t)qt * TQ, n0 = (int64_t)nt * TN;
-    const int tid = threadIdx.x;
     const int tq = tid >> 4, tn = tid & 15;          // 16 x 16 threads, each 4 queries x 4 bank rows
     const bool vec = ((d & 3) == 0) && (((reinterpret_cast<uintptr_t>(bank) | reinterpret_cast<uintptr_t>(query)) & 15) == 0);
 
@@ -86,24 +99,121 @@ __global__ void __launch_bounds__(THREADS) l2_knn_f32_kernel(const float *__rest
 
     const float fd = (float)d;
 #pragma unroll
-    for (int a = 0; a < 4; ++a) {
-        const int64_t q = q0 + tq * 4 + a;
-        unsigned long long best = ~0ull;
+    for (int a = 0; a < 4; ++a)
 #pragma unroll
         for (int b = 0; b < 4; ++b) {
-            const int64_t n = n0 + tn + 16 * b;
             const float s = __fadd_rn(__fadd_rn(acc[a][b][0], acc[a][b][1]), __fadd_rn(acc[a][b][2], acc[a][b][3]));
-            const float dist = __fdiv_rn(s, fd);
-            const unsigned long long key = ((unsigned long long)__float_as_uint(dist) << 32) | (unsigned long long)(index_base + n);
-            if (n < n_rows && key < best) best = key;
+            dist[a][b] = __fdiv_rn(s, fd);
         }
-        // the 16 threads tn = 0..15 (consecutive lanes) hold the other bank rows of this query
+}
+
+// EPI 0: keys[q] = min(keys[q], float_bits(D32) << 32 | global index)   (gl_l2_knn_f32)
+// EPI 1: counts[q][col0 + t] += #{ n : D32(q, n) <= thr[t] }, the steps of gl_count_epi.h in this kernel's thread layout: one compare per pair
+//        against the largest radius and __syncthreads_or, so that tiles without a hit leave; the others turn the tile through the freed slice
+//        buffers so that 4 neighbouring lanes hold a query's 64 distances, fold the per-threshold counts with two shuffles (no second wave
+//        shares the query: no LDS table is needed to fold waves) and add ONE value per non-zero (query, t) with a 64-bit atomicAdd.
+// EPI 2: float_bits(D32) as pieces[((n >> 2) * nq + q) * 4 + (n & 3)] for gl_topk_select_merge(elem = 4, shift = 32).  A thread's four rows are
+//        16 apart, so the tile is turned through LDS and leaves as 16-byte pieces, 64 consecutive queries (1 KiB) per wave and store.
+//        D32 >= +0 (a sum of squares divided by d > 0 never gives -0) and is not NaN for finite rows: unsigned order of the bits is the
+//        order of the floats, and 0xFFFFFFFF, the value of a masked piece, never occurs.
+template <int EPI>
+__global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__restrict__ bank, int64_t n_rows, const float *__restrict__ query, int64_t nq,
+                                                                int64_t d, int q_tiles, const f32_sink<EPI> sink)
+{
+    __shared__ __attribute__((aligned(16))) float smem[(TQ + TN) * LDS_STRIDE];
+    const int qt = blockIdx.x % q_tiles, nt = blockIdx.x / q_tiles;
+    const int64_t q0 = (int64_t)qt * TQ, n0 = (int64_t)nt * TN;
+    const int tid = threadIdx.x;
+    const int tq = tid >> 4, tn = tid & 15;
+
+    float dist[4][4];
+    pair_tile_f32(bank, n_rows, n0, query, nq, q0, d, smem, smem + TQ * LDS_STRIDE, tid, dist);
+
+    if constexpr (EPI == 0) {
 #pragma unroll
-        for (int o = 8; o > 0; o >>= 1) {
-            const unsigned long long other = __shfl_xor(best, o, 64);
-            best = other < best ? other : best;
+        for (int a = 0; a < 4; ++a) {
+            const int64_t q = q0 + tq * 4 + a;
+            unsigned long long best = ~0ull;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const int64_t n = n0 + tn + 16 * b;
+                const unsigned long long key = ((unsigned long long)__float_as_uint(dist[a][b]) << 32) | (unsigned long long)(sink.index_base + n);
+                if (n < n_rows && key < best) best = key;
+            }
+            // the 16 threads tn = 0..15 (consecutive lanes) hold the other bank rows of this query
+#pragma unroll
+            for (int o = 8; o > 0; o >>= 1) {
+                const unsigned long long other = __shfl_xor(best, o, 64);
+                best = other < best ? other : best;
+            }
+            if (tn == 0 && q < nq && best != ~0ull) atomicMin(&sink.keys[q], best);
         }
-        if (tn == 0 && q < nq && best != ~0ull) atomicMin(&keys[q], best);
+    } else {
+        const int n_left = gl_count::rows_left(n_rows, n0), q_left = gl_count::rows_left(nq, q0);
+        unsigned valid = 0;                           // bit a * 4 + b: the pair is a real one
+#pragma unroll
+        for (int a = 0; a < 4; ++a)
+#pragma unroll
+            for (int b = 0; b < 4; ++b) valid |= ((tq * 4 + a < q_left && tn + 16 * b < n_left) ? 1u : 0u) << (a * 4 + b);
+
+        if constexpr (EPI == 1) {
+            const gl_count::count_args<float> &A = sink.a;
+            const float top = A.thr[A.n - 1];
+            int hit = 0;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) hit |= (((valid >> (a * 4 + b)) & 1u) && dist[a][b] <= top) ? 1 : 0;
+            if (!__syncthreads_or(hit)) return;
+
+            // the tile turned through LDS, query-major (masked pairs as NaN, which no radius meets): a query's 64 distances then sit with 4
+            // neighbouring lanes, 16 each, and the per-threshold work needs nothing of the K loop's registers
+            constexpr int TS = TN + 4;
+            float *turn = smem;                                     // [TQ][TS]
+            static_assert(TQ * TS + GL_COUNT_MAX_T <= (TQ + TN) * LDS_STRIDE, "the turned tile and the radii must fit the slice buffers");
+            float *thr = smem + TQ * TS;                            // a run-time index into kernel arguments would cost registers
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) turn[(tq * 4 + a) * TS + tn + 16 * b] = ((valid >> (a * 4 + b)) & 1u) ? dist[a][b] : __builtin_nanf("");
+            if (tid == 0) {
+#pragma unroll
+                for (int t = 0; t < GL_COUNT_MAX_T; ++t) thr[t] = A.thr[t];
+            }
+            __syncthreads();
+            const int ql = tid >> 2, part = tid & 3;
+            float4 v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const float4 *>(&turn[ql * TS + part * 16 + i * 4]);
+            for (int t = A.n - 1; t >= 0; --t) {
+                const float th = thr[t];
+                unsigned c = 0;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) c += (v[i].x <= th ? 1u : 0u) + (v[i].y <= th ? 1u : 0u) + (v[i].z <= th ? 1u : 0u) + (v[i].w <= th ? 1u : 0u);
+                if (!__any(c != 0u)) break;                         // ascending radii: the wave holds nothing within the smaller ones either
+                c += __shfl_xor(c, 1, 64);
+                c += __shfl_xor(c, 2, 64);
+                if (part == 0 && c != 0u) atomicAdd(&sink.counts[(q0 + ql) * A.pitch + A.col0 + t], (unsigned long long)c);
+            }
+        } else {
+            constexpr int TS = TN + 4;                 // row stride of the turned tile: 16-byte aligned pieces
+            static_assert(TQ * TS <= (TQ + TN) * LDS_STRIDE, "the turned tile must fit the slice buffers");
+            unsigned *turn = reinterpret_cast<unsigned *>(smem);   // [TQ][TS]: query-major, bank rows contiguous
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    turn[(tq * 4 + a) * TS + tn + 16 * b] = ((valid >> (a * 4 + b)) & 1u) ? __float_as_uint(dist[a][b]) : 0xFFFFFFFFu;
+            __syncthreads();
+            // 64 queries x 16 pieces, 4 per thread; consecutive lanes take consecutive queries of one piece row
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int e = tid + i * THREADS;
+                const int ql = e & (TQ - 1), g = e >> 6;
+                if (ql < q_left && g * 4 < n_left)
+                    *reinterpret_cast<uint4 *>(sink.pieces + (((n0 >> 2) + g) * nq + q0 + ql) * 4) = *reinterpret_cast<const uint4 *>(&turn[ql * TS + g * 4]);
+            }
+        }
     }
 }
 
@@ -147,9 +257,95 @@ int gl_l2_knn_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, int64_t in
     GL_REQUIRE(bank_dev && query_dev && keys_dev, "gl_l2_knn_f32: NULL device pointer");
     const int64_t q_tiles = gl_ceil_div(nq, TQ), n_tiles = gl_ceil_div(n_rows, TN);
     GL_REQUIRE(q_tiles * n_tiles < (1ll << 31), "gl_l2_knn_f32: grid too large");
-    hipLaunchKernelGGL(l2_knn_f32_kernel, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev, n_rows, index_base, query_dev,
-                       nq, d, reinterpret_cast<unsigned long long *>(keys_dev), (int)q_tiles);
+    f32_sink<0> sink;
+    sink.keys = reinterpret_cast<unsigned long long *>(keys_dev);
+    sink.index_base = index_base;
+    hipLaunchKernelGGL(l2_pairs_f32_kernel<0>, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev, n_rows, query_dev, nq, d,
+                       (int)q_tiles, sink);
     GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_l2_count_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const float *thr_host, int n_thr,
+                    uint64_t *counts_dev)
+{
+    static const char *fn = "gl_l2_count_f32";
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && n_rows >= 0 && nq >= 0 && d > 0, "%s: bad sizes", fn);
+    GL_REQUIRE(n_thr >= 1 && n_thr <= GL_COUNT_MAX_T, "%s: n_thr=%d outside [1, %d]", fn, n_thr, GL_COUNT_MAX_T);
+    GL_REQUIRE(thr_host, "%s: NULL thresholds", fn);
+    for (int t = 0; t < n_thr; ++t) {
+        GL_REQUIRE(!std::isnan(thr_host[t]), "%s: thr[%d] is NaN", fn, t);
+        GL_REQUIRE(t == 0 || thr_host[t - 1] <= thr_host[t], "%s: thresholds must be ascending (thr[%d]=%g > thr[%d]=%g)", fn, t - 1,
+                   (double)thr_host[t - 1], t, (double)thr_host[t]);
+    }
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    GL_REQUIRE(bank_dev && query_dev && counts_dev, "%s: NULL device pointer", fn);
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(counts_dev) & 7) == 0, "%s: the counters must be 8-byte aligned", fn);
+    const int64_t q_tiles = gl_ceil_div(nq, TQ), n_tiles = gl_ceil_div(n_rows, TN);
+    GL_REQUIRE(q_tiles * n_tiles < (1ll << 31), "%s: grid too large", fn);
+    if (thr_host[n_thr - 1] < 0.0f) return GL_OK;        // D32 >= +0: no pair lies within a negative radius
+    int skip = 0;
+    while (thr_host[skip] < 0.0f) ++skip;                 // ... so those columns stay as they are
+    f32_sink<1> sink;
+    sink.a.n = n_thr - skip;
+    sink.a.col0 = skip;
+    sink.a.pitch = n_thr;
+    for (int t = 0; t < GL_COUNT_MAX_T; ++t) sink.a.thr[t] = thr_host[skip + (t < sink.a.n ? t : sink.a.n - 1)];
+    sink.counts = reinterpret_cast<unsigned long long *>(counts_dev);
+    hipLaunchKernelGGL(l2_pairs_f32_kernel<1>, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev, n_rows, query_dev, nq, d,
+                       (int)q_tiles, sink);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_l2_topk_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, int64_t index_base, const float *query_dev, int64_t nq, int64_t d, int k,
+                   uint64_t *topk_keys_dev)
+{
+    static const char *fn = "gl_l2_topk_f32";
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && n_rows >= 0 && nq >= 0 && d > 0, "%s: bad sizes", fn);
+    GL_REQUIRE(k >= 1 && k <= GL_TOPK_MAX, "%s: k=%d outside [1, %d]", fn, k, GL_TOPK_MAX);
+    GL_REQUIRE(index_base >= 0 && index_base + n_rows <= 0xFFFFFFFFll, "%s: global index does not fit 32 bits", fn);
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    GL_REQUIRE(bank_dev && query_dev && topk_keys_dev, "%s: NULL device pointer", fn);
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(topk_keys_dev) & 7) == 0, "%s: the key lists must be 8-byte aligned", fn);
+
+    // slices: qs queries x rs bank rows of D32 within the budget, whole tiles (or the whole extent), never below one tile
+    const int64_t budget = (int64_t)gl_topk_workspace_budget(ctx);
+    int64_t qs = budget / (TQ * 4) / TQ * TQ;
+    if (qs < TQ) qs = TQ;
+    if (qs > GL_TOPK_MAX_QUERY_SLICE) qs = GL_TOPK_MAX_QUERY_SLICE;
+    if (qs > nq) qs = nq;
+    int64_t rs = budget / (qs * 4) / TN * TN;
+    if (rs < TN) rs = TN;
+    if (rs > n_rows) rs = n_rows;
+    GL_REQUIRE(gl_ceil_div(qs, TQ) * gl_ceil_div(rs, TN) < (1ll << 31), "%s: grid too large", fn);
+    const int64_t groups = gl_ceil_div(rs, 4);
+    const int64_t segs = gl_topk_segments(qs, rs);
+
+    gl_scratch_guard mem{ctx};
+    int rc = gl_malloc(ctx, (size_t)(groups * qs * 16), &mem.p[0]);
+    if (rc != GL_OK) return rc;
+    rc = gl_malloc(ctx, (size_t)(segs * qs * k * 8), &mem.p[1]);
+    if (rc != GL_OK) return rc;
+    f32_sink<2> sink;
+    sink.pieces = static_cast<unsigned *>(mem.p[0]);
+    unsigned long long *lists = static_cast<unsigned long long *>(mem.p[1]);
+    unsigned long long *dst = reinterpret_cast<unsigned long long *>(topk_keys_dev);
+
+    for (int64_t q_lo = 0; q_lo < nq; q_lo += qs) {
+        const int64_t nqs = nq - q_lo < qs ? nq - q_lo : qs;
+        for (int64_t r_lo = 0; r_lo < n_rows; r_lo += rs) {
+            const int64_t nrs = n_rows - r_lo < rs ? n_rows - r_lo : rs;
+            const int64_t q_tiles = gl_ceil_div(nqs, TQ), n_tiles = gl_ceil_div(nrs, TN);
+            hipLaunchKernelGGL(l2_pairs_f32_kernel<2>, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev + r_lo * d, nrs,
+                               query_dev + q_lo * d, nqs, d, (int)q_tiles, sink);
+            GL_LAUNCH_CHECK();
+            rc = gl_topk_select_merge(ctx, mem.p[0], 4, nrs, nqs, k, 32, index_base + r_lo, dst + q_lo * k, lists, segs);
+            if (rc != GL_OK) return rc;
+        }
+    }
     return GL_OK;
 }
 

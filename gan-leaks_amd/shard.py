@@ -212,6 +212,23 @@ def allreduce_min_keys_host(keys_host, group=None):
     return t.numpy().view(np.uint64)
 
 
+def _group_layout(queries, bank, batch_size, float_path):
+    """(float_path, _layout) for the ranks of a DeviceGroup call: every rank must take the same arithmetic path, so the host decides once,
+    from the rows that take part -- (None, None): both sides on one lattice, the exact-integer path as without the keyword;
+    ('exact', 'f32'): fp32 rows on every rank.  A generated bank is 8-bit codes."""
+    from ._lib import DeviceArray
+    from .attack import _check_rows_float_path, host_rows_kind
+    if _check_rows_float_path(float_path) is None:
+        return None, None
+    kb = "u8"
+    if bank is not None:
+        rows = bank.numpy() if isinstance(bank, DeviceArray) else bank
+        kb = host_rows_kind(rows[:(len(rows) // int(batch_size)) * int(batch_size)])
+    if kb != "f32" and host_rows_kind(queries) == kb:
+        return None, None
+    return "exact", "f32"
+
+
 class DeviceGroup:
     """The sharded attack inside ONE process: a context per GPU, a host thread per context and call, the packed keys min-reduced by RCCL
     between the contexts (`gl_comm_init_all` + `gl_allreduce_min_keys`, each on its own stream).  When RCCL cannot form the
@@ -279,17 +296,20 @@ class DeviceGroup:
         return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call)
 
     def ball_counts(self, queries, make_generator=None, z=None, bank=None, eps=None, batch_size=64, weights=None, distance="l2", make_lpips=None,
-                    **generate_kwargs):
+                    float_path=None, **generate_kwargs):
         """attack.ball_counts over the group's contexts: rank r counts over rows [bounds[r], bounds[r+1]) of the bank (handed over or
         generated, as in attack_on_devices), the [Q, T] counters are summed across the ranks (allreduce_sum_counts, or on the host where RCCL
         cannot form the communicator).  int64 [Q, T], identical to the single-device result.  The queries are prepared once per context and
-        shared with attack() under the same distance on the same array.  distance, make_lpips: as in attack_on_devices."""
-        from .attack import _check_eps, ball_counts
+        shared with attack() under the same distance on the same array.  distance, make_lpips: as in attack_on_devices.  float_path: as
+        in attack.ball_counts; with 'exact' the host settles one layout for all ranks from the rows that take part."""
+        from .attack import _check_eps, _check_rows_float_path, ball_counts
+        _check_rows_float_path(float_path)
         if distance not in ("l2", "l2-lpips"):
             raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
         if eps is None:
             raise ValueError("needs eps")
         eps = _check_eps(eps)
+        fpath, layout = _group_layout(queries, bank, batch_size, float_path) if distance == "l2" else (None, None)
 
         def reduce_fn_for(rank, ctx, comms, host):
             if comms is not None:
@@ -299,22 +319,26 @@ class DeviceGroup:
             return lambda counts: ctx.to_device(host.merge(rank, counts.numpy(), op="sum"))
 
         def call(prepared, shard, ctx, reduce_fn, model, lo):
-            return ball_counts(prepared, shard, eps, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, index_base=lo, distance=distance, lpips=model)
+            return ball_counts(prepared, shard, eps, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, index_base=lo, distance=distance, lpips=model,
+                               float_path=fpath, _layout=layout)
 
         return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
 
     def nearest_neighbours(self, queries, make_generator=None, z=None, bank=None, k=None, batch_size=64, weights=None, distance="l2-lpips",
-                           make_lpips=None, **generate_kwargs):
+                           make_lpips=None, float_path=None, **generate_kwargs):
         """attack.nearest_neighbours over the group's contexts: rank r keeps the k nearest rows of [bounds[r], bounds[r+1]) of the bank
         (handed over or generated, as in attack_on_devices), the [Q, k] key lists are merged across the ranks (allreduce_topk_keys, or on the
         host where RCCL cannot form the communicator).  (dist float32 [Q, k], idx int64 [Q, k]), identical to the single-device result.
-        distance 'l2-lpips' (default) or 'l2'; make_lpips as in attack_on_devices."""
-        from .attack import _check_k, nearest_neighbours
+        distance 'l2-lpips' (default) or 'l2'; make_lpips as in attack_on_devices.  float_path (distance='l2'): as in
+        attack.nearest_neighbours; with 'exact' the host settles one layout for all ranks from the rows that take part."""
+        from .attack import _check_k, _check_rows_float_path, nearest_neighbours
+        _check_rows_float_path(float_path)
         if distance not in ("l2", "l2-lpips"):
             raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
         if k is None:
             raise ValueError("needs k")
         k = _check_k(k)
+        fpath, layout = _group_layout(queries, bank, batch_size, float_path) if distance == "l2" else (None, None)
 
         def validate(n_eff):
             if k > n_eff:
@@ -328,7 +352,8 @@ class DeviceGroup:
             return lambda keys: ctx.to_device(host.merge(rank, keys.numpy(), k))
 
         def call(prepared, shard, ctx, reduce_fn, model, lo):
-            return nearest_neighbours(prepared, shard, k, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, lpips=model, index_base=lo)
+            return nearest_neighbours(prepared, shard, k, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, lpips=model, index_base=lo,
+                                      float_path=fpath, _layout=layout)
 
         return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call)
 
@@ -463,16 +488,20 @@ def attack_on_devices(queries, make_generator=None, z=None, devices=None, distan
 
 
 def ball_counts_on_devices(queries, make_generator=None, z=None, devices=None, eps=None, batch_size=64, weights=None, bank=None, distance="l2",
-                           make_lpips=None, **generate_kwargs):
-    """attack.ball_counts sharded over a DeviceGroup built for the call (arguments as attack_on_devices): int64 [Q, T], identical to the
-    single-device counts."""
+                           make_lpips=None, float_path=None, **generate_kwargs):
+    """attack.ball_counts sharded over a DeviceGroup built for the call (arguments as attack_on_devices; float_path as attack.ball_counts):
+    int64 [Q, T], identical to the single-device counts."""
+    from .attack import _check_rows_float_path
+    _check_rows_float_path(float_path)       # before any Context
     with DeviceGroup(devices) as group:
-        return group.ball_counts(queries, make_generator, z, bank, eps, batch_size, weights, distance, make_lpips, **generate_kwargs)
+        return group.ball_counts(queries, make_generator, z, bank, eps, batch_size, weights, distance, make_lpips, float_path, **generate_kwargs)
 
 
 def nearest_neighbours_on_devices(queries, make_generator=None, z=None, devices=None, k=None, batch_size=64, weights=None, bank=None,
-                                  distance="l2-lpips", make_lpips=None, **generate_kwargs):
-    """attack.nearest_neighbours sharded over a DeviceGroup built for the call (arguments as attack_on_devices):
-    (dist float32 [Q, k], idx int64 [Q, k]), identical to the single-device lists."""
+                                  distance="l2-lpips", make_lpips=None, float_path=None, **generate_kwargs):
+    """attack.nearest_neighbours sharded over a DeviceGroup built for the call (arguments as attack_on_devices; float_path as
+    attack.nearest_neighbours): (dist float32 [Q, k], idx int64 [Q, k]), identical to the single-device lists."""
+    from .attack import _check_rows_float_path
+    _check_rows_float_path(float_path)       # before any Context
     with DeviceGroup(devices) as group:
-        return group.nearest_neighbours(queries, make_generator, z, bank, k, batch_size, weights, distance, make_lpips, **generate_kwargs)
+        return group.nearest_neighbours(queries, make_generator, z, bank, k, batch_size, weights, distance, make_lpips, float_path, **generate_kwargs)

@@ -209,6 +209,19 @@ int gl_l2_rows_u8(gl_ctx *ctx, const uint8_t *x_hat_u8_dev, int64_t b, const uin
 int gl_l2_knn_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, int64_t index_base, const float *query_dev, int64_t nq, int64_t d,
                   uint64_t *keys_dev);
 int gl_keys_unpack_f32(gl_ctx *ctx, const uint64_t *keys_dev, int64_t nq, float *dist_dev, int64_t *idx_dev);
+/* The other two reductions over the same D32(q, n) -- the K loop of gl_l2_knn_f32 with another epilogue, so the value is the same bits and a
+ * function of the two rows alone (no tile, slice, chunk or shard shows in it).  Finite rows; D32 >= +0.
+ * gl_l2_topk_f32: custom_knn (attack_models/fbb.py:73-88) keeping the args.K nearest samples for rows off the lattices.  topk_keys_dev [nq][k]
+ *   as for gl_l2_topk_i8 (gl_topk_init, folds into what the lists hold, every global index at most once), keys float_bits(D32) << 32 |
+ *   (index_base + n): column 0 is gl_l2_knn_f32's key, ties go to the smaller index.  Merge with gl_topk_merge, unpack with
+ *   gl_topk_unpack_f32.  Slices of D32 pieces live in the workspace of gl_topk_set_workspace; synchronises when it returns it.
+ * gl_l2_count_f32: counts[q][t] += #{ n in [0, n_rows) : D32(q, n) <= thr_host[t] }, a float32 compare of mean((y - x)**2)
+ *   (attack_models/utils.py:163); thr_host: n_thr (1..GL_COUNT_MAX_T) radii in HOST memory, ascending, not NaN; a negative radius counts
+ *   nothing, +inf every row.  counts_dev [nq][n_thr] uint64 (gl_counts_init, gl_counts_add across shards).  One kernel, asynchronous. */
+int gl_l2_topk_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, int64_t index_base, const float *query_dev, int64_t nq, int64_t d, int k,
+                   uint64_t *topk_keys_dev);
+int gl_l2_count_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const float *thr_host,
+                    int n_thr, uint64_t *counts_dev);
 /* Loss('l2').forward for fp32 inputs: out[i] = dist(x_hat[i], x_gt[b_gt == 1 ? 0 : i]) */
 int gl_l2_rows_f32(gl_ctx *ctx, const float *x_hat_dev, int64_t b, const float *x_gt_dev, int64_t b_gt, int64_t d, float *out_dev);
 

@@ -87,6 +87,9 @@ SIGNATURES = {
     "gl_l2_count_i8": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
     "gl_l2_count_i8_wide": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
     "gl_counts_add": (_i, [_p, _p, _p, _i64, _i, _i64]),
+    "gl_hist_init": (_i, [_p, _p, _i]),
+    "gl_l2_hist_i8": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _i, _i, _p]),
+    "gl_l2_hist_i8_wide": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _i, _i, _p]),
     "gl_l2_rows_u8": (_i, [_p, _p, _i64, _p, _i64, _i64, _p]),
     "gl_l2_knn_f32": (_i, [_p, _p, _i64, _i64, _p, _i64, _i64, _p]),
     "gl_l2_topk_f32": (_i, [_p, _p, _i64, _i64, _p, _i64, _i64, _i, _p]),
@@ -304,7 +307,7 @@ class Context:
     def event(self):
         return Event(self)
 
-    PROF_TAGS = {"gather_conv": 0, "l2_knn": 1, "convt_rgb": 2, "l2_prepare": 3, "feat_knn": 4, "topk_select": 5, "l2_count": 6, "feat_count": 7}
+    PROF_TAGS = {"gather_conv": 0, "l2_knn": 1, "convt_rgb": 2, "l2_prepare": 3, "feat_knn": 4, "topk_select": 5, "l2_count": 6, "feat_count": 7, "l2_hist": 8}
 
     def prof_enable(self, on=True):
         check(self.lib.gl_prof_enable(self.handle, 1 if on else 0))

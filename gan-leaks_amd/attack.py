@@ -612,6 +612,201 @@ def _ball_counts_l2(queries, bank, e32, batch_size, ctx, reduce_fn, chunk_bytes,
     return out
 
 
+GL_HIST_MAX_BINS = 2048
+_RADIX_BITS = 11                             # 2^11 = GL_HIST_MAX_BINS bins per level of select_ranks
+
+
+def new_hist(ctx, n_bins):
+    """zeroed histogram DeviceArray [n_bins, 1] uint64 (gl_hist_init); the shape shard.allreduce_sum_counts sums"""
+    hist = ctx.empty((int(n_bins), 1), np.uint64)
+    check(ctx.lib.gl_hist_init(ctx.handle, _p(hist.ptr), int(n_bins)))
+    return hist
+
+
+def pair_histogram(bank, queries, lo, shift, n_bins, n_rows=None, hist=None):
+    """launch the histogram kernel: hist DeviceArray [n_bins, 1] (uint64), hist[b] += #{ q, n < n_rows : lo <= S(q, n) and
+    (S(q, n) - lo) >> shift == b } over ALL pairs of the query rows and bank rows [0, n_rows); pairs outside the window are not counted.
+    `hist` from an earlier call (another chunk of the bank) is added to.  Exact-integer banks only ('u8' / 'int', either norm width), the
+    refusals of count_balls.  Returns (hist, the prepared query Bank, the bank's kind), as count_balls does.  Asynchronous."""
+    ctx = bank.ctx
+    if bank.kind not in ("u8", "int"):
+        raise _OffLattice("pair histograms need rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
+    if not isinstance(queries, Bank):
+        queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind=bank.kind, norms64=bank.wide)
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    if queries.kind != bank.kind:
+        raise _OffLattice("pair histograms need queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" %
+                          (queries.kind, bank.kind))
+    if queries.wide != bank.wide:
+        raise ValueError("the query Bank has %s row norms, the bank %s: prepare both with the same norms64" %
+                         ("int64" if queries.wide else "int32", "int64" if bank.wide else "int32"))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if hist is None:
+        hist = new_hist(ctx, n_bins)
+    fn = ctx.lib.gl_l2_hist_i8_wide if bank.wide else ctx.lib.gl_l2_hist_i8
+    check(fn(ctx.handle, _p(bank.rows_i8.ptr), _p(bank.norms.ptr), n_rows, _p(queries.rows_i8.ptr), _p(queries.norms.ptr), queries.n, bank.d,
+             int(lo), int(shift), int(n_bins), _p(hist.ptr)))
+    return hist, queries, bank.kind
+
+
+def select_ranks(hist_fn, ranks, s_max):
+    """the exact values at the given ranks of a multiset M of integers in [0, s_max], by radix-select over histograms.  Host only.
+
+    hist_fn(lo, shift, n_bins) -> int64 [n_bins]: #{ S in M : lo <= S and (S - lo) >> shift == b } per bin b (one pass over the pairs:
+              pair_histogram, summed over chunks and shards).
+    ranks   : 0-based ranks into sorted(M), any order, repeats allowed -- or a callable(|M|) -> such ranks, for callers that learn |M|
+              from the first histogram, whose window covers every S.
+    The first level covers [0, 2^bitlen(s_max)) with up to 2048 bins of the top 11 bits; the bin of each rank follows from the cumulative
+    sum, and each further level zooms into such a bin with the next 11 bits (11, 11, 10 for S < 2^32: 3 levels; 4 up to 2^40), until
+    shift == 0, where a bin is one value -- the only stopping rule: bins alone cannot show that a window holds a single distinct value, so
+    every rank takes all its levels.  A bin that holds several of the ranks is visited once.
+    returns (S int64 [len(ranks)], passes = calls of hist_fn)."""
+    bits = max(int(s_max).bit_length(), 1)
+    passes = 0
+    out = None
+    # (lo, shift of the window's bins, bits the window spans, [(position in `out`, rank counted from the window's first element)])
+    work = [(0, max(bits - _RADIX_BITS, 0), bits, None)]
+    while work:
+        lo, shift, span, wanted = work.pop()
+        n_bins = 1 << (span - shift)
+        hist = np.asarray(hist_fn(lo, shift, n_bins), np.int64).reshape(-1)
+        passes += 1
+        if hist.shape != (n_bins,):
+            raise ValueError("hist_fn returned %d bins for a window of %d" % (hist.size, n_bins))
+        cum = np.cumsum(hist)
+        if wanted is None:                   # the first level: its window holds all of M
+            total = int(cum[-1])
+            rk = ranks(total) if callable(ranks) else ranks
+            rk = [int(r) for r in np.atleast_1d(np.asarray(rk, dtype=object))]
+            if any(not 0 <= r < total for r in rk):
+                raise ValueError("ranks must lie in [0, %d), got %r" % (total, rk))
+            out = np.empty(len(rk), np.int64)
+            wanted = list(enumerate(rk))
+        by_bin = {}
+        for pos, r in wanted:
+            b = int(np.searchsorted(cum, r, side="right"))
+            if b >= n_bins:
+                raise ValueError("the histogram of window (lo=%d, shift=%d) holds %d elements, rank %d is beyond it" % (lo, shift, int(cum[-1]), r))
+            by_bin.setdefault(b, []).append((pos, r - (int(cum[b - 1]) if b else 0)))
+        for b, inside in by_bin.items():
+            first = lo + (b << shift)
+            if shift == 0:
+                for pos, _ in inside:
+                    out[pos] = first
+            else:
+                work.append((first, max(shift - _RADIX_BITS, 0), shift, inside))
+    return out, passes
+
+
+def _check_quantiles(quantiles):
+    """quantiles (a number or a sequence of 1..GL_COUNT_MAX_T numbers in [0, 1]) -> list of Python floats; needs no GPU"""
+    v = np.atleast_1d(np.asarray(quantiles, np.float64))
+    if v.ndim != 1:
+        raise ValueError("quantiles must be a number or a flat sequence of numbers, got shape %r" % (v.shape,))
+    if not 1 <= len(v) <= GL_COUNT_MAX_T:
+        raise ValueError("quantiles must hold 1..%d values, got %d" % (GL_COUNT_MAX_T, len(v)))
+    if np.any(np.isnan(v)):
+        raise ValueError("quantiles hold NaN")
+    if np.any((v < 0.0) | (v > 1.0)):
+        raise ValueError("quantiles must lie in [0, 1], got %r" % (v.tolist(),))
+    return [float(x) for x in v]
+
+
+def quantile_ranks(quantiles, pairs):
+    """the 0-based rank floor(v * (pairs - 1)) of every quantile v, evaluated exactly (the float v as a fraction; no float64 product, which
+    rounds once pairs exceeds 2^53 / v's denominator).  Host only."""
+    from fractions import Fraction
+    return [int(Fraction(v) * (int(pairs) - 1)) for v in _check_quantiles(quantiles)]
+
+
+def distance_quantiles(queries, bank, quantiles, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0, distance="l2"):
+    """exact quantiles of ALL Q x n_eff query-sample distances: the percentile heuristic for the radius of the Monte-Carlo attack
+    (Hilprecht et al., PoPETs 2019: a small quantile, typically 0.001, of all d(x_i, g_j)).
+
+    M = { S(q, n) : q < Q, n < n_eff } with the exact S and the n_eff of attack() / ball_counts(); for a quantile v the rank is
+    r = floor(v * (|M| - 1)) (exactly, quantile_ranks) and the answer S_v = sorted(M)[r], an attained S.
+    quantiles: a float or 1..16 floats in [0, 1], any order, repeats allowed.
+    returns (eps float32 [T], S int64 [T], pairs = |M|): eps[t] = dist32(S[t]), the float32 attack() reports for that S, so
+              ball_counts(eps=eps[t]).sum() >= r + 1 and ball_counts(eps=nextafter(eps[t], -inf)).sum() <= r; v = 0 gives attack()'s smallest
+              distance, v = 1 the largest one present.
+    queries, bank, batch_size, ctx, chunk_bytes, index_base: as ball_counts(distance='l2'): images, a prepared `Bank`, a `GeneratedBank`,
+              integer tables, either norm width; a bank beyond `chunk_bytes` is streamed.  Every level of the radix-select (select_ranks: 3
+              for S < 2^32, 4 for larger images, times the distinct bins the ranks fall into) is one pass over the bank
+              (pair_histogram), so a streamed or generated bank is prepared / generated once per pass.
+    reduce_fn: optional callable(hist DeviceArray [n_bins, 1] uint64) -> DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts): the
+              histogram of every level is summed before the bin is chosen, so every shard takes the same decisions; |M| is read from the
+              summed first-level histogram.
+    Exact-integer L2 only: rows off both lattices, LPIPS feature rows and distance='l2-lpips' raise NotImplementedError."""
+    q = _check_quantiles(quantiles)          # before any Context: these checks run without a GPU
+    unsupported = "distance quantiles are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    if distance == "l2-lpips":
+        raise NotImplementedError(unsupported + "distance='l2-lpips' is not (its float32 distance bits would radix-select the same way)")
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError(unsupported + "got LPIPS feature rows")
+    prepared = isinstance(bank, Bank)
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx = bank.ctx
+        base = bank.index_base
+    else:
+        ctx = ctx or Context.get()
+        base = int(index_base)
+    shard = reduce_fn is not None or base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    if prepared and bank.kind == "f32":
+        raise _OffLattice(unsupported + "the bank is off both lattices")
+    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
+    if fq.kind == "f32":
+        raise _OffLattice(unsupported + "the queries are off both lattices")
+    if not prepared:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
+
+    def rows(lo, hi):
+        if generated:
+            return bank.rows(lo, hi)
+        if isinstance(bank, DeviceArray):
+            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+        return bank[lo:hi]
+
+    def one_pass(lo, shift, n_bins):
+        hist = new_hist(ctx, n_bins)                         # fresh bins per pass
+        if prepared:
+            pair_histogram(bank, fq, lo, shift, n_bins, n_rows, hist)
+        else:
+            for r0 in range(0, n_rows, step):
+                r1 = min(r0 + step, n_rows)
+                chunk = rows(r0, r1)
+                if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
+                    raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
+                try:
+                    b = Bank.from_images(chunk, ctx, index_base=base + r0, force_kind=fq.kind, norms64=fq.wide)
+                except ValueError as e:
+                    raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
+                pair_histogram(b, fq, lo, shift, n_bins, hist=hist)
+                ctx.sync()
+        if reduce_fn is not None:            # (a shard without rows takes part with zeros)
+            hist = reduce_fn(hist)
+        return hist.numpy().reshape(-1)[:n_bins].astype(np.int64)
+
+    pairs = []
+
+    def ranks(total):
+        if total == 0:
+            raise ValueError("no query-sample pair takes part: the multiset of distances is empty")
+        pairs.append(total)
+        return quantile_ranks(q, total)
+
+    S, _ = select_ranks(one_pass, ranks, 65025 * fq.d)
+    eps = np.asarray([_dist32(int(v), fq.d, fq.kind) for v in S], np.float32)
+    return eps, S, pairs[0]
+
+
 def host_rows_kind(rows):
     """the Bank kind Bank.from_images would give a HOST array (numpy / CPU torch), by numpy alone: 'u8' (8-bit codes, or floats on the image
     lattice fl32(2*(u/255.)-1)), 'int' (floats equal to an integer 0..255) or 'f32'.  For callers that must settle the layout of a sharded

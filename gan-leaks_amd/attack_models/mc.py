@@ -7,7 +7,7 @@ Score of a query x:  f_eps(x) = #{ i < n_eff : dist(x, g_i) <= eps } / n_eff  ov
 full-black-box attack, n_eff = (N // BATCH_SIZE) * BATCH_SIZE (fbb.py:77).  All eps are counted in ONE pass over the bank
 (ganleaks_amd.attack.ball_counts).
 
-    python -m ganleaks_amd.attack_models.mc --syn_data_path ... --pos_data_dir ... --neg_data_dir ... [--eps e1,e2,... | --eps_quantile q1,q2,...]
+    python -m ganleaks_amd.attack_models.mc --syn_data_path ... --pos_data_dir ... --neg_data_dir ... [--eps e1,e2,... | --eps_quantile q1,q2,... | --eps_pair_quantile q1,q2,...]
                                             [--distance {l2,l2-lpips}]
 
 --syn_data_path, --pos_data_dir, --neg_data_dir: a folder of PNG files (8-bit codes), or a file of floats (bank_io.load_rows): an .npz with
@@ -21,6 +21,9 @@ full-black-box attack, n_eff = (N // BATCH_SIZE) * BATCH_SIZE (fbb.py:77).  All 
 --eps           the radii themselves (up to 16)
 --eps_quantile  (default 0.5: Hilprecht's median heuristic) eps = that quantile (method 'lower': an attained distance) of the pooled
                 positive + negative nearest-sample distances, which one attack() under the same distance over the same prepared rows gives
+--eps_pair_quantile  Hilprecht's percentile heuristic: eps = that quantile (typically 0.001) of ALL query-sample distances d(x_i, g_j), exactly
+                (ganleaks_amd.attack.distance_quantiles: an attained distance, rank floor(q * (pairs - 1))); --distance l2 on the exact-integer
+                path only
 Files under ./mc_attack/<exp_name>/:
     eps.npy float32 [T]; {pos,neg}_count.npy int64 [n, T]; {pos,neg}_mc.npy float64 [n, T] = count / n_eff; params.txt;
     {pos,neg}_loss.npy float64 [n, 1] = -mc[:, 0], so `eval_roc --attack_type fbb -ldir mc_attack/<exp_name>` scores the first eps.
@@ -33,9 +36,13 @@ import warnings
 
 import numpy as np
 
-from ..attack import GL_COUNT_MAX_T, Bank, _budget_bytes, attack, ball_counts, prepare_queries
+from ..attack import GL_COUNT_MAX_T, Bank, _budget_bytes, attack, ball_counts, distance_quantiles, prepare_queries
 from .fbb import shard_devices, update_args  # noqa: F401  (update_args: the YAML overlay of the command line)
 from .utils import check_folder, save_files
+
+
+# options added after params.txt got its form: an unused one leaves the file as it was before the option existed
+LATER_OPTIONS = ("eps_pair_quantile",)
 
 
 def parse_arguments(argv=None):
@@ -55,6 +62,9 @@ def parse_arguments(argv=None):
                         help="distance the balls are measured in: 'l2', or 'l2-lpips' = 0.2 * LPIPS + L2 (the reference's fbb distance)")
     parser.add_argument('--eps_quantile', type=str, default=None,
                         help='comma-separated quantiles of the pooled nearest-sample distances to use as radii (default 0.5, the median heuristic)')
+    parser.add_argument('--eps_pair_quantile', type=str, default=None,
+                        help='comma-separated quantiles of ALL query-sample distances to use as radii (the percentile heuristic; try 0.001); '
+                             '--distance l2 only')
     return parser.parse_args(argv)
 
 
@@ -71,7 +81,19 @@ def _floats(text, what):
 
 
 def radii_request(args):
-    """('eps', values) or ('quantile', values) from the command line; refused before any file is read"""
+    """('eps', values), ('quantile', values) or ('pair_quantile', values) from the command line; refused before any file is read"""
+    pair = getattr(args, "eps_pair_quantile", None)
+    if pair is not None:
+        if getattr(args, "eps", None) is not None or getattr(args, "eps_quantile", None) is not None:
+            raise SystemExit("--eps, --eps_quantile and --eps_pair_quantile exclude each other")
+        if getattr(args, "distance", "l2") != "l2":
+            raise SystemExit("--eps_pair_quantile is built for --distance l2 (exact-integer L2), not %r" % (getattr(args, "distance", None),))
+        values = _floats(pair, "--eps_pair_quantile")
+        if any(not 0.0 <= v <= 1.0 for v in values):     # (NaN fails both comparisons)
+            raise SystemExit("--eps_pair_quantile needs values in [0, 1], got %r" % (values,))
+        if not 1 <= len(values) <= GL_COUNT_MAX_T:
+            raise SystemExit("1..%d radii per run, got %d" % (GL_COUNT_MAX_T, len(values)))
+        return "pair_quantile", values
     if getattr(args, "eps", None) is not None and getattr(args, "eps_quantile", None) is not None:
         raise SystemExit("--eps and --eps_quantile exclude each other")
     if getattr(args, "eps", None) is not None:
@@ -94,7 +116,7 @@ def main(args):
         raise SystemExit("--distance must be l2 or l2-lpips, got %r" % (distance,))
     assert os.path.exists(args.syn_data_path)
     save_dir = check_folder(os.path.join(os.getcwd(), 'mc_attack', args.exp_name))
-    lines = ["%s:%s" % (key, value) for key, value in vars(args).items()]
+    lines = ["%s:%s" % (key, value) for key, value in vars(args).items() if not (key in LATER_OPTIONS and value is None)]
     with open(os.path.join(save_dir, 'params.txt'), 'w') as handle:
         handle.write("".join(line + "\n" for line in lines))
     print("\n".join(lines))
@@ -145,12 +167,16 @@ def main(args):
             # float_path='exact' spelt out: the radius read from the nearest distances must be an attained D32 of the counting pass
             nearest = lambda: attack(queries, bank, distance="l2", batch_size=args.BATCH_SIZE, float_path="exact")[0]   # noqa: E731
             count = lambda eps: ball_counts(queries, bank, eps, batch_size=args.BATCH_SIZE, float_path="exact")         # noqa: E731
+            pair_quantiles = lambda: distance_quantiles(queries, bank, values, batch_size=args.BATCH_SIZE)[0]           # noqa: E731
         else:
             nearest = lambda: group.attack(both, bank=syn_imgs, distance="l2", batch_size=args.BATCH_SIZE)[0]      # noqa: E731
             count = lambda eps: group.ball_counts(both, bank=syn_imgs, eps=eps, batch_size=args.BATCH_SIZE, float_path="exact")   # noqa: E731
+            pair_quantiles = lambda: group.distance_quantiles(both, bank=syn_imgs, quantiles=values, batch_size=args.BATCH_SIZE)[0]   # noqa: E731
         if mode == "eps":
             with np.errstate(over="ignore"):
                 eps = np.asarray(values, np.float64).astype(np.float32)
+        elif mode == "pair_quantile":
+            eps = np.asarray(pair_quantiles(), np.float32)
         else:
             top1 = np.asarray(nearest(), np.float32)
             eps = np.asarray([np.quantile(top1, v, method="lower") for v in values], np.float32)

@@ -324,6 +324,43 @@ class DeviceGroup:
 
         return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
 
+    def distance_quantiles(self, queries, make_generator=None, z=None, bank=None, quantiles=None, batch_size=64, weights=None, **generate_kwargs):
+        """attack.distance_quantiles over the group's contexts: rank r bins the pairs of rows [bounds[r], bounds[r+1]) of the bank (handed
+        over or generated, as in attack_on_devices); the histogram of every level of the radix-select is summed across the ranks
+        (allreduce_sum_counts, or on the host where RCCL cannot form the communicator: one rendezvous per level), so every rank zooms into
+        the same bins.  (eps float32 [T], S int64 [T], pairs), identical to the single-device result.  The queries are prepared once per
+        context and shared with attack() / ball_counts() under 'l2' on the same array.  Rows off both lattices (or on different ones) raise
+        NotImplementedError on the host, before any context works; the group stays usable.  (Classifying a bank handed over as a
+        DeviceArray reads all of it back to the host once per call, as _run does anyway to shard it.)"""
+        from ._lib import DeviceArray
+        from .attack import _OffLattice, _check_quantiles, distance_quantiles, host_rows_kind
+        if quantiles is None:
+            raise ValueError("needs quantiles")
+        quantiles = _check_quantiles(quantiles)
+        # an argument error, settled on the host before any rank starts (a refusal inside a rank would cost the group its communicators):
+        # both sides on one lattice, as attack.distance_quantiles demands.  A generated bank is 8-bit codes.
+        if getattr(queries, "kind", None) not in ("feat", "u8", "int", "f32"):           # (prepared rows: _run's TypeError)
+            kb = "u8"
+            if bank is not None:
+                rows = bank.numpy() if isinstance(bank, DeviceArray) else bank
+                kb = host_rows_kind(rows[:(len(rows) // int(batch_size)) * int(batch_size)])
+            kq = host_rows_kind(queries)
+            if kb == "f32" or kq != kb:
+                raise _OffLattice("distance quantiles are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+                                  "got %r queries, %r bank rows" % (kq, kb))
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            if comms is not None:
+                return lambda hist: allreduce_sum_counts(hist, comm=comms[rank])
+            if self.world == 1:
+                return None
+            return lambda hist: ctx.to_device(host.merge(rank, hist.numpy(), op="sum"))
+
+        def call(prepared, shard, ctx, reduce_fn, model, lo):
+            return distance_quantiles(prepared, shard, quantiles, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, index_base=lo)
+
+        return self._run(queries, make_generator, z, bank, "l2", batch_size, None, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
+
     def nearest_neighbours(self, queries, make_generator=None, z=None, bank=None, k=None, batch_size=64, weights=None, distance="l2-lpips",
                            make_lpips=None, float_path=None, **generate_kwargs):
         """attack.nearest_neighbours over the group's contexts: rank r keeps the k nearest rows of [bounds[r], bounds[r+1]) of the bank
@@ -495,6 +532,18 @@ def ball_counts_on_devices(queries, make_generator=None, z=None, devices=None, e
     _check_rows_float_path(float_path)       # before any Context
     with DeviceGroup(devices) as group:
         return group.ball_counts(queries, make_generator, z, bank, eps, batch_size, weights, distance, make_lpips, float_path, **generate_kwargs)
+
+
+def distance_quantiles_on_devices(queries, make_generator=None, z=None, devices=None, quantiles=None, batch_size=64, weights=None, bank=None,
+                                  **generate_kwargs):
+    """attack.distance_quantiles sharded over a DeviceGroup built for the call (arguments as attack_on_devices):
+    (eps float32 [T], S int64 [T], pairs), identical to the single-device result."""
+    from .attack import _check_quantiles
+    if quantiles is None:
+        raise ValueError("needs quantiles")
+    _check_quantiles(quantiles)              # before any Context
+    with DeviceGroup(devices) as group:
+        return group.distance_quantiles(queries, make_generator, z, bank, quantiles, batch_size, weights, **generate_kwargs)
 
 
 def nearest_neighbours_on_devices(queries, make_generator=None, z=None, devices=None, k=None, batch_size=64, weights=None, bank=None,

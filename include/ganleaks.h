@@ -91,6 +91,7 @@ int gl_event_elapsed_ms(void *start, void *stop, float *out_ms);   /* synchronis
 #define GL_PROF_TOPK_SELECT 5   /* top-K: selection over the stored S values + list merge (the pairwise kernel itself reports as GL_PROF_L2_KNN) */
 #define GL_PROF_L2_COUNT 6      /* int8-MFMA pairwise L2 + epsilon-ball counts (gl_l2_count_i8*) */
 #define GL_PROF_FEAT_COUNT 7    /* fp16-MFMA pairwise l2-lpips distance + epsilon-ball counts / stored matrix (gl_feat_count*, gl_feat_pair_dist*) */
+#define GL_PROF_L2_HIST 8       /* int8-MFMA pairwise L2 + histogram of all pair distances (gl_l2_hist_i8*) */
 int gl_prof_enable(gl_ctx *ctx, int on);
 int gl_prof_read(gl_ctx *ctx, int tag, double *out_total_ms, int64_t *out_launches);
 int gl_prof_reset(gl_ctx *ctx);
@@ -196,6 +197,27 @@ int gl_l2_count_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *b
 /* dst[q][t] += sum over l < n_lists of src[l][q][t]; src_dev is [n_lists][nq][n_thr] (e.g. what gl_allgather_rows delivers from the ranks of a
  * sharded bank): the cross-shard sum, the counterpart of gl_topk_merge. */
 int gl_counts_add(gl_ctx *ctx, uint64_t *dst_dev, const uint64_t *src_dev, int64_t nq, int n_thr, int64_t n_lists);
+
+/* ---- histogram of ALL pair distances under the same exact S: the primitive under an exact quantile of the nq x n_rows distances (the
+ * percentile heuristic for the radius of the Monte-Carlo attack, Hilprecht et al., PoPETs 2019: a small quantile of all d(x_i, g_j)).
+ * For a window (lo >= 0, 0 <= shift <= 40, 1 <= n_bins <= GL_HIST_MAX_BINS):
+ *     hist[b] += #{ q < nq, n < n_rows : lo <= S(q, n) and (S(q, n) - lo) >> shift == b },  b < n_bins;
+ * pairs outside the window are not counted.  hist_dev is [n_bins] uint64; the adds are integer adds of an exact S, so the histogram is a
+ * function of the multiset of pair distances alone: it does not depend on tile, chunking or sharding.  A host radix-select (zoom into the
+ * bin that holds the rank: attack.select_ranks) finds the exact S at any rank in 3 passes for S < 2^32, 4 for the wide form. */
+#define GL_HIST_MAX_BINS 2048
+/* every bin = 0 */
+int gl_hist_init(gl_ctx *ctx, uint64_t *hist_dev, int n_bins);
+/* Accumulates, so a streamed bank is binned chunk by chunk into one histogram; binning the same rows twice counts them twice.  Rows, norms and
+ * their checks as gl_l2_count_i8 (16-byte aligned prepared rows, d <= gl_l2_max_d(0)); hist_dev 8-byte aligned; n_rows == 0 or nq == 0 is
+ * GL_OK and touches nothing.  Shards are summed with gl_counts_add(dst, src, nq = n_bins, n_thr = 1, n_lists).  One kernel (the pair loop of
+ * gl_l2_count_i8 with a binning epilogue), no workspace: no pairwise value is written to memory.  Asynchronous on the context's stream.
+ * Reports as GL_PROF_L2_HIST. */
+int gl_l2_hist_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
+                  const int32_t *query_norm_dev, int64_t nq, int64_t d, int64_t lo, int shift, int n_bins, uint64_t *hist_dev);
+/* the same for rows prepared by gl_l2_prepare_wide (int64 norms, d <= gl_l2_max_d(1)); equal to gl_l2_hist_i8 wherever both apply */
+int gl_l2_hist_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
+                       const int64_t *query_norm_dev, int64_t nq, int64_t d, int64_t lo, int shift, int n_bins, uint64_t *hist_dev);
 
 /* out[i] = fl32(S(x_hat[i], x_gt[b_gt == 1 ? 0 : i]) * 4/(255^2 d)), i < b: the per-sample loss vector
  * Loss('l2').forward(x_hat, x_gt) returns (attack_models/utils.py:163,169,171-177; x_gt broadcasts

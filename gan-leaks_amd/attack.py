@@ -862,6 +862,29 @@ def count_balls_f32(bank, queries, thr, n_rows=None, counts=None):
     return counts
 
 
+def pair_histogram_f32(bank, queries, lo, shift, n_bins, n_rows=None, hist=None):
+    """pair_histogram for 'f32' Banks: hist DeviceArray [n_bins, 1] (uint64), hist[b] += #{ q, n < n_rows : lo <= bits(D32(q, n)) <= 0x7F800000
+    and (bits(D32(q, n)) - lo) >> shift == b }, bits the uint32 pattern of the float32 distance count_balls_f32 compares (gl_l2_hist_f32: the
+    same K loop with a binning epilogue).  D32 >= +0, so the order of the patterns is the order of the floats; +inf (0x7F800000) is counted,
+    NaN patterns lie outside every window.  lo: 0 .. 2^32 - 1, 0 <= shift <= 31, 1 <= n_bins <= 2048.  `hist` from an earlier call (another
+    chunk of the bank) is added to.  Asynchronous."""
+    ctx = bank.ctx
+    if bank.kind != "f32" or queries.kind != "f32":
+        raise ValueError("pair_histogram_f32 takes 'f32' Banks (Bank.as_f32()), got %r queries, %r bank" % (queries.kind, bank.kind))
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    lo, shift, n_bins = int(lo), int(shift), int(n_bins)
+    if not 0 <= lo <= 0xFFFFFFFF or not 0 <= shift <= 31 or not 1 <= n_bins <= GL_HIST_MAX_BINS:
+        raise ValueError("pair_histogram_f32 needs 0 <= lo < 2^32, 0 <= shift <= 31, 1 <= n_bins <= %d; got lo=%d shift=%d n_bins=%d" %
+                         (GL_HIST_MAX_BINS, lo, shift, n_bins))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if hist is None:
+        hist = new_hist(ctx, n_bins)
+    check(ctx.lib.gl_l2_hist_f32(ctx.handle, _p(bank.rows_f32.ptr), n_rows, _p(queries.rows_f32.ptr), queries.n, bank.d, lo, shift, n_bins,
+                                 _p(hist.ptr)))
+    return hist
+
+
 def _float_rows(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base, k=None, eps=None):
     """nearest_neighbours / ball_counts (distance='l2', float_path='exact') with every row in fp32: 8-bit codes and integer tables decoded,
     floats as they are.  The bank passes through HBM in chunks of at most `chunk_bytes` of fp32 rows (one chunk when it fits), every chunk
@@ -1195,6 +1218,229 @@ def nearest_neighbours(queries, bank, k, distance="l2-lpips", batch_size=64, ctx
     if reduce_fn is not None:
         keys = reduce_fn(keys)
     return unpack_topk_f32(ctx, keys, fq.n, k)
+
+
+F32_BITS_MAX = 0x7F800000                    # the pattern of +inf: the largest uint32 pattern of a float32 distance that is not NaN
+
+
+def _select_float_bits(one_pass, q, ctx, reduce_fn, local_pairs):
+    """select_ranks over the uint32 patterns of float32 distances >= +0.  one_pass(lo, shift, n_bins) -> int64 [n_bins], summed over chunks,
+    query slices and shards.  local_pairs: the Q x n_rows pairs this shard bins; summed across the shards like a histogram, it is what the
+    first level (whose window [0, 2^31) holds every pattern up to +inf) must total -- NaN patterns lie outside every window."""
+    expected = int(local_pairs)
+    if reduce_fn is not None:
+        expected = int(reduce_fn(ctx.to_device(np.asarray([[expected]], np.uint64))).numpy().reshape(-1)[0])
+    pairs = []
+
+    def ranks(total):
+        if total != expected:
+            raise ValueError("%d of the %d query-sample distances are NaN (rows with NaN, or with +inf and -inf, or differences that overflow "
+                             "to inf - inf): they have no rank" % (expected - total, expected))
+        if total == 0:
+            raise ValueError("no query-sample pair takes part: the multiset of distances is empty")
+        pairs.append(total)
+        return quantile_ranks(q, total)
+
+    key, _ = select_ranks(one_pass, ranks, F32_BITS_MAX)
+    return key.astype(np.uint32).view(np.float32), key, pairs[0]
+
+
+def _pair_quantiles_f32(queries, bank, q, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """pair_distance_quantiles(distance='l2', float_path='exact') with every row in fp32: _float_rows' rows, chunks and n_eff, one
+    pair_histogram_f32 pass per level.  A bank of one chunk is uploaded once, a longer one once per pass."""
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError("distance='l2' takes images or tables; got LPIPS feature rows")
+    prepared = isinstance(bank, Bank)
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx = bank.ctx
+        base = bank.index_base
+    else:
+        ctx = ctx or Context.get()
+        base = int(index_base)
+    shard = reduce_fn is not None or base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    fq = queries.as_f32() if isinstance(queries, Bank) else Bank.from_images(queries, ctx, force_kind="f32")
+    resident = None
+    if prepared:
+        resident = bank.as_f32()
+    else:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (4 * fq.d)))
+
+    def rows(lo, hi):
+        if generated:
+            return bank.rows(lo, hi)
+        if isinstance(bank, DeviceArray):
+            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+        return bank[lo:hi]
+
+    if resident is None and 0 < n_rows <= step:
+        resident = Bank.from_images(rows(0, n_rows), ctx, index_base=base, force_kind="f32")
+
+    def one_pass(lo, shift, n_bins):
+        hist = new_hist(ctx, n_bins)                         # fresh bins per pass
+        if resident is not None:
+            pair_histogram_f32(resident, fq, lo, shift, n_bins, n_rows, hist)
+        else:
+            for r0 in range(0, n_rows, step):
+                b = Bank.from_images(rows(r0, min(r0 + step, n_rows)), ctx, index_base=base + r0, force_kind="f32")
+                pair_histogram_f32(b, fq, lo, shift, n_bins, hist=hist)
+                ctx.sync()
+        if reduce_fn is not None:            # (a shard without rows takes part with zeros)
+            hist = reduce_fn(hist)
+        return hist.numpy().reshape(-1)[:n_bins].astype(np.int64)
+
+    return _select_float_bits(one_pass, q, ctx, reduce_fn, fq.n * n_rows)
+
+
+def _pair_quantiles_lpips(queries, bank, q, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
+    """pair_distance_quantiles(distance='l2-lpips'): ball_counts' resident / streamed decision and row preparation, one lpips.feat_hist pass
+    per level.  layout: None, or 'hilo' to put fp16 search rows of both sides in the hi / lo layout from the start (DeviceGroup)."""
+    from . import lpips as _lp
+    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
+    q_feat = getattr(queries, "kind", None) == "feat"
+    if model is None and not (prepared and q_feat):        # prepared rows on both sides need no VGG16
+        model = _lp.default_model()
+    streamed = False
+    if not prepared:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
+            streamed = True
+        else:
+            per_img = _feature_row_bytes(ctx, model, bank)
+            streamed = per_img * n_rows > chunk_bytes or (not q_feat and len(queries) * per_img > chunk_bytes)
+        if not streamed:
+            bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
+
+    if not streamed:
+        if layout == "hilo" and model is not None and model.search_role("bank"):
+            fb = bank if prepared else model.features(bank, index_base=index_base, role="bank", fmt="hilo")
+            fq = queries if q_feat else model.features(queries, role="query", fmt="hilo")
+        else:
+            fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
+        nq = fq.n
+
+        def one_pass(lo, shift, n_bins):
+            hist = _lp.feat_hist(fb, fq, lo, shift, n_bins, n_rows)
+            if reduce_fn is not None:
+                hist = reduce_fn(hist)
+            return hist.numpy().reshape(-1)[:n_bins].astype(np.int64)
+    else:
+        # The stream of _attack_streamed, once per level.  One row layout for ALL levels: 8-bit codes give lattice rows until a query slice
+        # or a bank chunk turns out to be off-lattice floats; then the pass starts over with fresh bins in the hi / lo layout, and every
+        # later pass starts there.  Nothing of an abandoned layout survives in a histogram.
+        def rows(lo, hi):
+            if generated:
+                return bank.rows(lo, hi)
+            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1))) if isinstance(bank, DeviceArray) else bank[lo:hi]
+
+        role_q = None if q_feat else model.search_role("query")
+        nq = queries.n if q_feat else len(queries)
+        if q_feat or nq == 0:
+            slices = [(0, nq)]
+        else:
+            q_step = max(1, int(_query_budget_bytes(chunk_bytes, ctx) // _feature_row_bytes(ctx, model, queries)))
+            slices = [(a, min(a + q_step, nq)) for a in range(0, nq, q_step)]
+        state = {"fmt": "hilo" if (layout == "hilo" and role_q) else None, "fq": None}
+
+        def query_rows(a, b):
+            if q_feat:
+                return queries
+            if len(slices) == 1 and state["fq"] is not None and getattr(state["fq"], "fmt", None) == state["fmt"]:
+                return state["fq"]           # one slice: featurised once per layout, not once per pass
+            fq = model.features(queries[a:b], role=role_q, fmt=state["fmt"] if role_q else None)
+            if len(slices) == 1:
+                state["fq"] = fq
+            return fq
+
+        def stream(lo, shift, n_bins, hist):
+            """False: an off-lattice slice or chunk met lattice rows"""
+            for a, b in slices:
+                try:
+                    fq = query_rows(a, b)
+                except ValueError:
+                    if state["fmt"] != "lattice":
+                        raise
+                    return False
+                if role_q and state["fmt"] is None:
+                    state["fmt"] = fq.fmt    # the first slice settles it: 'lattice' for 8-bit codes, else 'hilo'
+                b_role = "bank" if getattr(fq, "role", None) else None
+                step = max(1, int(chunk_bytes // (fq.K * (2 if fq.role else 4))))
+                if fq.role:
+                    step = _lp.preferred_bank_rows(step, fq.n)
+                buf = None
+                for r0 in range(0, n_rows, step):
+                    try:
+                        buf = model.features(rows(r0, min(r0 + step, n_rows)), index_base=index_base + r0, role=b_role, out=buf,
+                                             fmt=getattr(fq, "fmt", None))
+                    except ValueError:
+                        if q_feat or getattr(fq, "fmt", None) != "lattice":
+                            raise
+                        return False
+                    _lp.feat_hist(buf, fq, lo, shift, n_bins, hist=hist)
+                    ctx.sync()
+            return True
+
+        def one_pass(lo, shift, n_bins):
+            hist = new_hist(ctx, n_bins)
+            if not stream(lo, shift, n_bins, hist):
+                state["fmt"], state["fq"] = "hilo", None
+                hist = new_hist(ctx, n_bins)             # the bins of the abandoned layout are dropped
+                if not stream(lo, shift, n_bins, hist):
+                    raise AssertionError("unreachable")
+            if reduce_fn is not None:
+                hist = reduce_fn(hist)
+            return hist.numpy().reshape(-1)[:n_bins].astype(np.int64)
+
+    return _select_float_bits(one_pass, q, ctx, reduce_fn, nq * n_rows)
+
+
+def pair_distance_quantiles(queries, bank, quantiles, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None,
+                            index_base=0, float_path=None, _layout=None):
+    """exact quantiles of ALL Q x n_eff query-sample distances under any distance and arithmetic path ball_counts() counts on: the percentile
+    heuristic for the radius of the Monte-Carlo attack (Hilprecht et al., PoPETs 2019: a small quantile, typically 0.001, of all
+    d(x_i, g_j)).  distance_quantiles is the older spelling and stays exact-integer only; this function is the way in for 'l2-lpips' -- the
+    distance fbb.main hard-wires, hence the default -- and for rows off both lattices.
+
+    returns (eps float32 [T], key int64 [T], pairs): for a quantile v the rank is r = floor(v * (pairs - 1)) (exactly, quantile_ranks),
+              eps[t] the distance at that rank of the sorted multiset -- an attained distance of ball_counts() under the same arguments, so
+              ball_counts(eps=eps[t]).sum() >= r + 1 and ball_counts(eps=nextafter(eps[t], -inf)).sum() <= r; v = 0 is attack()'s smallest
+              distance, v = 1 the largest one present.  key[t] is the integer the radix-select ran on: the uint32 bit pattern of eps[t] on
+              the float paths, the exact sum of squared differences S on the integer path.  pairs = Q * n_eff.
+    quantiles: a float or 1..16 floats in [0, 1], any order, repeats allowed.
+    distance='l2-lpips': M = { bits(D32(q, n)) } with D32 the float32 distance attack(distance='l2-lpips') minimises, ball_counts counts and
+              pair_distances stores, bit for bit (the search kernel with a binning epilogue, lpips.feat_hist).  D32 >= +0, so the unsigned
+              order of the patterns is the order of the floats, and select_ranks runs on them with s_max = 0x7F800000 (+inf): levels of 11,
+              11 and 9 bits, 3 passes per distinct bin.  Accepts what ball_counts(distance='l2-lpips') accepts: u8 or float images,
+              prepared FeatureBanks on either side, a GeneratedBank; banks beyond `chunk_bytes` are streamed, query sets beyond the query
+              budget go in slices (their bins add).  EVERY LEVEL IS A PASS OVER THE BANK: a streamed or generated bank is generated and
+              featurised again per pass, about 7 times for two quantiles -- materialise a FeatureBank where it fits.  One row layout per
+              call: off-lattice floats anywhere put both sides of every level in the hi / lo layout (a pass that meets them late starts
+              over with fresh bins).
+    distance='l2': both sides on one lattice: distance_quantiles, unchanged (key = S).  Otherwise float_path='exact' is needed (without it:
+              the NotImplementedError of ball_counts) and the WHOLE call runs on fp32 rows, as ball_counts(float_path='exact') does:
+              M = { bits(D32(q, n)) } with D32 the fixed-order float32 distance of gl_l2f32.hip (pair_histogram_f32).  A pair at +inf is
+              counted; NaN distances raise ValueError.  'mfma' raises NotImplementedError, anything else ValueError.
+    reduce_fn: optional callable(hist DeviceArray [n_bins, 1] uint64) -> DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts): every
+              level's histogram is summed before the bin is chosen, so every shard takes the same decisions; the shards must agree on the
+              layout (DeviceGroup sees to it).  index_base, ctx, chunk_bytes, batch_size, n_eff: as ball_counts."""
+    q = _check_quantiles(quantiles)          # before any Context: these checks run without a GPU
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    float_path = _check_rows_float_path(float_path)
+    if distance == "l2-lpips":
+        return _pair_quantiles_lpips(queries, bank, q, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, _layout)
+    if float_path is None or _layout != "f32":
+        try:
+            return distance_quantiles(queries, bank, q, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, chunk_bytes=chunk_bytes,
+                                      index_base=index_base)
+        except _OffLattice:
+            if float_path is None:
+                raise                        # nothing of the integer pass survives: the fp32 rows start over
+    return _pair_quantiles_f32(queries, bank, q, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
 
 
 def pair_distances(queries, bank, distance="l2-lpips", batch_size=64, lpips=None):

@@ -7,7 +7,7 @@ Score of a query x:  f_eps(x) = #{ i < n_eff : dist(x, g_i) <= eps } / n_eff  ov
 full-black-box attack, n_eff = (N // BATCH_SIZE) * BATCH_SIZE (fbb.py:77).  All eps are counted in ONE pass over the bank
 (ganleaks_amd.attack.ball_counts).
 
-    python -m ganleaks_amd.attack_models.mc --syn_data_path ... --pos_data_dir ... --neg_data_dir ... [--eps e1,e2,... | --eps_quantile q1,q2,... | --eps_pair_quantile q1,q2,...]
+    python -m ganleaks_amd.attack_models.mc --syn_data_path ... --pos_data_dir ... --neg_data_dir ... [--eps e1,e2,... | --eps_quantile q1,q2,... | --eps_pair_quantile q1,q2,... | --eps_percentile q1,q2,...]
                                             [--distance {l2,l2-lpips}]
 
 --syn_data_path, --pos_data_dir, --neg_data_dir: a folder of PNG files (8-bit codes), or a file of floats (bank_io.load_rows): an .npz with
@@ -24,6 +24,11 @@ full-black-box attack, n_eff = (N // BATCH_SIZE) * BATCH_SIZE (fbb.py:77).  All 
 --eps_pair_quantile  Hilprecht's percentile heuristic: eps = that quantile (typically 0.001) of ALL query-sample distances d(x_i, g_j), exactly
                 (ganleaks_amd.attack.distance_quantiles: an attained distance, rank floor(q * (pairs - 1))); --distance l2 on the exact-integer
                 path only
+--eps_percentile  the same percentile heuristic under either --distance and for every input the counting pass takes (float images and
+                continuous tables in the fixed-order float32 arithmetic, l2-lpips on the distance the counting pass counts):
+                ganleaks_amd.attack.pair_distance_quantiles, an attained distance of the counting pass at rank floor(q * (pairs - 1)).  Every
+                level of its radix-select (3 per distinct bin, about 7 for two quantiles) is one more pass over the bank.  On 8-bit images
+                or integer tables under --distance l2 it is --eps_pair_quantile
 Files under ./mc_attack/<exp_name>/:
     eps.npy float32 [T]; {pos,neg}_count.npy int64 [n, T]; {pos,neg}_mc.npy float64 [n, T] = count / n_eff; params.txt;
     {pos,neg}_loss.npy float64 [n, 1] = -mc[:, 0], so `eval_roc --attack_type fbb -ldir mc_attack/<exp_name>` scores the first eps.
@@ -36,13 +41,13 @@ import warnings
 
 import numpy as np
 
-from ..attack import GL_COUNT_MAX_T, Bank, _budget_bytes, attack, ball_counts, distance_quantiles, prepare_queries
+from ..attack import GL_COUNT_MAX_T, Bank, _budget_bytes, attack, ball_counts, distance_quantiles, pair_distance_quantiles, prepare_queries
 from .fbb import shard_devices, update_args  # noqa: F401  (update_args: the YAML overlay of the command line)
 from .utils import check_folder, save_files
 
 
 # options added after params.txt got its form: an unused one leaves the file as it was before the option existed
-LATER_OPTIONS = ("eps_pair_quantile",)
+LATER_OPTIONS = ("eps_pair_quantile", "eps_percentile")
 
 
 def parse_arguments(argv=None):
@@ -65,6 +70,9 @@ def parse_arguments(argv=None):
     parser.add_argument('--eps_pair_quantile', type=str, default=None,
                         help='comma-separated quantiles of ALL query-sample distances to use as radii (the percentile heuristic; try 0.001); '
                              '--distance l2 only')
+    parser.add_argument('--eps_percentile', type=str, default=None,
+                        help='comma-separated quantiles of ALL query-sample distances to use as radii (the percentile heuristic; try 0.001) '
+                             'under either --distance and for float inputs too; every level of the selection is one more pass over the bank')
     return parser.parse_args(argv)
 
 
@@ -81,7 +89,18 @@ def _floats(text, what):
 
 
 def radii_request(args):
-    """('eps', values), ('quantile', values) or ('pair_quantile', values) from the command line; refused before any file is read"""
+    """('eps', values), ('quantile', values), ('pair_quantile', values) or ('percentile', values) from the command line; refused before any
+    file is read"""
+    percentile = getattr(args, "eps_percentile", None)
+    if percentile is not None:
+        if any(getattr(args, other, None) is not None for other in ("eps", "eps_quantile", "eps_pair_quantile")):
+            raise SystemExit("--eps, --eps_quantile, --eps_pair_quantile and --eps_percentile exclude each other")
+        values = _floats(percentile, "--eps_percentile")
+        if any(not 0.0 <= v <= 1.0 for v in values):     # (NaN fails both comparisons)
+            raise SystemExit("--eps_percentile needs values in [0, 1], got %r" % (values,))
+        if not 1 <= len(values) <= GL_COUNT_MAX_T:
+            raise SystemExit("1..%d radii per run, got %d" % (GL_COUNT_MAX_T, len(values)))
+        return "percentile", values
     pair = getattr(args, "eps_pair_quantile", None)
     if pair is not None:
         if getattr(args, "eps", None) is not None or getattr(args, "eps_quantile", None) is not None:
@@ -153,9 +172,12 @@ def main(args):
                     bank = model.features(syn_imgs[:n_eff], role=model.search_role("bank"), fmt=queries.fmt)
                 nearest = lambda: attack(queries, bank, distance=distance, batch_size=args.BATCH_SIZE, lpips=model)[0]                # noqa: E731
                 count = lambda eps: ball_counts(queries, bank, eps, batch_size=args.BATCH_SIZE, distance=distance, lpips=model)        # noqa: E731
+                percentiles = lambda: pair_distance_quantiles(queries, bank, values, distance=distance, batch_size=args.BATCH_SIZE, lpips=model)[0]   # noqa: E731
             else:
                 nearest = lambda: group.attack(both, bank=syn_imgs, distance=distance, batch_size=args.BATCH_SIZE)[0]            # noqa: E731
                 count = lambda eps: group.ball_counts(both, bank=syn_imgs, eps=eps, batch_size=args.BATCH_SIZE, distance=distance)  # noqa: E731
+                percentiles = lambda: group.pair_distance_quantiles(both, bank=syn_imgs, quantiles=values, batch_size=args.BATCH_SIZE,   # noqa: E731
+                                                                    distance=distance)[0]
         elif group is None:
             queries = prepare_queries(both, "l2")
             d = int(np.prod(syn_imgs.shape[1:], dtype=np.int64))
@@ -168,15 +190,21 @@ def main(args):
             nearest = lambda: attack(queries, bank, distance="l2", batch_size=args.BATCH_SIZE, float_path="exact")[0]   # noqa: E731
             count = lambda eps: ball_counts(queries, bank, eps, batch_size=args.BATCH_SIZE, float_path="exact")         # noqa: E731
             pair_quantiles = lambda: distance_quantiles(queries, bank, values, batch_size=args.BATCH_SIZE)[0]           # noqa: E731
+            percentiles = lambda: pair_distance_quantiles(queries, bank, values, distance="l2", batch_size=args.BATCH_SIZE,   # noqa: E731
+                                                          float_path="exact")[0]
         else:
             nearest = lambda: group.attack(both, bank=syn_imgs, distance="l2", batch_size=args.BATCH_SIZE)[0]      # noqa: E731
             count = lambda eps: group.ball_counts(both, bank=syn_imgs, eps=eps, batch_size=args.BATCH_SIZE, float_path="exact")   # noqa: E731
             pair_quantiles = lambda: group.distance_quantiles(both, bank=syn_imgs, quantiles=values, batch_size=args.BATCH_SIZE)[0]   # noqa: E731
+            percentiles = lambda: group.pair_distance_quantiles(both, bank=syn_imgs, quantiles=values, batch_size=args.BATCH_SIZE,   # noqa: E731
+                                                                distance="l2", float_path="exact")[0]
         if mode == "eps":
             with np.errstate(over="ignore"):
                 eps = np.asarray(values, np.float64).astype(np.float32)
         elif mode == "pair_quantile":
             eps = np.asarray(pair_quantiles(), np.float32)
+        elif mode == "percentile":
+            eps = np.asarray(percentiles(), np.float32)
         else:
             top1 = np.asarray(nearest(), np.float32)
             eps = np.asarray([np.quantile(top1, v, method="lower") for v in values], np.float32)

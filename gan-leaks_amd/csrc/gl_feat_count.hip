@@ -19,9 +19,15 @@
 //          floats is float comparison, so the order of the keys is the order of (D32, index): column 0 is the search's key.  D32 is never
 //          NaN after fmaxf, so 0xFFFFFFFF never occurs in the top half and ~0 stays the empty slot.  As D32 of a pair does not depend on
 //          where the pair sits, neither does the set of keys: the lists need no rescoring and do not depend on tile, slice, chunk or shard.
+// EPI = 3: hist[b] += #{ pairs : lo <= bits(D32) <= hi and (bits(D32) - lo) >> shift == b } through gl_hist_epi.h's hist_epilogue on the uint32
+//          pattern of D32: D32 >= +0 (see EPI = 2), so the unsigned order of the patterns is the order of the floats and a host radix-select
+//          over such windows (attack.select_ranks with s_max = 0x7F800000, the pattern of +inf) finds the exact D32 at any rank.  The bin table
+//          (at most 8 KiB) lives in the slice buffers, as the table of EPI = 0 does.  Integer adds of a value that does not depend on where the
+//          pair sits: the histogram is a function of the multiset of D32 values.
 #include "gl_conv.h"
 #include "gl_count_epi.h"
 #include "gl_feat_pair.h"
+#include "gl_hist_epi.h"
 #include "gl_pair256.h"
 #include "gl_topk_sel.h"
 #include <cmath>
@@ -42,10 +48,14 @@ template <> struct pair_sink<1> {
 template <> struct pair_sink<2> {
     unsigned *pieces;                // [ceil(n_rows / 4)][nq][4], n_rows and nq the kernel's (one slice)
 };
+template <> struct pair_sink<3> {
+    gl_hist::hist_args<unsigned> a;  // the window on the bit pattern of D32
+    unsigned long long *hist;        // [a.n_bins]
+};
 
 // The epilogue of one tile.  acc holds the dot products of the lane's NI x 4 tiles of 16 x 16 (column = query qcol0 + j * 16 + (lane & 15) of
 // the tile, row = bank row nbase + i * 16 + r); D32 replaces them in place, so that no norm stays live next to the accumulators.
-// Every thread of the workgroup must call this (EPI = 0 has barriers and uses smem).
+// Every thread of the workgroup must call this (EPI = 0 and EPI = 3 have barriers and use smem).
 // EPI = 2: acc[i][j] is 4 consecutive bank rows (from a multiple of 4) of one query = one piece, a 16-byte store; the 16 lanes of a column
 // group are 16 consecutive queries = 256 contiguous bytes.  Pieces whose first row is past n_rows are not written; rows past n_rows inside a
 // written piece hold whatever the clamped operands gave (the selection masks n < n_rows).
@@ -74,6 +84,9 @@ __device__ __forceinline__ void finish_tile(v4f (&acc)[NI][4], const float *__re
     if constexpr (EPI == 0) {
         auto s_of = [&](int i, int j, int r) -> float { return acc[i][j][r]; };
         gl_count::count_epilogue<NI, float>(s_of, n_left, q0, qcol0, q_left, tile_q, sink.a, sink.counts, smem, lane);
+    } else if constexpr (EPI == 3) {
+        auto s_of = [&](int i, int j, int r) -> unsigned { return __float_as_uint(acc[i][j][r]); };
+        gl_hist::hist_epilogue<NI, unsigned, true>(s_of, n_left, qcol0, q_left, sink.a, sink.hist, smem, lane);
     } else if constexpr (EPI == 2) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -136,12 +149,17 @@ feat_pairs_h1_kernel(const char *__restrict__ bank, const float *__restrict__ ba
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = (v4f){0.f, 0.f, 0.f, 0.f};
+        // The binning epilogue is the one with the most live values next to the accumulators.  The lane's LDS offsets of the main loop are
+        // invariants of the tile loop; kept across that epilogue they are spilled and reloaded inside the K loop.  Formed per tile from a
+        // copy of `lane` the compiler cannot see through, they end with the K loop (a few VALU instructions per tile).
+        int mlane = lane;
+        if constexpr (EPI == 3) asm volatile("" : "+v"(mlane));
         for (int seg = 0; seg < nseg; ++seg) {
             meet();
             if (!active) continue;
             const int64_t k0 = (int64_t)seg * kSegSlices;
             const int64_t len = nk - k0 < kSegSlices ? nk - k0 : kSegSlices;
-            gl_pair256::mainloop<v8h>(sa, sb, len, smem, acc, wave, lane,
+            gl_pair256::mainloop<v8h>(sa, sb, len, smem, acc, wave, mlane,
                                       [](const v8h &a, const v8h &b, const v4f &c) { return __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c, 0, 0, 0); }, k0 * kstep, kstep);
             __syncthreads();                             // all fragment reads of the segment are done before its buffers are refilled
             if (nseg > 1) {
@@ -158,7 +176,13 @@ feat_pairs_h1_kernel(const char *__restrict__ bank, const float *__restrict__ ba
             }
         }
         if (!active) return;
-        finish_tile<EPI, 8>(acc, bank_norm, n_rows, n0 + wn * 128 + fk * 4, query_norm, nq, q0, wq * 64, GT, inv_s2, sink, smem, lane);
+        if constexpr (EPI == 3) {
+            int elane = lane;                            // (as mlane: what the epilogue derives from the lane is formed after the K loop)
+            asm volatile("" : "+v"(elane));
+            finish_tile<EPI, 8>(acc, bank_norm, n_rows, n0 + wn * 128 + (elane >> 4) * 4, query_norm, nq, q0, wq * 64, GT, inv_s2, sink, smem, elane);
+        } else {
+            finish_tile<EPI, 8>(acc, bank_norm, n_rows, n0 + wn * 128 + fk * 4, query_norm, nq, q0, wq * 64, GT, inv_s2, sink, smem, lane);
+        }
     };
 
     if constexpr (CLUSTER) {
@@ -316,6 +340,29 @@ int make_dist_sink(const char *fn, float *out, int64_t ld, int64_t n_rows, bool 
     return GL_OK;
 }
 
+// the window of gl_feat_hist* on the patterns of D32: 0 .. 0x7F800000 (+inf) is all there is (D32 >= +0 and never NaN after fmaxf), so a
+// window is cut there.  `above`: the window lies beyond every pattern and the caller returns.
+constexpr unsigned kMaxBits = 0x7F800000u;
+
+int make_hist_sink(const char *fn, uint32_t lo, int shift, int n_bins, uint64_t *hist, bool need_hist, pair_sink<3> &s, bool &above)
+{
+    static_assert(GL_HIST_MAX_BINS * 4 <= 4 * FOPER && GL_HIST_MAX_BINS * 4 <= 4 * GOPER, "the bin table lives in the slice buffers");
+    GL_REQUIRE(n_bins >= 1 && n_bins <= GL_HIST_MAX_BINS, "%s: n_bins=%d outside [1, %d]", fn, n_bins, GL_HIST_MAX_BINS);
+    GL_REQUIRE(shift >= 0 && shift <= 31, "%s: shift=%d outside [0, 31]", fn, shift);
+    if (need_hist) {
+        GL_REQUIRE(hist, "%s: NULL histogram", fn);
+        GL_REQUIRE((reinterpret_cast<uintptr_t>(hist) & 7) == 0, "%s: the histogram must be 8-byte aligned", fn);
+    }
+    above = lo > kMaxBits;
+    const unsigned long long last = (unsigned long long)lo + ((unsigned long long)n_bins << shift) - 1ull;
+    s.a.lo = lo;
+    s.a.hi = (unsigned)(last < kMaxBits ? last : kMaxBits);
+    s.a.shift = shift;
+    s.a.n_bins = n_bins;
+    s.hist = reinterpret_cast<unsigned long long *>(hist);
+    return GL_OK;
+}
+
 // the dispatch of gl_feat_knn_h1_scaled: clusters on a whole MI355X, the cluster-free persistent form on a device with fewer compute units
 // (tuning builds: GL_PAIR_VARIANT=5 forces the latter).  Either way the same bits.
 bool h1_clustered(const gl_ctx *ctx, int64_t K1)
@@ -460,6 +507,33 @@ int gl_feat_count(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_d
     if (const int rc = make_count_sink(fn, thr_host, n_thr, col0, pitch, counts_dev, n_rows > 0 && nq > 0, sink)) return rc;
     if (n_rows == 0 || nq == 0) return GL_OK;
     return launch_split<0>(ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, sink);
+}
+
+int gl_feat_hist_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,
+                           const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, uint32_t lo, int shift, int n_bins, uint64_t *hist_dev)
+{
+    static const char *fn = "gl_feat_hist_h1_scaled";
+    gl_make_current(ctx);
+    pair_sink<3> sink;
+    bool above = false;
+    if (const int rc = check_rows(fn, ctx, bank_V16_dev, bank_norm_dev, n_rows, query_V16_dev, query_norm_dev, nq, K1, 64)) return rc;
+    if (const int rc = make_hist_sink(fn, lo, shift, n_bins, hist_dev, n_rows > 0 && nq > 0, sink, above)) return rc;
+    GL_REQUIRE(row_scale > 0.0f && std::isfinite(row_scale), "%s: the row scale must be positive", fn);
+    if (n_rows == 0 || nq == 0 || above) return GL_OK;
+    return launch_h1<3>(fn, ctx, bank_V16_dev, bank_norm_dev, n_rows, query_V16_dev, query_norm_dev, nq, K1, row_scale, sink);
+}
+
+int gl_feat_hist(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev, const float *query_norm_dev,
+                 int64_t nq, int64_t K, uint32_t lo, int shift, int n_bins, uint64_t *hist_dev)
+{
+    static const char *fn = "gl_feat_hist";
+    gl_make_current(ctx);
+    pair_sink<3> sink;
+    bool above = false;
+    if (const int rc = check_rows(fn, ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, 32)) return rc;
+    if (const int rc = make_hist_sink(fn, lo, shift, n_bins, hist_dev, n_rows > 0 && nq > 0, sink, above)) return rc;
+    if (n_rows == 0 || nq == 0 || above) return GL_OK;
+    return launch_split<3>(ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, sink);
 }
 
 int gl_feat_pair_dist_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,

@@ -24,12 +24,15 @@ template <typename ST> struct hist_args {
 // NI: 16-row groups of bank rows per wave (4 or 8).  s_of(i, j, r): S of the lane's bank row i * 16 + r (valid while < n_left) and its query
 // column j (query qcol0 + j * 16 + (lane & 15) of the tile, valid while < q_left).  Every thread of the workgroup must call this (barriers);
 // smem must hold a.n_bins words and be free.
-template <int NI, typename ST, typename SOf>
+// FRESH: the second pass compares against copies of lo and hi the compiler cannot see through.  Otherwise it keeps the NI * 16 lane masks
+// of the first pass in scalar registers for the second, hundreds of them, which are spilled to lanes of vector registers set aside for the
+// whole kernel: the kernels on gl_pair256::mainloop at 8 accumulator rows have none to give without spilling inside their K loop.
+template <int NI, typename ST, bool FRESH = false, typename SOf>
 __device__ __forceinline__ void hist_epilogue(SOf s_of, int n_left, int qcol0, int q_left, const hist_args<ST> &a,
                                               unsigned long long *__restrict__ hist, char *smem, int lane)
 {
     const int frow = lane & 15;
-    const ST lo = a.lo, hi = a.hi;
+    ST lo = a.lo, hi = a.hi;
     const int shift = a.shift;
     unsigned rvalid = 0;                                  // bit i * 4 + r: the bank row is a real one
 #pragma unroll
@@ -54,6 +57,7 @@ __device__ __forceinline__ void hist_epilogue(SOf s_of, int n_left, int qcol0, i
     // (also the barrier after which the slice buffers may be overwritten)
     if (!__syncthreads_or(hit)) return;
 
+    if constexpr (FRESH) asm volatile("" : "+s"(lo), "+s"(hi));
     unsigned *tab = reinterpret_cast<unsigned *>(smem);   // [n_bins]; at most 65 536 per entry
     for (int e = threadIdx.x; e < a.n_bins; e += blockDim.x) tab[e] = 0u;
     __syncthreads();

@@ -13,6 +13,7 @@
 // the fp32 difference).  Tile: 64 queries x 64 bank rows per workgroup, 256 threads x (4 x 4) pairs,
 // K slices of 32 floats staged through LDS (row stride 36 floats: conflict-free float4 reads).
 #include "gl_count_epi.h"
+#include "gl_hist_epi.h"
 #include "gl_topk_sel.h"
 #include <cmath>
 
@@ -47,6 +48,10 @@ template <> struct f32_sink<1> {
 };
 template <> struct f32_sink<2> {
     unsigned *pieces;                // [ceil(n_rows / 4)][nq][4], n_rows and nq the kernel's (one slice)
+};
+template <> struct f32_sink<3> {
+    gl_hist::hist_args<unsigned> a;  // the window on the bit pattern of D32, hi <= 0x7F800000 (+inf): NaN patterns lie outside every window
+    unsigned long long *hist;        // [a.n_bins]
 };
 
 // The K loop of one 64 x 64 tile, shared by every epilogue: dist[a][b] = D32(query q0 + tq * 4 + a, bank row n0 + tn + 16 * b), the chain of
@@ -116,6 +121,11 @@ __device__ __forceinline__ void pair_tile_f32(const float *__restrict__ bank, in
 //        16 apart, so the tile is turned through LDS and leaves as 16-byte pieces, 64 consecutive queries (1 KiB) per wave and store.
 //        D32 >= +0 (a sum of squares divided by d > 0 never gives -0) and is not NaN for finite rows: unsigned order of the bits is the
 //        order of the floats, and 0xFFFFFFFF, the value of a masked piece, never occurs.
+// EPI 3: hist[b] += #{ pairs : lo <= bits(D32) <= hi and (bits(D32) - lo) >> shift == b }, the steps of gl_hist_epi.h in this kernel's thread
+//        layout: two compares per pair and __syncthreads_or, so that tiles without a pair inside the window leave (at the refined levels of
+//        a radix-select almost all do); the others bin their pairs into a table unsigned [n_bins] in the freed slice buffers (one LDS atomic
+//        per pair inside; a tile holds 4096 pairs) and add ONE value per non-zero bin with a 64-bit atomicAdd.  The bin is formed from the
+//        distance registers one pair at a time.  Integer adds of a function of the two rows alone: nothing depends on tile, chunk or shard.
 template <int EPI>
 __global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__restrict__ bank, int64_t n_rows, const float *__restrict__ query, int64_t nq,
                                                                 int64_t d, int q_tiles, const f32_sink<EPI> sink)
@@ -194,6 +204,36 @@ __global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__re
                 c += __shfl_xor(c, 1, 64);
                 c += __shfl_xor(c, 2, 64);
                 if (part == 0 && c != 0u) atomicAdd(&sink.counts[(q0 + ql) * A.pitch + A.col0 + t], (unsigned long long)c);
+            }
+        } else if constexpr (EPI == 3) {
+            const unsigned lo = sink.a.lo, hi = sink.a.hi;
+            const int shift = sink.a.shift, n_bins = sink.a.n_bins;
+            auto inside = [&](int a, int b) -> bool {
+                const unsigned s = __float_as_uint(dist[a][b]);
+                return ((valid >> (a * 4 + b)) & 1u) && s >= lo && s <= hi;
+            };
+            int hit = 0;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) hit |= inside(a, b) ? 1 : 0;
+            if (!__syncthreads_or(hit)) return;
+
+            static_assert(GL_HIST_MAX_BINS * 4 <= (TQ + TN) * LDS_STRIDE * 4, "the bin table must fit the slice buffers");
+            unsigned *tab = reinterpret_cast<unsigned *>(smem);     // [n_bins]; at most 4096 per entry
+            for (int e = tid; e < n_bins; e += THREADS) tab[e] = 0u;
+            __syncthreads();
+            if (hit) {
+#pragma unroll
+                for (int a = 0; a < 4; ++a)
+#pragma unroll
+                    for (int b = 0; b < 4; ++b)
+                        if (inside(a, b)) atomicAdd(&tab[(__float_as_uint(dist[a][b]) - lo) >> shift], 1u);      // below n_bins because bits <= hi
+            }
+            __syncthreads();
+            for (int e = tid; e < n_bins; e += THREADS) {
+                const unsigned c = tab[e];
+                if (c != 0u) atomicAdd(&sink.hist[e], (unsigned long long)c);
             }
         } else {
             constexpr int TS = TN + 4;                 // row stride of the turned tile: 16-byte aligned pieces
@@ -294,6 +334,34 @@ int gl_l2_count_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const fl
     for (int t = 0; t < GL_COUNT_MAX_T; ++t) sink.a.thr[t] = thr_host[skip + (t < sink.a.n ? t : sink.a.n - 1)];
     sink.counts = reinterpret_cast<unsigned long long *>(counts_dev);
     hipLaunchKernelGGL(l2_pairs_f32_kernel<1>, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev, n_rows, query_dev, nq, d,
+                       (int)q_tiles, sink);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_l2_hist_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, uint32_t lo, int shift, int n_bins,
+                   uint64_t *hist_dev)
+{
+    static const char *fn = "gl_l2_hist_f32";
+    constexpr unsigned kMaxBits = 0x7F800000u;            // +inf: the largest pattern of a D32 that is not NaN
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && n_rows >= 0 && nq >= 0 && d > 0, "%s: bad sizes", fn);
+    GL_REQUIRE(n_bins >= 1 && n_bins <= GL_HIST_MAX_BINS, "%s: n_bins=%d outside [1, %d]", fn, n_bins, GL_HIST_MAX_BINS);
+    GL_REQUIRE(shift >= 0 && shift <= 31, "%s: shift=%d outside [0, 31]", fn, shift);
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    GL_REQUIRE(bank_dev && query_dev && hist_dev, "%s: NULL device pointer", fn);
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(hist_dev) & 7) == 0, "%s: the histogram must be 8-byte aligned", fn);
+    const int64_t q_tiles = gl_ceil_div(nq, TQ), n_tiles = gl_ceil_div(n_rows, TN);
+    GL_REQUIRE(q_tiles * n_tiles < (1ll << 31), "%s: grid too large", fn);
+    if (lo > kMaxBits) return GL_OK;                      // the window lies above every pattern
+    const unsigned long long last = (unsigned long long)lo + ((unsigned long long)n_bins << shift) - 1ull;
+    f32_sink<3> sink;
+    sink.a.lo = lo;
+    sink.a.hi = (unsigned)(last < kMaxBits ? last : kMaxBits);
+    sink.a.shift = shift;
+    sink.a.n_bins = n_bins;
+    sink.hist = reinterpret_cast<unsigned long long *>(hist_dev);
+    hipLaunchKernelGGL(l2_pairs_f32_kernel<3>, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev, n_rows, query_dev, nq, d,
                        (int)q_tiles, sink);
     GL_LAUNCH_CHECK();
     return GL_OK;

@@ -354,6 +354,34 @@ def feat_count(bank, queries, thr, n_rows=None, counts=None):
     return counts
 
 
+def feat_hist(bank, queries, lo, shift, n_bins, n_rows=None, hist=None):
+    """histogram of ALL pair distances under the distance feat_knn_keys searches: hist DeviceArray [n_bins, 1] (uint64),
+    hist[b] += #{ q, n < n_rows : lo <= bits(D32(q, n)) and (bits(D32(q, n)) - lo) >> shift == b }, bits the uint32 pattern of the float32
+    distance feat_count compares and feat_pair_dist stores, bit for bit (same kernel up to the epilogue).  D32 >= +0, so the order of the
+    patterns is the order of the floats: the primitive attack.pair_distance_quantiles radix-selects on.  lo: 0 .. 2^32 - 1 (a window above
+    0x7F800000, +inf, holds nothing), 0 <= shift <= 31, 1 <= n_bins <= 2048.  `hist` from an earlier call (another chunk of the bank, another
+    slice of the queries) is added to.  Row formats and layouts as feat_knn_keys.  Asynchronous."""
+    from .attack import GL_HIST_MAX_BINS, new_hist
+    ctx = bank.ctx
+    roles = _search_pair_roles(bank, queries, "feat_hist")
+    lo, shift, n_bins = int(lo), int(shift), int(n_bins)
+    if not 0 <= lo <= 0xFFFFFFFF or not 0 <= shift <= 31 or not 1 <= n_bins <= GL_HIST_MAX_BINS:
+        raise ValueError("feat_hist needs 0 <= lo < 2^32, 0 <= shift <= 31, 1 <= n_bins <= %d; got lo=%d shift=%d n_bins=%d" %
+                         (GL_HIST_MAX_BINS, lo, shift, n_bins))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if hist is None:
+        hist = new_hist(ctx, n_bins)
+    elif tuple(hist.shape) != (n_bins, 1) or hist.dtype != np.dtype(np.uint64):
+        raise ValueError("feat_hist(hist=...): needs uint64 bins of shape %r" % ((n_bins, 1),))
+    if roles[0]:
+        check(ctx.lib.gl_feat_hist_h1_scaled(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr), queries.n,
+                                             bank.K, bank.scale, lo, shift, n_bins, _p(hist.ptr)))
+    else:
+        check(ctx.lib.gl_feat_hist(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr), queries.n, bank.K,
+                                   lo, shift, n_bins, _p(hist.ptr)))
+    return hist
+
+
 def feat_topk_keys(bank, queries, k, n_rows=None, keys=None):
     """the k nearest bank rows of every query under the distance feat_knn_keys searches: DeviceArray [Q, k] (uint64), ascending per query,
     the k smallest keys float_bits(D32(q, n)) << 32 | global index over bank rows [0, n_rows), ~0 in empty slots; D32 is the float32

@@ -361,6 +361,52 @@ class DeviceGroup:
 
         return self._run(queries, make_generator, z, bank, "l2", batch_size, None, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
 
+    def pair_distance_quantiles(self, queries, make_generator=None, z=None, bank=None, quantiles=None, batch_size=64, weights=None,
+                                distance="l2-lpips", make_lpips=None, float_path=None, **generate_kwargs):
+        """attack.pair_distance_quantiles over the group's contexts, on ball_counts' runner: rank r bins the pairs of rows
+        [bounds[r], bounds[r+1]) of the bank (handed over or generated, as in attack_on_devices), the query rows are prepared once per
+        context and kept, and the histogram of every level of the radix-select is summed across the ranks (allreduce_sum_counts, or on the
+        host where RCCL cannot form the communicator: one rendezvous per level), so every rank zooms into the same bins.
+        (eps float32 [T], key int64 [T], pairs), identical to the single-device result.  The host settles ONE layout for all ranks and all
+        levels from the rows that take part: under 'l2' as ball_counts does (float_path as in attack.pair_distance_quantiles); under
+        'l2-lpips' fp16 search rows are lattice rows only if queries and bank are both 8-bit codes (a generated bank is), else hi / lo rows on
+        every rank -- queries prepared as lattice rows are then featurised once more."""
+        from ._lib import DeviceArray
+        from .attack import _check_quantiles, _check_rows_float_path, host_rows_kind, pair_distance_quantiles
+        if quantiles is None:
+            raise ValueError("needs quantiles")
+        quantiles = _check_quantiles(quantiles)
+        _check_rows_float_path(float_path)
+        if distance not in ("l2", "l2-lpips"):
+            raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+        if distance == "l2":
+            fpath, layout = _group_layout(queries, bank, batch_size, float_path)
+        else:
+            fpath, layout = None, None
+            if getattr(queries, "kind", None) not in ("feat", "u8", "int", "f32"):       # (prepared rows: _run's TypeError)
+                kb = "u8"
+                if bank is not None:
+                    rows = bank.numpy() if isinstance(bank, DeviceArray) else bank
+                    kb = host_rows_kind(rows[:(len(rows) // int(batch_size)) * int(batch_size)])
+                if kb != "u8" or host_rows_kind(queries) != "u8":
+                    layout = "hilo"
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            if comms is not None:
+                return lambda hist: allreduce_sum_counts(hist, comm=comms[rank])
+            if self.world == 1:
+                return None
+            return lambda hist: ctx.to_device(host.merge(rank, hist.numpy(), op="sum"))
+
+        def call(prepared, shard, ctx, reduce_fn, model, lo):
+            if layout == "hilo" and getattr(prepared, "fmt", None) == "lattice":
+                prepared = model.features(queries, role="query", fmt="hilo")
+            return pair_distance_quantiles(prepared, shard, quantiles, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn,
+                                           lpips=model, index_base=lo, float_path=fpath, _layout=layout)
+
+        return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, lambda n_eff: None,
+                         reduce_fn_for, call)
+
     def nearest_neighbours(self, queries, make_generator=None, z=None, bank=None, k=None, batch_size=64, weights=None, distance="l2-lpips",
                            make_lpips=None, float_path=None, **generate_kwargs):
         """attack.nearest_neighbours over the group's contexts: rank r keeps the k nearest rows of [bounds[r], bounds[r+1]) of the bank
@@ -544,6 +590,22 @@ def distance_quantiles_on_devices(queries, make_generator=None, z=None, devices=
     _check_quantiles(quantiles)              # before any Context
     with DeviceGroup(devices) as group:
         return group.distance_quantiles(queries, make_generator, z, bank, quantiles, batch_size, weights, **generate_kwargs)
+
+
+def pair_distance_quantiles_on_devices(queries, make_generator=None, z=None, devices=None, quantiles=None, batch_size=64, weights=None, bank=None,
+                                       distance="l2-lpips", make_lpips=None, float_path=None, **generate_kwargs):
+    """attack.pair_distance_quantiles sharded over a DeviceGroup built for the call (arguments as attack_on_devices; distance and float_path
+    as attack.pair_distance_quantiles): (eps float32 [T], key int64 [T], pairs), identical to the single-device result."""
+    from .attack import _check_quantiles, _check_rows_float_path
+    if quantiles is None:
+        raise ValueError("needs quantiles")
+    _check_quantiles(quantiles)              # before any Context
+    _check_rows_float_path(float_path)
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    with DeviceGroup(devices) as group:
+        return group.pair_distance_quantiles(queries, make_generator, z, bank, quantiles, batch_size, weights, distance, make_lpips, float_path,
+                                             **generate_kwargs)
 
 
 def nearest_neighbours_on_devices(queries, make_generator=None, z=None, devices=None, k=None, batch_size=64, weights=None, bank=None,

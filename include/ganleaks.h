@@ -244,6 +244,18 @@ int gl_l2_topk_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, int64_t i
                    uint64_t *topk_keys_dev);
 int gl_l2_count_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const float *thr_host,
                     int n_thr, uint64_t *counts_dev);
+/* The histogram of ALL pair distances on fp32 rows: the primitive under an exact quantile of the nq x n_rows values D32(q, n) (the K loop of
+ * gl_l2_knn_f32 with a binning epilogue, so D32 is the same bits again).  D32 >= +0, so the unsigned order of the uint32 patterns
+ * bits(D32) is the order of the floats and a radix-select over windows of patterns finds the exact D32 at any rank.  For a window
+ * (lo: uint32, 0 <= shift <= 31, 1 <= n_bins <= GL_HIST_MAX_BINS):
+ *     hist[b] += #{ q < nq, n < n_rows : lo <= bits(D32(q, n)) <= 0x7F800000 and (bits(D32(q, n)) - lo) >> shift == b },  b < n_bins.
+ * 0x7F800000 is +inf: a pair at +inf is counted, NaN patterns lie outside every window (a first level over [0, 2^31) that holds fewer than
+ * nq * n_rows pairs shows them).  A window above 0x7F800000 returns at once.  hist_dev [n_bins] uint64, 8-byte aligned, zeroed by
+ * gl_hist_init; accumulates like gl_l2_hist_i8; shards are summed with gl_counts_add(dst, src, nq = n_bins, n_thr = 1, n_lists).
+ * n_rows == 0 or nq == 0 is GL_OK and touches nothing.  One kernel, no workspace, asynchronous; like gl_l2_count_f32 it reports under no
+ * profiling id. */
+int gl_l2_hist_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, uint32_t lo, int shift,
+                   int n_bins, uint64_t *hist_dev);
 /* Loss('l2').forward for fp32 inputs: out[i] = dist(x_hat[i], x_gt[b_gt == 1 ? 0 : i]) */
 int gl_l2_rows_f32(gl_ctx *ctx, const float *x_hat_dev, int64_t b, const float *x_gt_dev, int64_t b_gt, int64_t d, float *out_dev);
 
@@ -444,6 +456,23 @@ int gl_feat_count_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *
                             uint64_t *counts_dev);
 int gl_feat_count(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev, const float *query_norm_dev,
                   int64_t nq, int64_t K, const float *thr_host, int n_thr, int col0, int pitch, uint64_t *counts_dev);
+/* The histogram of ALL pair distances under 0.2 LPIPS + L2 (the primitive under an exact quantile of the nq x n_rows values D32(q, n): the
+ * percentile heuristic for the radius of the Monte-Carlo attack under the reference's fbb distance).  D32 >= +0 and never NaN, so the
+ * unsigned order of the uint32 patterns bits(D32) is the order of the floats.  For a window (lo: uint32, 0 <= shift <= 31,
+ * 1 <= n_bins <= GL_HIST_MAX_BINS):
+ *     hist_dev[b] += #{ q < nq, n < n_rows : lo <= bits(D32(q, n)) and (bits(D32(q, n)) - lo) >> shift == b },  b < n_bins;
+ * pairs outside the window are not counted; the window is cut at 0x7F800000 (+inf, which is inside) and one above it returns at once.
+ * hist_dev [n_bins] uint64 of gl_hist_init, 8-byte aligned; accumulates, so a streamed bank is binned chunk by chunk; shards are summed with
+ * gl_counts_add(dst, src, nq = n_bins, n_thr = 1, n_lists).  Row, norm, size and scale arguments, their checks and the choice between the
+ * three kernels as gl_feat_count_h1_scaled / gl_feat_count; n_rows == 0 or nq == 0 is GL_OK.  One kernel (the count's main loop with
+ * gl_l2_hist_i8's binning epilogue), no pairwise value is written to memory; integer adds of a value that does not depend on where a pair
+ * sits, so the histogram does not depend on tile, chunking, query slicing, sharding or kernel.  Asynchronous.  Reports as
+ * GL_PROF_FEAT_COUNT, the id of the other reductions over the same pair loop. */
+int gl_feat_hist_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,
+                           const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, uint32_t lo, int shift, int n_bins,
+                           uint64_t *hist_dev);
+int gl_feat_hist(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev, const float *query_norm_dev,
+                 int64_t nq, int64_t K, uint32_t lo, int shift, int n_bins, uint64_t *hist_dev);
 /* out_dev[q * ld + n] = D32(q, n) for q < nq, n < n_rows (ld >= n_rows floats per query): the matrix itself, for small cases -- the distance
  * histogram a radius is chosen from, and an exact handle on the per-pair values (its row minimum is the search's distance). */
 int gl_feat_pair_dist_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,

@@ -612,6 +612,324 @@ def _ball_counts_l2(queries, bank, e32, batch_size, ctx, reduce_fn, chunk_bytes,
     return out
 
 
+def _check_eps_rows(eps, nq=None):
+    """eps [Q, T] (1 <= T <= GL_COUNT_MAX_T, no NaN) -> float32 [Q, T]; needs no GPU"""
+    e = np.asarray(eps, np.float64)
+    if e.ndim != 2:
+        raise ValueError("eps must be a [Q, T] array with one row of radii per query, got shape %r" % (e.shape,))
+    if not 1 <= e.shape[1] <= GL_COUNT_MAX_T:
+        raise ValueError("eps must hold 1..%d values per query, got %d" % (GL_COUNT_MAX_T, e.shape[1]))
+    if nq is not None and e.shape[0] != int(nq):
+        raise ValueError("eps has %d rows for %d queries" % (e.shape[0], int(nq)))
+    if np.any(np.isnan(e)):
+        raise ValueError("eps holds NaN")
+    with np.errstate(over="ignore"):
+        return e.astype(np.float32)
+
+
+def eps_to_ssd_rows(eps, d, kind="u8"):
+    """eps_to_ssd element by element for a [Q, T] array of radii (one row per query): int64 [Q, T], entry by entry the largest exact S whose
+    float32 distance (_dist32) is <= float32(eps), -1 where none qualifies, 65025 d at most.  Vectorised: the float32 distance is
+    non-decreasing in S, so one bisection over [-1, 65025 d] -- bit_length(65025 d) + 1 steps of the float32 comparison itself, on all
+    entries at once -- finds what eps_to_ssd's stepping finds.  Host only."""
+    if kind not in ("u8", "int"):
+        raise ValueError("kind must be 'u8' or 'int', got %r" % (kind,))
+    d = int(d)
+    if d <= 0:
+        raise ValueError("d must be positive")
+    e32 = _check_eps_rows(eps)
+    s_max = 65025 * d
+    lo = np.full(e32.shape, -1, np.int64)                  # qualifies (or is -1)
+    hi = np.full(e32.shape, s_max + 1, np.int64)           # does not qualify (or is beyond the largest S)
+    while True:
+        open_ = hi - lo > 1
+        if not open_.any():
+            return lo
+        mid = np.where(open_, (lo + hi) // 2, 0)
+        ok = open_ & (_dist32(mid, d, kind) <= e32)
+        lo = np.where(ok, mid, lo)
+        hi = np.where(open_ & ~ok, mid, hi)
+
+
+def kth_pass_bound(s_max):
+    """ceil(log17(s_max + 2)) in integers: the most passes select_kth_rows takes"""
+    p, reach = 0, 1
+    while reach < int(s_max) + 2:
+        p, reach = p + 1, reach * 17
+    return p
+
+
+def _kth_place(lo, hi, slots, pad):
+    """up to `slots` distinct thresholds evenly strictly inside (lo, hi) per query, then `pad`: int64 [nq, GL_COUNT_MAX_T], ascending rows"""
+    w = hi - lo
+    m = np.clip(w - 1, 0, slots)
+    thr = np.empty((len(lo), GL_COUNT_MAX_T), np.int64)
+    for i in range(GL_COUNT_MAX_T):
+        thr[:, i] = np.where(i < m, lo + ((i + 1) * w) // (m + 1), pad)
+    return thr
+
+
+def select_kth_rows(count_fn, k, nq, s_max):
+    """the exact k-th smallest element (k counted from 1) of nq multisets of integers in [0, s_max], one multiset per query, by a 17-way
+    search over counts.  Host only.
+
+    count_fn(thr int64 [nq, 16]) -> int64 [nq, 16]: per query #{ S in its multiset : S <= thr[q, t] }; the rows of thr are ascending
+              (count_balls_rows, summed over chunks and shards).
+    k       : an int, or one int per query.
+    Per query a bracket (lo, hi]: the count at lo is < k (lo starts at -1), the count at hi is >= k.  hi starts at s_max + 1, a value
+    no element has and whose count is taken as infinite, which makes k beyond the multiset one more outcome of the same search.  Every
+    pass puts up to 16 distinct thresholds evenly strictly inside the bracket (the remaining slots repeat min(hi, s_max)) and moves the
+    bracket to the pair of neighbours between which the count reaches k: 17 ways, so s_max + 2 values take ceil(log17(s_max + 2)) passes
+    (kth_pass_bound: 8 up to 3 x 64 x 64 images, 10 up to 2^40).  Queries whose bracket has closed ride along with all 16 slots on their
+    answer.  The first pass gives its last slot to s_max itself -- the per-query total, so that k beyond it raises ValueError before
+    anything else is counted -- wherever the bound survives the 16-way start (it does for every d this library accepts except within a
+    few percent below a power of 17; there the refusal comes when the bracket closes on s_max + 1).
+    returns (S int64 [nq], passes = calls of count_fn <= kth_pass_bound(s_max))."""
+    nq, s_max = int(nq), int(s_max)
+    if s_max < 0:
+        raise ValueError("s_max must not be negative")
+    kk = np.asarray(k)
+    if kk.dtype == object or not np.issubdtype(kk.dtype, np.integer) or kk.ndim > 1 or (kk.ndim == 1 and len(kk) != nq):
+        raise ValueError("k must be an integer or one integer per query")
+    kk = np.broadcast_to(kk.astype(np.int64), (nq,))
+    if np.any(kk < 1):
+        raise ValueError("k counts from 1")
+    lo = np.full(nq, -1, np.int64)
+    hi = np.full(nq, s_max + 1, np.int64)
+    if nq == 0:
+        return hi, 0
+
+    def narrow(thr):
+        nonlocal lo, hi
+        c = np.asarray(count_fn(thr), np.int64)
+        if c.shape != thr.shape:
+            raise ValueError("count_fn returned shape %r for thresholds of shape %r" % (c.shape, thr.shape))
+        ge = c >= kk[:, None]
+        first = np.where(ge.any(axis=1), ge.argmax(axis=1), GL_COUNT_MAX_T)      # the first slot whose count reaches k
+        below = np.take_along_axis(thr, np.clip(first - 1, 0, GL_COUNT_MAX_T - 1)[:, None], axis=1)[:, 0]
+        at = np.take_along_axis(thr, np.clip(first, 0, GL_COUNT_MAX_T - 1)[:, None], axis=1)[:, 0]
+        lo, hi = np.where(first > 0, below, lo), np.where(first < GL_COUNT_MAX_T, at, hi)
+        return c
+
+    # widths after a 16-way start on (-1, s_max]: does the bound hold?
+    w, passes_16 = -(-(s_max + 1) // 16), 1
+    while w > 1:
+        w, passes_16 = -(-w // 17), passes_16 + 1
+    passes = 1
+    if passes_16 <= kth_pass_bound(s_max):
+        top = np.full(nq, s_max, np.int64)
+        c = narrow(_kth_place(lo, top, GL_COUNT_MAX_T - 1, top))
+        short = kk > c[:, -1]
+        if short.any():
+            q = int(np.argmax(short))
+            raise ValueError("k=%d exceeds the %d elements of query %d" % (int(kk[q]), int(c[q, -1]), q))
+    else:
+        narrow(_kth_place(lo, hi, GL_COUNT_MAX_T, np.minimum(hi, s_max)))
+    while np.any(hi - lo > 1):
+        narrow(_kth_place(lo, hi, GL_COUNT_MAX_T, np.minimum(hi, s_max)))
+        passes += 1
+    if np.any(hi > s_max):
+        q = int(np.argmax(hi > s_max))
+        raise ValueError("k=%d exceeds the elements of query %d" % (int(kk[q]), q))
+    return hi, passes
+
+
+def count_balls_rows(bank, queries, thr, n_rows=None, counts=None):
+    """launch the counting kernel with thresholds per query: counts DeviceArray [Q, T] (uint64),
+    counts[q, t] += #{ n < n_rows : S(q, n) <= thr[q, t] }.  thr: int64 [Q, T] (1 <= T <= 16), every row ascending -- a host array (uploaded
+    here) or a DeviceArray (a streamed bank uploads once for all its chunks); negative entries count nothing, entries >= 65025 d every row.
+    `counts` from an earlier call (another chunk of the bank) is added to.  The refusals of count_balls: exact-integer banks only ('u8' /
+    'int', either norm width), both sides on one lattice and with one norm width.  Returns (counts, the prepared query Bank, the bank's
+    kind), as count_balls does.  Asynchronous."""
+    ctx = bank.ctx
+    if bank.kind not in ("u8", "int"):
+        raise _OffLattice("ball counts need rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
+    if not isinstance(queries, Bank):
+        queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind=bank.kind, norms64=bank.wide)
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    if queries.kind != bank.kind:
+        raise _OffLattice("ball counts need queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" %
+                                  (queries.kind, bank.kind))
+    if queries.wide != bank.wide:
+        raise ValueError("the query Bank has %s row norms, the bank %s: prepare both with the same norms64" %
+                         ("int64" if queries.wide else "int32", "int64" if bank.wide else "int32"))
+    if isinstance(thr, DeviceArray):
+        if thr.dtype != np.dtype(np.int64) or len(thr.shape) != 2:
+            raise TypeError("thr must be int64 [Q, T]")
+        thr_dev = thr
+    else:
+        host = np.ascontiguousarray(thr, np.int64)
+        if host.ndim != 2:
+            raise ValueError("thr must be [Q, T], got shape %r" % (host.shape,))
+        if np.any(host[:, 1:] < host[:, :-1]):
+            raise ValueError("every row of thr must be ascending")
+        thr_dev = ctx.to_device(host) if host.size else None
+    shape = tuple(thr.shape)
+    if shape[0] != queries.n or not 1 <= shape[1] <= GL_COUNT_MAX_T:
+        raise ValueError("thr has shape %r for %d queries and 1..%d thresholds" % (shape, queries.n, GL_COUNT_MAX_T))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if counts is None:
+        counts = new_counts(ctx, queries.n, shape[1])
+    fn = ctx.lib.gl_l2_count_rows_i8_wide if bank.wide else ctx.lib.gl_l2_count_rows_i8
+    check(fn(ctx.handle, _p(bank.rows_i8.ptr), _p(bank.norms.ptr), n_rows, _p(queries.rows_i8.ptr), _p(queries.norms.ptr), queries.n, bank.d,
+             _p(thr_dev.ptr if thr_dev is not None else None), shape[1], _p(counts.ptr)))
+    if thr_dev is not thr:
+        ctx.sync()                           # the uploaded thresholds are released on return
+    return counts, queries, bank.kind
+
+
+def _rows_counter(what, queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """what ball_counts_rows and kth_distances share: the bank forms and refusals of _ball_counts_l2, and one pass over the bank per call of
+    the returned function.  Returns (fq: the prepared query Bank, n_rows: the local rows that take part, count_pass), with
+    count_pass(thr int64 [Q, T], rows ascending) -> int64 [Q, T], summed over the chunks and -- through reduce_fn -- the shards."""
+    unsupported = what + " are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError(unsupported + "got LPIPS feature rows")
+    prepared = isinstance(bank, Bank)
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx = bank.ctx
+        base = bank.index_base
+    else:
+        ctx = ctx or Context.get()
+        base = int(index_base)
+    shard = reduce_fn is not None or base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    if prepared and bank.kind == "f32":
+        raise _OffLattice(unsupported + "the bank is off both lattices (per-query radii on the float paths are not built)")
+    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
+    if fq.kind == "f32":
+        raise _OffLattice(unsupported + "the queries are off both lattices (per-query radii on the float paths are not built)")
+    if not prepared:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
+
+    def rows(lo, hi):
+        if generated:
+            return bank.rows(lo, hi)
+        if isinstance(bank, DeviceArray):
+            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+        return bank[lo:hi]
+
+    def count_pass(thr):
+        thr = np.ascontiguousarray(thr, np.int64)
+        counts = new_counts(ctx, fq.n, thr.shape[1])         # fresh counters per pass
+        if fq.n and n_rows:
+            thr_dev = ctx.to_device(thr)
+            if prepared:
+                count_balls_rows(bank, fq, thr_dev, n_rows, counts)
+            else:
+                for r0 in range(0, n_rows, step):
+                    r1 = min(r0 + step, n_rows)
+                    chunk = rows(r0, r1)
+                    if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
+                        raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
+                    try:
+                        b = Bank.from_images(chunk, ctx, index_base=base + r0, force_kind=fq.kind, norms64=fq.wide)
+                    except ValueError as e:
+                        raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
+                    count_balls_rows(b, fq, thr_dev, counts=counts)
+                    ctx.sync()
+            ctx.sync()                                       # thr_dev is released on return
+        if reduce_fn is not None:            # (a shard without rows takes part with zeros)
+            counts = reduce_fn(counts)
+        return counts.numpy()[:fq.n].astype(np.int64)
+
+    return fq, n_rows, count_pass
+
+
+def ball_counts_rows(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0, distance="l2"):
+    """ball_counts with one row of radii PER QUERY: counts int64 [Q, T], counts[q, t] = #{ n < n_eff : dist32(S(q, n)) <= float32(eps[q, t]) }
+    -- row q is exactly ball_counts(queries[q:q+1], bank, eps[q])[0].  For "samples within (1 + a) d1(q)" and for counts inside every
+    query's own k-NN ball of another bank (kth_distances).
+
+    eps     : [Q, T] floats, 1 <= T <= 16; within a row any order, repeats, negative values (count nothing) and inf (counts n_eff).
+    queries, bank, batch_size, ctx, chunk_bytes, index_base, reduce_fn: as ball_counts(distance='l2'): images, a prepared `Bank`, a
+              `GeneratedBank`, integer tables, either norm width, a shard of a bank; a bank beyond `chunk_bytes` is streamed, the counters
+              accumulate across the chunks.  One pass over the bank (gl_l2_count_rows_i8*: the counting kernels with thresholds per query).
+    Exact-integer L2 only: rows off both lattices, LPIPS feature rows and distance='l2-lpips' raise NotImplementedError; per-query radii on
+    the float paths are not built."""
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    nq = None if isinstance(queries, Bank) or not hasattr(queries, "__len__") else len(queries)
+    e32 = _check_eps_rows(eps, nq)           # before any Context: these checks run without a GPU
+    if distance == "l2-lpips":
+        raise NotImplementedError("per-query radii are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+                                  "distance='l2-lpips' is not (its thresholds are floats; ball_counts takes radii shared by all queries)")
+    fq, _, count_pass = _rows_counter("per-query ball counts", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    if e32.shape[0] != fq.n:
+        raise ValueError("eps has %d rows for %d queries" % (e32.shape[0], fq.n))
+    # the library sees every row sorted; the columns are put back in the caller's order at the end
+    thr = eps_to_ssd_rows(e32, fq.d, fq.kind)
+    order = np.argsort(thr, axis=1, kind="stable")
+    host = count_pass(np.take_along_axis(thr, order, axis=1))
+    out = np.empty(thr.shape, np.int64)
+    np.put_along_axis(out, order, host, axis=1)
+    return out
+
+
+def _check_kth(k):
+    """k (an int or a sequence of 1..GL_COUNT_MAX_T ints >= 1) -> list of Python ints; needs no GPU"""
+    v = np.atleast_1d(np.asarray(k))
+    if v.ndim != 1 or not 1 <= len(v) <= GL_COUNT_MAX_T:
+        raise ValueError("k must be an integer or a flat sequence of 1..%d integers, got %r" % (GL_COUNT_MAX_T, k))
+    if v.dtype == np.dtype(bool) or not np.issubdtype(v.dtype, np.integer):
+        raise ValueError("k must hold integers, got %r" % (k,))
+    if np.any(v < 1):
+        raise ValueError("k counts from 1, got %r" % (k,))
+    return [int(x) for x in v]
+
+
+def kth_distances(queries, bank, k, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0, distance="l2"):
+    """the exact distance of every query to its k-th nearest sample, for ANY k up to n_eff: the score of the k-NN density attack (k around
+    sqrt(N)) and, taken on two banks, of the density-ratio attack.  attack(k=) / nearest_neighbours carry k keys per query and stop at 32;
+    this searches the value alone and keeps no neighbour index.
+
+    k       : an int or 1..16 ints in [1, n_eff], any order, repeats allowed.
+    returns (dist float32 [Q, len(k)], S int64 [Q, len(k)], passes): S[q, i] is the k[i]-th smallest exact S(q, n) over the n_eff rows
+              attack() searches (ties counted with multiplicity: sorted(S(q, :))[k[i] - 1]), dist = dist32(S), the float32 attack() returns
+              for that S -- so dist[:, i] equals column k[i] - 1 of attack(..., k=32)'s distances for k[i] <= 32, and
+              ball_counts_rows(eps=dist) >= k everywhere.
+    passes  : every pass is one run of the counting kernels over the bank with 16 thresholds per query (count_balls_rows), driven by
+              select_kth_rows: at most ceil(log17(65025 d + 2)) passes per distinct k -- 8 up to 3 x 64 x 64 images, 10 for the largest
+              -- and the distinct k are searched one after another, so passes <= len(set(k)) * that bound.  No pairwise value is stored.
+              A streamed or generated bank is prepared / generated again on every pass.
+    queries, bank, batch_size, ctx, chunk_bytes, index_base: as ball_counts_rows.
+    reduce_fn: optional callable(counts DeviceArray [Q, 16] uint64) -> DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts): the
+              counts of every pass are summed before the brackets move, so every shard takes the same decisions; k is then checked
+              against the summed total of the first pass.
+    Exact-integer L2 only: rows off both lattices, LPIPS feature rows and distance='l2-lpips' raise NotImplementedError."""
+    ks = _check_kth(k)                       # before any Context: these checks run without a GPU
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    if distance == "l2-lpips":
+        raise NotImplementedError("k-th neighbour distances are built for the exact-integer L2 search (8-bit images or integer tables on both "
+                                  "sides); distance='l2-lpips' is not (nearest_neighbours gives its 32 nearest)")
+    fq, n_rows, count_pass = _rows_counter("k-th neighbour distances", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    if reduce_fn is None and max(ks) > n_rows:
+        raise ValueError("k=%d exceeds the %d bank rows that take part" % (max(ks), n_rows))
+    s_max = 65025 * fq.d
+    found, passes = {}, 0
+    for kk in sorted(set(ks)):
+        found[kk], p = select_kth_rows(count_pass, kk, fq.n, s_max)
+        passes += p
+    S = np.stack([found[kk] for kk in ks], axis=1) if fq.n else np.empty((0, len(ks)), np.int64)
+    return _dist32(S, fq.d, fq.kind), S, passes
+
+
+def density_ratio_loss(S_syn, S_ref):
+    """the log density ratio of the calibrated k-NN attack from the exact k-th neighbour S under the synthetic bank and under a reference
+    set: 0.5 * (ln max(S_syn, 1) - ln max(S_ref, 1)) in float64 = ln(r_syn / r_ref) with r the k-NN radius -- the k-NN density is
+    k / (N r^d), so the ratio of the two densities is this up to the factor d and the constant ln(N_ref / N_syn), which a ROC does not
+    see.  Clamping at 1, the smallest non-zero S on the lattice, keeps exact duplicates finite.  Small = member-like.  Host only."""
+    a = np.maximum(np.asarray(S_syn, np.int64), 1).astype(np.float64)
+    b = np.maximum(np.asarray(S_ref, np.int64), 1).astype(np.float64)
+    return 0.5 * (np.log(a) - np.log(b))
+
+
 GL_HIST_MAX_BINS = 2048
 _RADIX_BITS = 11                             # 2^11 = GL_HIST_MAX_BINS bins per level of select_ranks
 

@@ -361,6 +361,45 @@ class DeviceGroup:
 
         return self._run(queries, make_generator, z, bank, "l2", batch_size, None, weights, generate_kwargs, lambda n_eff: None, reduce_fn_for, call)
 
+    def kth_distances(self, queries, make_generator=None, z=None, bank=None, k=None, batch_size=64, weights=None, **generate_kwargs):
+        """attack.kth_distances over the group's contexts: rank r counts over rows [bounds[r], bounds[r+1]) of the bank (handed over or
+        generated, as in attack_on_devices); the [Q, 16] counters of every pass of the search are summed across the ranks
+        (allreduce_sum_counts, or on the host where RCCL cannot form the communicator: one rendezvous per pass), and every rank derives the
+        same next thresholds from the summed counts.  (dist float32 [Q, len(k)], S int64 [Q, len(k)], passes), identical to the
+        single-device result.  k is checked against the global n_eff before any rank starts.  The queries are prepared once per context
+        and shared with attack() / ball_counts() under 'l2' on the same array.  Rows off both lattices (or on different ones) raise
+        NotImplementedError on the host, before any context works; the group stays usable."""
+        from ._lib import DeviceArray
+        from .attack import _OffLattice, _check_kth, host_rows_kind, kth_distances
+        if k is None:
+            raise ValueError("needs k")
+        ks = _check_kth(k)
+        if getattr(queries, "kind", None) not in ("feat", "u8", "int", "f32"):           # (prepared rows: _run's TypeError)
+            kb = "u8"
+            if bank is not None:
+                rows = bank.numpy() if isinstance(bank, DeviceArray) else bank
+                kb = host_rows_kind(rows[:(len(rows) // int(batch_size)) * int(batch_size)])
+            kq = host_rows_kind(queries)
+            if kb == "f32" or kq != kb:
+                raise _OffLattice("k-th neighbour distances are built for the exact-integer L2 search (8-bit images or integer tables on both "
+                                  "sides); got %r queries, %r bank rows" % (kq, kb))
+
+        def validate(n_eff):
+            if max(ks) > n_eff:
+                raise ValueError("k=%d exceeds the %d bank rows that take part" % (max(ks), n_eff))
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            if comms is not None:
+                return lambda counts: allreduce_sum_counts(counts, comm=comms[rank])
+            if self.world == 1:
+                return None
+            return lambda counts: ctx.to_device(host.merge(rank, counts.numpy(), op="sum"))
+
+        def call(prepared, shard, ctx, reduce_fn, model, lo):
+            return kth_distances(prepared, shard, ks, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, index_base=lo)
+
+        return self._run(queries, make_generator, z, bank, "l2", batch_size, None, weights, generate_kwargs, validate, reduce_fn_for, call)
+
     def pair_distance_quantiles(self, queries, make_generator=None, z=None, bank=None, quantiles=None, batch_size=64, weights=None,
                                 distance="l2-lpips", make_lpips=None, float_path=None, **generate_kwargs):
         """attack.pair_distance_quantiles over the group's contexts, on ball_counts' runner: rank r bins the pairs of rows
@@ -590,6 +629,17 @@ def distance_quantiles_on_devices(queries, make_generator=None, z=None, devices=
     _check_quantiles(quantiles)              # before any Context
     with DeviceGroup(devices) as group:
         return group.distance_quantiles(queries, make_generator, z, bank, quantiles, batch_size, weights, **generate_kwargs)
+
+
+def kth_distances_on_devices(queries, make_generator=None, z=None, devices=None, k=None, batch_size=64, weights=None, bank=None, **generate_kwargs):
+    """attack.kth_distances sharded over a DeviceGroup built for the call (arguments as attack_on_devices):
+    (dist float32 [Q, len(k)], S int64 [Q, len(k)], passes), identical to the single-device result."""
+    from .attack import _check_kth
+    if k is None:
+        raise ValueError("needs k")
+    _check_kth(k)                            # before any Context
+    with DeviceGroup(devices) as group:
+        return group.kth_distances(queries, make_generator, z, bank, k, batch_size, weights, **generate_kwargs)
 
 
 def pair_distance_quantiles_on_devices(queries, make_generator=None, z=None, devices=None, quantiles=None, batch_size=64, weights=None, bank=None,

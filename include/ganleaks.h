@@ -194,6 +194,17 @@ int gl_l2_count_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *bank_n
 /* the same for rows prepared by gl_l2_prepare_wide (int64 norms, d <= gl_l2_max_d(1)); equal to gl_l2_count_i8 wherever both apply */
 int gl_l2_count_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
                         const int64_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *thr_host, int n_thr, uint64_t *counts_dev);
+/* thresholds PER QUERY: counts[q][t] += #{ n in [0, n_rows) : S(q, n) <= thr_dev[q][t] }.  thr_dev: [nq][n_thr] int64 in DEVICE memory, 8-byte
+ * aligned, n_thr in 1..GL_COUNT_MAX_T, ascending within each row (the caller's contract: the rows are not read on the host); a negative value
+ * means "no pair of this query qualifies", a value >= 65025 d "every pair".  The kernels, tile rule, accumulation and checks of gl_l2_count_i8
+ * (sizes, alignment, NULLs, n_thr); the result is a function of the multiset of S alone.  The primitive under counts with one radius per query
+ * and under the exact k-th smallest S per query for any k (a host search over these counts, 16 thresholds per query and pass).  Profiled
+ * under GL_PROF_L2_COUNT.  Asynchronous on the context's stream. */
+int gl_l2_count_rows_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
+                        const int32_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *thr_dev, int n_thr, uint64_t *counts_dev);
+/* the same for rows prepared by gl_l2_prepare_wide (int64 norms); equal to gl_l2_count_rows_i8 wherever both apply */
+int gl_l2_count_rows_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
+                             const int64_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *thr_dev, int n_thr, uint64_t *counts_dev);
 /* dst[q][t] += sum over l < n_lists of src[l][q][t]; src_dev is [n_lists][nq][n_thr] (e.g. what gl_allgather_rows delivers from the ranks of a
  * sharded bank): the cross-shard sum, the counterpart of gl_topk_merge. */
 int gl_counts_add(gl_ctx *ctx, uint64_t *dst_dev, const uint64_t *src_dev, int64_t nq, int n_thr, int64_t n_lists);

@@ -96,6 +96,7 @@ SIGNATURES = {
     "gl_l2_knn_f32": (_i, [_p, _p, _i64, _i64, _p, _i64, _i64, _p]),
     "gl_l2_topk_f32": (_i, [_p, _p, _i64, _i64, _p, _i64, _i64, _i, _p]),
     "gl_l2_count_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p, _i, _p]),
+    "gl_l2_count_rows_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p, _i, _p]),
     "gl_l2_hist_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, ctypes.c_uint32, _i, _i, _p]),
     "gl_keys_unpack_f32": (_i, [_p, _p, _i64, _p, _p]),
     "gl_l2_rows_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p]),
@@ -154,6 +155,8 @@ SIGNATURES = {
     "gl_feat_knn_h1_scaled": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _p, ctypes.c_float]),
     "gl_feat_count_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _i, _i, _i, _p]),
     "gl_feat_count": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _i, _i, _p]),
+    "gl_feat_count_rows_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _i, _p]),
+    "gl_feat_count_rows": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
     "gl_feat_hist_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, ctypes.c_uint32, _i, _i, _p]),
     "gl_feat_hist": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_uint32, _i, _i, _p]),
     "gl_feat_pair_dist_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _i64]),

@@ -1761,6 +1761,344 @@ def pair_distance_quantiles(queries, bank, quantiles, distance="l2-lpips", batch
     return _pair_quantiles_f32(queries, bank, q, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
 
 
+def eps_rows_to_bits(eps):
+    """per-query radii on the float paths as thresholds on the uint32 pattern of the float32 distance: eps [Q, T] floats (_check_eps_rows:
+    1 <= T <= 16, no NaN, rounded to float32) -> int64 [Q, T]; eps < 0 -> -1 (counts nothing), +-0 -> 0, +inf -> 0x7F800000, anything else
+    the pattern of float32(eps).  The distances of the float paths are >= +0, where the unsigned order of the patterns is the order of the
+    floats: bits(D32) <= thr  <=>  D32 <= float32(eps).  Host only."""
+    e32 = _check_eps_rows(eps)
+    bits = np.ascontiguousarray(e32).view(np.uint32).astype(np.int64)
+    return np.where(e32 < 0, np.int64(-1), np.where(e32 == 0, np.int64(0), bits))
+
+
+def count_balls_rows_f32(bank, queries, thr, n_rows=None, counts=None):
+    """count_balls_f32 with thresholds PER QUERY, on the uint32 pattern of the distance: counts DeviceArray [Q, T] (uint64),
+    counts[q, t] += #{ n < n_rows : bits(D32(q, n)) <= thr[q, t] } (gl_l2_count_rows_f32).  thr: int64 [Q, T] (1 <= T <= 16), every row
+    ascending (eps_rows_to_bits of sorted radii) -- a host array (uploaded here) or a DeviceArray; negative entries count nothing, entries
+    >= 0x7F800000 every row whose distance is not NaN.  `counts` from an earlier call (another chunk of the bank) is added to."""
+    ctx = bank.ctx
+    if bank.kind != "f32" or queries.kind != "f32":
+        raise ValueError("count_balls_rows_f32 takes 'f32' Banks (Bank.as_f32()), got %r queries, %r bank" % (queries.kind, bank.kind))
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    if isinstance(thr, DeviceArray):
+        if thr.dtype != np.dtype(np.int64) or len(thr.shape) != 2:
+            raise TypeError("thr must be int64 [Q, T]")
+        thr_dev = thr
+    else:
+        host = np.ascontiguousarray(thr, np.int64)
+        if host.ndim != 2:
+            raise ValueError("thr must be [Q, T], got shape %r" % (host.shape,))
+        if np.any(host[:, 1:] < host[:, :-1]):
+            raise ValueError("every row of thr must be ascending")
+        thr_dev = ctx.to_device(host) if host.size else None
+    shape = tuple(thr.shape)
+    if shape[0] != queries.n or not 1 <= shape[1] <= GL_COUNT_MAX_T:
+        raise ValueError("thr has shape %r for %d queries and 1..%d thresholds" % (shape, queries.n, GL_COUNT_MAX_T))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if counts is None:
+        counts = new_counts(ctx, queries.n, shape[1])
+    check(ctx.lib.gl_l2_count_rows_f32(ctx.handle, _p(bank.rows_f32.ptr), n_rows, _p(queries.rows_f32.ptr), queries.n, bank.d,
+                                       _p(thr_dev.ptr if thr_dev is not None else None), shape[1], _p(counts.ptr)))
+    if thr_dev is not thr:
+        ctx.sync()                           # the uploaded thresholds are released on return
+    return counts
+
+
+def _pair_rows_counter_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """the per-query counts on fp32 rows: _pair_quantiles_f32's rows, chunks and n_eff.  Returns (ctx, nq, n_rows, count_pass) with
+    count_pass(thr int64 [Q, T] on patterns, rows ascending) -> int64 [Q, T], summed over the chunks and -- through reduce_fn -- the shards.
+    A bank of one chunk is uploaded once, a longer one once per pass."""
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError("distance='l2' takes images or tables; got LPIPS feature rows")
+    prepared = isinstance(bank, Bank)
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx = bank.ctx
+        base = bank.index_base
+    else:
+        ctx = ctx or Context.get()
+        base = int(index_base)
+    shard = reduce_fn is not None or base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    fq = queries.as_f32() if isinstance(queries, Bank) else Bank.from_images(queries, ctx, force_kind="f32")
+    resident = None
+    if prepared:
+        resident = bank.as_f32()
+    else:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (4 * fq.d)))
+
+    def rows(lo, hi):
+        if generated:
+            return bank.rows(lo, hi)
+        if isinstance(bank, DeviceArray):
+            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+        return bank[lo:hi]
+
+    if resident is None and 0 < n_rows <= step:
+        resident = Bank.from_images(rows(0, n_rows), ctx, index_base=base, force_kind="f32")
+
+    def count_pass(thr):
+        thr = np.ascontiguousarray(thr, np.int64)
+        counts = new_counts(ctx, fq.n, thr.shape[1])         # fresh counters per pass
+        if fq.n and n_rows:
+            thr_dev = ctx.to_device(thr)
+            if resident is not None:
+                count_balls_rows_f32(resident, fq, thr_dev, n_rows, counts)
+            else:
+                for r0 in range(0, n_rows, step):
+                    b = Bank.from_images(rows(r0, min(r0 + step, n_rows)), ctx, index_base=base + r0, force_kind="f32")
+                    count_balls_rows_f32(b, fq, thr_dev, counts=counts)
+                    ctx.sync()
+            ctx.sync()                                       # thr_dev is released on return
+        if reduce_fn is not None:            # (a shard without rows takes part with zeros)
+            counts = reduce_fn(counts)
+        return counts.numpy()[:fq.n].astype(np.int64)
+
+    return ctx, fq.n, n_rows, count_pass
+
+
+def _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
+    """the per-query counts under 'l2-lpips': _pair_quantiles_lpips' resident / streamed decision, row preparation, query slices and single
+    row layout per call, one lpips.feat_count_rows pass per call of count_pass.  Returns (ctx, nq, n_rows, count_pass) as
+    _pair_rows_counter_f32 does."""
+    from . import lpips as _lp
+    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
+    q_feat = getattr(queries, "kind", None) == "feat"
+    if model is None and not (prepared and q_feat):        # prepared rows on both sides need no VGG16
+        model = _lp.default_model()
+    streamed = False
+    if not prepared:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
+            streamed = True
+        else:
+            per_img = _feature_row_bytes(ctx, model, bank)
+            streamed = per_img * n_rows > chunk_bytes or (not q_feat and len(queries) * per_img > chunk_bytes)
+        if not streamed:
+            bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
+
+    if not streamed:
+        if layout == "hilo" and model is not None and model.search_role("bank"):
+            fb = bank if prepared else model.features(bank, index_base=index_base, role="bank", fmt="hilo")
+            fq = queries if q_feat else model.features(queries, role="query", fmt="hilo")
+        else:
+            fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
+        nq = fq.n
+
+        def count_pass(thr):
+            thr = np.ascontiguousarray(thr, np.int64)
+            counts = new_counts(ctx, nq, thr.shape[1])           # fresh counters per pass
+            if nq and n_rows:
+                thr_dev = ctx.to_device(thr)
+                _lp.feat_count_rows(fb, fq, thr_dev, n_rows, counts)
+                ctx.sync()                                       # thr_dev is released on return
+            if reduce_fn is not None:
+                counts = reduce_fn(counts)
+            return counts.numpy()[:nq].astype(np.int64)
+    else:
+        # The stream of _pair_quantiles_lpips, once per pass.  One row layout for ALL passes: 8-bit codes give lattice rows until a query
+        # slice or a bank chunk turns out to be off-lattice floats; then the pass starts over with fresh counters in the hi / lo layout,
+        # and every later pass starts there.  Nothing of an abandoned layout survives in a counter.
+        def rows(lo, hi):
+            if generated:
+                return bank.rows(lo, hi)
+            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1))) if isinstance(bank, DeviceArray) else bank[lo:hi]
+
+        role_q = None if q_feat else model.search_role("query")
+        nq = queries.n if q_feat else len(queries)
+        if q_feat or nq == 0:
+            slices = [(0, nq)]
+        else:
+            q_step = max(1, int(_query_budget_bytes(chunk_bytes, ctx) // _feature_row_bytes(ctx, model, queries)))
+            slices = [(a, min(a + q_step, nq)) for a in range(0, nq, q_step)]
+        state = {"fmt": "hilo" if (layout == "hilo" and role_q) else None, "fq": None}
+
+        def query_rows(a, b):
+            if q_feat:
+                return queries
+            if len(slices) == 1 and state["fq"] is not None and getattr(state["fq"], "fmt", None) == state["fmt"]:
+                return state["fq"]           # one slice: featurised once per layout, not once per pass
+            fq = model.features(queries[a:b], role=role_q, fmt=state["fmt"] if role_q else None)
+            if len(slices) == 1:
+                state["fq"] = fq
+            return fq
+
+        def stream(thr_dev, n_thr, counts):
+            """False: an off-lattice slice or chunk met lattice rows"""
+            for a, b in slices:
+                if b == a:
+                    continue
+                try:
+                    fq = query_rows(a, b)
+                except ValueError:
+                    if state["fmt"] != "lattice":
+                        raise
+                    return False
+                if role_q and state["fmt"] is None:
+                    state["fmt"] = fq.fmt    # the first slice settles it: 'lattice' for 8-bit codes, else 'hilo'
+                b_role = "bank" if getattr(fq, "role", None) else None
+                step = max(1, int(chunk_bytes // (fq.K * (2 if fq.role else 4))))
+                if fq.role:
+                    step = _lp.preferred_bank_rows(step, fq.n)
+                # the slice's rows of the thresholds and of the counters
+                thr_s = thr_dev.view((b - a, n_thr), offset_bytes=a * n_thr * 8)
+                cnt_s = counts.view((b - a, n_thr), offset_bytes=a * n_thr * 8)
+                buf = None
+                for r0 in range(0, n_rows, step):
+                    try:
+                        buf = model.features(rows(r0, min(r0 + step, n_rows)), index_base=index_base + r0, role=b_role, out=buf,
+                                             fmt=getattr(fq, "fmt", None))
+                    except ValueError:
+                        if q_feat or getattr(fq, "fmt", None) != "lattice":
+                            raise
+                        return False
+                    _lp.feat_count_rows(buf, fq, thr_s, counts=cnt_s)
+                    ctx.sync()
+            return True
+
+        def count_pass(thr):
+            thr = np.ascontiguousarray(thr, np.int64)
+            n_thr = thr.shape[1]
+            counts = new_counts(ctx, nq, n_thr)
+            if nq and n_rows:
+                thr_dev = ctx.to_device(thr)                 # once per pass, for all slices and chunks
+                if not stream(thr_dev, n_thr, counts):
+                    state["fmt"], state["fq"] = "hilo", None
+                    counts = new_counts(ctx, nq, n_thr)      # the counters of the abandoned layout are dropped
+                    if not stream(thr_dev, n_thr, counts):
+                        raise AssertionError("unreachable")
+                ctx.sync()                                   # thr_dev is released on return
+            if reduce_fn is not None:        # (a shard without rows takes part with zeros)
+                counts = reduce_fn(counts)
+            return counts.numpy()[:nq].astype(np.int64)
+
+    return ctx, nq, n_rows, count_pass
+
+
+def _pair_rows_counter(queries, bank, distance, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, layout):
+    if distance == "l2-lpips":
+        return _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, layout)
+    return _pair_rows_counter_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+
+
+def pair_ball_counts_rows(queries, bank, eps, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, index_base=0,
+                          float_path=None, _layout=None):
+    """ball_counts with one row of radii PER QUERY under any distance and arithmetic path ball_counts() counts on: counts int64 [Q, T],
+    row q exactly ball_counts(queries[q:q+1], bank, eps[q], distance=..., float_path=...)[0] under the same arguments.  ball_counts_rows
+    is the older spelling and stays exact-integer only; this function is the way in for 'l2-lpips' -- the distance fbb.main hard-wires,
+    hence the default -- and for rows off both lattices.
+
+    eps     : [Q, T] floats, 1 <= T <= 16; within a row any order, repeats, negative values (count nothing) and inf (counts n_eff).
+    distance='l2-lpips': counts[q, t] = #{ n < n_eff : D32(q, n) <= float32(eps[q, t]) }, D32 the float32 distance
+              attack(distance='l2-lpips') minimises and ball_counts counts, bit for bit (the search kernel with a counting epilogue,
+              lpips.feat_count_rows).  D32 >= +0, so the kernels compare uint32 patterns (eps_rows_to_bits), which there is the float
+              compare.  Accepts what ball_counts(distance='l2-lpips') accepts: u8 or float images, prepared FeatureBanks on either side, a
+              GeneratedBank; banks beyond `chunk_bytes` are streamed (the thresholds are uploaded once for all chunks), query sets beyond
+              the query budget go in slices.  One row layout per call, as pair_distance_quantiles.
+    distance='l2': both sides on one lattice: ball_counts_rows, unchanged.  Otherwise float_path='exact' is needed (without it: the
+              NotImplementedError of ball_counts_rows) and the WHOLE call runs on fp32 rows, as ball_counts(float_path='exact') does
+              (count_balls_rows_f32).  A pair at +inf is counted at eps = inf, a NaN distance never.  'mfma' raises NotImplementedError,
+              anything else ValueError.
+    reduce_fn: optional callable(counts DeviceArray [Q, T] uint64) -> DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts); the
+              shards must agree on the layout (DeviceGroup sees to it).  index_base, ctx, chunk_bytes, batch_size, n_eff: as ball_counts."""
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    float_path = _check_rows_float_path(float_path)
+    nq = None if getattr(queries, "kind", None) in ("feat", "u8", "int", "f32") or not hasattr(queries, "__len__") else len(queries)
+    e32 = _check_eps_rows(eps, nq)           # before any Context: these checks run without a GPU
+    if distance == "l2" and (float_path is None or _layout != "f32"):
+        try:
+            return ball_counts_rows(queries, bank, e32, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, chunk_bytes=chunk_bytes,
+                                    index_base=index_base)
+        except _OffLattice:
+            if float_path is None:
+                raise                        # nothing of the integer pass survives: the fp32 rows start over
+    ctx, nq, _, count_pass = _pair_rows_counter(queries, bank, distance, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, _layout)
+    if e32.shape[0] != nq:
+        raise ValueError("eps has %d rows for %d queries" % (e32.shape[0], nq))
+    # the library sees every row sorted; the columns are put back in the caller's order at the end
+    thr = eps_rows_to_bits(e32)
+    order = np.argsort(thr, axis=1, kind="stable")
+    host = count_pass(np.take_along_axis(thr, order, axis=1))
+    out = np.empty(thr.shape, np.int64)
+    np.put_along_axis(out, order, host, axis=1)
+    return out
+
+
+def pair_kth_distances(queries, bank, k, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, index_base=0,
+                       float_path=None, _layout=None):
+    """the exact distance of every query to its k-th nearest sample, for ANY k up to n_eff, under any distance and arithmetic path
+    nearest_neighbours() searches on: the score of the k-NN density attack (k around sqrt(N)) under the reference's default distance.
+    kth_distances is the older spelling and stays exact-integer only; nearest_neighbours carries k keys per query and stops at 32.
+
+    k       : an int or 1..16 ints in [1, n_eff], any order, repeats allowed.
+    returns (dist float32 [Q, len(k)], key int64 [Q, len(k)], passes): key[q, i] = sorted(bits(D32(q, :)))[k[i] - 1] over the n_eff rows
+              attack() searches, ties counted with multiplicity, bits the uint32 pattern of the float32 distance; dist is that pattern viewed
+              as float32.  So dist[:, i] equals column k[i] - 1 of nearest_neighbours(..., 32)'s distances for k[i] <= 32, bit for bit, and
+              pair_ball_counts_rows(eps=dist) >= k everywhere.  On the exact-integer path (below) key is S.
+    passes  : every pass is one run of the counting kernels over the bank with 16 thresholds per query, driven by
+              select_kth_rows(count_pass, k, Q, 0x7F800000): D32 >= +0, so the unsigned order of the patterns is the order of the floats
+              and the search runs on integers in [0, 0x7F800000] (+inf): 8 passes per distinct k, the distinct k one after another.  No
+              pairwise value is stored.
+    distance='l2-lpips': D32 the float32 distance attack(distance='l2-lpips') minimises, bit for bit (lpips.feat_count_rows).  Accepts what
+              pair_ball_counts_rows accepts.  EVERY PASS IS A PASS OVER THE BANK: a streamed or generated bank is generated and featurised
+              again on each of the 8 passes per distinct k -- materialise the rows with model.features(bank, role="bank") where they fit and
+              hand over that FeatureBank.  One row layout per call: an off-lattice float chunk met late restarts the pass with fresh
+              counters in the hi / lo layout, and every later pass starts there.
+    distance='l2': both sides on one lattice: kth_distances, unchanged (key = S).  Otherwise float_path='exact' is needed (without it: the
+              NotImplementedError of kth_distances) and the WHOLE call runs on fp32 rows (count_balls_rows_f32).  NaN distances have no
+              rank: they raise ValueError.  'mfma' raises NotImplementedError, anything else ValueError.
+    k > n_eff raises ValueError.  reduce_fn: the cross-shard SUM of a [Q, T] counter table (shard.allreduce_sum_counts), applied to every
+              pass before the brackets move, so every shard takes the same decisions; a shard without rows takes part with zeros."""
+    ks = _check_kth(k)                       # before any Context: these checks run without a GPU
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    float_path = _check_rows_float_path(float_path)
+    if distance == "l2" and (float_path is None or _layout != "f32"):
+        try:
+            return kth_distances(queries, bank, ks, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, chunk_bytes=chunk_bytes, index_base=index_base)
+        except _OffLattice:
+            if float_path is None:
+                raise
+    ctx, nq, n_rows, count_pass = _pair_rows_counter(queries, bank, distance, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, _layout)
+    if reduce_fn is None and max(ks) > n_rows:
+        raise ValueError("k=%d exceeds the %d bank rows that take part" % (max(ks), n_rows))
+    expected = int(n_rows)                   # the rows that take part, summed across the shards like a counter
+    if reduce_fn is not None:
+        expected = int(reduce_fn(ctx.to_device(np.asarray([[expected]], np.uint64))).numpy().reshape(-1)[0])
+
+    def checked_pass(thr):
+        c = count_pass(thr)
+        top = np.asarray(thr)[:, -1] >= F32_BITS_MAX         # the first pass carries +inf in its last slot: the per-query total
+        if np.any(top & (c[:, -1] < expected)):
+            q = int(np.argmax(top & (c[:, -1] < expected)))
+            raise ValueError("%d of the %d distances of query %d are NaN (rows with NaN, or with +inf and -inf, or differences that overflow "
+                             "to inf - inf): they have no rank" % (expected - int(c[q, -1]), expected, q))
+        return c
+
+    found, passes = {}, 0
+    for kk in sorted(set(ks)):
+        found[kk], p = select_kth_rows(checked_pass, kk, nq, F32_BITS_MAX)
+        passes += p
+    key = np.stack([found[kk] for kk in ks], axis=1) if nq else np.empty((0, len(ks)), np.int64)
+    return key.astype(np.uint32).view(np.float32), key, passes
+
+
+def density_ratio_loss_f32(d_syn, d_ref):
+    """density_ratio_loss for the float paths, from the k-th neighbour DISTANCES (pair_kth_distances) under the synthetic bank and under a
+    reference set: 0.5 * (ln max(d_syn, 2^-149) - ln max(d_ref, 2^-149)) in float64.  The distances are mean squared differences (or
+    0.2 LPIPS + L2), so the half is the square root of the radius as there.  Clamping at 2^-149, the smallest non-zero value of the pattern
+    lattice (as 1 is the smallest non-zero S), keeps exact duplicates finite.  Small = member-like.  Host only."""
+    tiny = 2.0 ** -149
+    a = np.maximum(np.asarray(d_syn, np.float64), tiny)
+    b = np.maximum(np.asarray(d_ref, np.float64), tiny)
+    return 0.5 * (np.log(a) - np.log(b))
+
+
 def pair_distances(queries, bank, distance="l2-lpips", batch_size=64, lpips=None):
     """the distance matrix attack(..., distance='l2-lpips') minimises over and ball_counts(..., distance='l2-lpips') counts in, float32
     [Q, n_eff]: M[q, n] = D32(q, n), n_eff by attack()'s rule, so M.min(axis=1) / the first argmin are attack()'s (dist, idx) and

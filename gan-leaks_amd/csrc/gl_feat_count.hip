@@ -24,6 +24,10 @@
 //          over such windows (attack.select_ranks with s_max = 0x7F800000, the pattern of +inf) finds the exact D32 at any rank.  The bin table
 //          (at most 8 KiB) lives in the slice buffers, as the table of EPI = 0 does.  Integer adds of a value that does not depend on where the
 //          pair sits: the histogram is a function of the multiset of D32 values.
+// EPI = 4: counts[q][t] += #{ n < n_rows : bits(D32(q, n)) <= thr[q][t] }, the thresholds of every query from device memory, through
+//          gl_count_epi.h's second count_epilogue (rows_args) on the uint32 pattern of D32 with s_max = 0x7F800000 (+inf): D32 >= +0 (see
+//          EPI = 2), so the unsigned compare of the patterns IS the float compare D32 <= float(thr), and a host search over integer brackets
+//          (attack.select_kth_rows) finds the exact D32 of any rank per query.  Same commuting integer adds as EPI = 0.
 #include "gl_conv.h"
 #include "gl_count_epi.h"
 #include "gl_feat_pair.h"
@@ -52,10 +56,14 @@ template <> struct pair_sink<3> {
     gl_hist::hist_args<unsigned> a;  // the window on the bit pattern of D32
     unsigned long long *hist;        // [a.n_bins]
 };
+template <> struct pair_sink<4> {
+    gl_count::rows_args a;           // thr[nq][a.n] on the bit pattern of D32, s_max = 0x7F800000
+    unsigned long long *counts;      // [nq][a.n]
+};
 
 // The epilogue of one tile.  acc holds the dot products of the lane's NI x 4 tiles of 16 x 16 (column = query qcol0 + j * 16 + (lane & 15) of
 // the tile, row = bank row nbase + i * 16 + r); D32 replaces them in place, so that no norm stays live next to the accumulators.
-// Every thread of the workgroup must call this (EPI = 0 and EPI = 3 have barriers and use smem).
+// Every thread of the workgroup must call this (EPI = 0, EPI = 3 and EPI = 4 have barriers and use smem).
 // EPI = 2: acc[i][j] is 4 consecutive bank rows (from a multiple of 4) of one query = one piece, a 16-byte store; the 16 lanes of a column
 // group are 16 consecutive queries = 256 contiguous bytes.  Pieces whose first row is past n_rows are not written; rows past n_rows inside a
 // written piece hold whatever the clamped operands gave (the selection masks n < n_rows).
@@ -87,6 +95,9 @@ __device__ __forceinline__ void finish_tile(v4f (&acc)[NI][4], const float *__re
     } else if constexpr (EPI == 3) {
         auto s_of = [&](int i, int j, int r) -> unsigned { return __float_as_uint(acc[i][j][r]); };
         gl_hist::hist_epilogue<NI, unsigned, true>(s_of, n_left, qcol0, q_left, sink.a, sink.hist, smem, lane);
+    } else if constexpr (EPI == 4) {
+        auto s_of = [&](int i, int j, int r) -> unsigned { return __float_as_uint(acc[i][j][r]); };
+        gl_count::count_epilogue<NI, unsigned>(s_of, n_left, q0, qcol0, q_left, tile_q, sink.a, sink.counts, smem, lane);
     } else if constexpr (EPI == 2) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -363,6 +374,25 @@ int make_hist_sink(const char *fn, uint32_t lo, int shift, int n_bins, uint64_t 
     return GL_OK;
 }
 
+// per-query thresholds of gl_feat_count_rows* on the patterns of D32: rows_bound<unsigned> gives at most kMaxBits + 1, which fits
+int make_rows_sink(const char *fn, const int64_t *thr_dev, int n_thr, uint64_t *counts, bool need_ptrs, pair_sink<4> &s)
+{
+    static_assert(gl_count::ROWS_THR_OFFSET + GT * GL_COUNT_MAX_T * 4 <= 4 * GOPER && gl_count::ROWS_THR_OFFSET + FT * GL_COUNT_MAX_T * 4 <= 4 * FOPER,
+                  "counters and bounds must fit the slice buffers");
+    GL_REQUIRE(n_thr >= 1 && n_thr <= GL_COUNT_MAX_T, "%s: n_thr=%d outside [1, %d]", fn, n_thr, GL_COUNT_MAX_T);
+    if (need_ptrs) {
+        GL_REQUIRE(thr_dev, "%s: NULL thresholds", fn);
+        GL_REQUIRE((reinterpret_cast<uintptr_t>(thr_dev) & 7) == 0, "%s: the thresholds must be 8-byte aligned", fn);
+        GL_REQUIRE(counts, "%s: NULL counters", fn);
+        GL_REQUIRE((reinterpret_cast<uintptr_t>(counts) & 7) == 0, "%s: the counters must be 8-byte aligned", fn);
+    }
+    s.a.thr = reinterpret_cast<const long long *>(thr_dev);
+    s.a.s_max = (long long)kMaxBits;
+    s.a.n = n_thr;
+    s.counts = reinterpret_cast<unsigned long long *>(counts);
+    return GL_OK;
+}
+
 // the dispatch of gl_feat_knn_h1_scaled: clusters on a whole MI355X, the cluster-free persistent form on a device with fewer compute units
 // (tuning builds: GL_PAIR_VARIANT=5 forces the latter).  Either way the same bits.
 bool h1_clustered(const gl_ctx *ctx, int64_t K1)
@@ -507,6 +537,31 @@ int gl_feat_count(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_d
     if (const int rc = make_count_sink(fn, thr_host, n_thr, col0, pitch, counts_dev, n_rows > 0 && nq > 0, sink)) return rc;
     if (n_rows == 0 || nq == 0) return GL_OK;
     return launch_split<0>(ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, sink);
+}
+
+int gl_feat_count_rows_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,
+                                 const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, const int64_t *thr_dev, int n_thr,
+                                 uint64_t *counts_dev)
+{
+    static const char *fn = "gl_feat_count_rows_h1_scaled";
+    gl_make_current(ctx);
+    pair_sink<4> sink;
+    if (const int rc = check_rows(fn, ctx, bank_V16_dev, bank_norm_dev, n_rows, query_V16_dev, query_norm_dev, nq, K1, 64)) return rc;
+    if (const int rc = make_rows_sink(fn, thr_dev, n_thr, counts_dev, n_rows > 0 && nq > 0, sink)) return rc;
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    return launch_h1<4>(fn, ctx, bank_V16_dev, bank_norm_dev, n_rows, query_V16_dev, query_norm_dev, nq, K1, row_scale, sink);
+}
+
+int gl_feat_count_rows(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev,
+                       const float *query_norm_dev, int64_t nq, int64_t K, const int64_t *thr_dev, int n_thr, uint64_t *counts_dev)
+{
+    static const char *fn = "gl_feat_count_rows";
+    gl_make_current(ctx);
+    pair_sink<4> sink;
+    if (const int rc = check_rows(fn, ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, 32)) return rc;
+    if (const int rc = make_rows_sink(fn, thr_dev, n_thr, counts_dev, n_rows > 0 && nq > 0, sink)) return rc;
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    return launch_split<4>(ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, sink);
 }
 
 int gl_feat_hist_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,

@@ -53,6 +53,10 @@ template <> struct f32_sink<3> {
     gl_hist::hist_args<unsigned> a;  // the window on the bit pattern of D32, hi <= 0x7F800000 (+inf): NaN patterns lie outside every window
     unsigned long long *hist;        // [a.n_bins]
 };
+template <> struct f32_sink<4> {
+    gl_count::rows_args a;           // thr[nq][a.n] on the bit pattern of D32, s_max = 0x7F800000 (+inf)
+    unsigned long long *counts;      // [nq][a.n]
+};
 
 // The K loop of one 64 x 64 tile, shared by every epilogue: dist[a][b] = D32(query q0 + tq * 4 + a, bank row n0 + tn + 16 * b), the chain of
 // the header comment.  Rows beyond n_rows and queries beyond nq are zero-filled in LDS: their distance is finite and the epilogues mask them.
@@ -126,6 +130,15 @@ __device__ __forceinline__ void pair_tile_f32(const float *__restrict__ bank, in
 //        a radix-select almost all do); the others bin their pairs into a table unsigned [n_bins] in the freed slice buffers (one LDS atomic
 //        per pair inside; a tile holds 4096 pairs) and add ONE value per non-zero bin with a 64-bit atomicAdd.  The bin is formed from the
 //        distance registers one pair at a time.  Integer adds of a function of the two rows alone: nothing depends on tile, chunk or shard.
+// EPI 4: counts[q][t] += #{ n : bits(D32(q, n)) <= thr[q][t] }, EPI 1 with the thresholds of every query from device memory (int64 on the
+//        pattern of D32, ascending per query; gl_count_epi.h's rows_bound turns "<= thr" into "< bound", at most 0x7F800001).  D32 >= +0, so
+//        the unsigned compare of the patterns is the float compare; NaN patterns lie above every bound.  One compare per pair against
+//        +inf and __syncthreads_or first (see there for what it buys), then the tile is turned as EPI 1 turns it, so that 4 neighbouring
+//        lanes hold a query's 64 distances; each of them reads four of the query's sixteen bounds (after the K loop: no bound is live in
+//        it) and they hand them round by shuffle.  The bounds are walked from the query's LAST one down and a wave stops at the first one
+//        it holds nothing within (a query lives in one wave: no barrier is needed for that), so tiles without a hit cost one compare per
+//        pair; the others count per bound, fold with two shuffles and add ONE value per non-zero (query, t) with a 64-bit atomicAdd.
+//        Queries beyond nq get the bound 0, which nothing meets.
 template <int EPI>
 __global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__restrict__ bank, int64_t n_rows, const float *__restrict__ query, int64_t nq,
                                                                 int64_t d, int q_tiles, const f32_sink<EPI> sink)
@@ -161,10 +174,12 @@ __global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__re
     } else {
         const int n_left = gl_count::rows_left(n_rows, n0), q_left = gl_count::rows_left(nq, q0);
         unsigned valid = 0;                           // bit a * 4 + b: the pair is a real one
+        if constexpr (EPI != 4) {
 #pragma unroll
-        for (int a = 0; a < 4; ++a)
+            for (int a = 0; a < 4; ++a)
 #pragma unroll
-            for (int b = 0; b < 4; ++b) valid |= ((tq * 4 + a < q_left && tn + 16 * b < n_left) ? 1u : 0u) << (a * 4 + b);
+                for (int b = 0; b < 4; ++b) valid |= ((tq * 4 + a < q_left && tn + 16 * b < n_left) ? 1u : 0u) << (a * 4 + b);
+        }
 
         if constexpr (EPI == 1) {
             const gl_count::count_args<float> &A = sink.a;
@@ -204,6 +219,61 @@ __global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__re
                 c += __shfl_xor(c, 1, 64);
                 c += __shfl_xor(c, 2, 64);
                 if (part == 0 && c != 0u) atomicAdd(&sink.counts[(q0 + ql) * A.pitch + A.col0 + t], (unsigned long long)c);
+            }
+        } else if constexpr (EPI == 4) {
+            // One compare per pair first, as in EPI 1, here against +inf, the largest bound there is: a tile that holds nothing but NaN
+            // leaves.  (The bounds of the queries are not read yet.  Reduced to this one bit right behind the K loop, the distances leave
+            // the loop at EPI 1's register count, two waves per SIMD; turned without it, the kernel needs more than 256 registers and runs
+            // at one, as it does when the masks below are formed from the thread index the K loop holds: hence the opaque copy.)
+            int alive = 0;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) alive |= __float_as_uint(dist[a][b]) <= 0x7F800000u ? 1 : 0;
+            if (!__syncthreads_or(alive)) return;
+            int etid = tid;
+            asm volatile("" : "+v"(etid));
+            const int etq = etid >> 4, etn = etid & 15;
+
+            // the tile turned through LDS as for EPI 1, as patterns (masked pairs as 0xFFFFFFFF, which lies above every bound): a query's 64
+            // distances then sit with 4 neighbouring lanes, 16 each, and nothing below needs the K loop's registers or another barrier
+            constexpr int TS = TN + 4;
+            static_assert(TQ * TS <= (TQ + TN) * LDS_STRIDE, "the turned tile must fit the slice buffers");
+            unsigned *turn = reinterpret_cast<unsigned *>(smem);   // [TQ][TS]
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    turn[(etq * 4 + a) * TS + etn + 16 * b] =
+                        (etq * 4 + a < q_left && etn + 16 * b < n_left) ? __float_as_uint(dist[a][b]) : 0xFFFFFFFFu;
+            __syncthreads();
+            const int ql = etid >> 2, part = etid & 3, lane = etid & 63;
+            uint4 v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const uint4 *>(&turn[ql * TS + part * 16 + i * 4]);
+            // each of the query's four lanes reads four of its (at most sixteen) bounds, here and not before: none is live in the K loop
+            const int n_thr = sink.a.n;
+            const long long *thr_q = sink.a.thr + (q0 + (ql < q_left ? ql : 0)) * n_thr;
+            unsigned mine[4];                                       // bounds part * 4 .. part * 4 + 3
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int t = part * 4 + i;
+                const unsigned bound = gl_count::rows_bound<unsigned>(thr_q[t < n_thr ? t : n_thr - 1], sink.a.s_max);
+                mine[i] = (ql < q_left && t < n_thr) ? bound : 0u;
+            }
+            // from the query's LAST bound down: a wave that holds nothing within it leaves at once (ascending bounds: nothing within the
+            // smaller ones either), which is where almost every tile of a refined search ends
+            for (int t = n_thr - 1; t >= 0; --t) {
+                const int i = t & 3;
+                const unsigned own = i == 0 ? mine[0] : (i == 1 ? mine[1] : (i == 2 ? mine[2] : mine[3]));
+                const unsigned th = __shfl(own, (lane & ~3) | (t >> 2), 64);
+                unsigned c = 0;
+#pragma unroll
+                for (int k = 0; k < 4; ++k) c += (v[k].x < th ? 1u : 0u) + (v[k].y < th ? 1u : 0u) + (v[k].z < th ? 1u : 0u) + (v[k].w < th ? 1u : 0u);
+                if (!__any(c != 0u)) break;
+                c += __shfl_xor(c, 1, 64);
+                c += __shfl_xor(c, 2, 64);
+                if (part == 0 && c != 0u) atomicAdd(&sink.counts[(q0 + ql) * n_thr + t], (unsigned long long)c);
             }
         } else if constexpr (EPI == 3) {
             const unsigned lo = sink.a.lo, hi = sink.a.hi;
@@ -334,6 +404,31 @@ int gl_l2_count_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const fl
     for (int t = 0; t < GL_COUNT_MAX_T; ++t) sink.a.thr[t] = thr_host[skip + (t < sink.a.n ? t : sink.a.n - 1)];
     sink.counts = reinterpret_cast<unsigned long long *>(counts_dev);
     hipLaunchKernelGGL(l2_pairs_f32_kernel<1>, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev, n_rows, query_dev, nq, d,
+                       (int)q_tiles, sink);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_l2_count_rows_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const int64_t *thr_dev,
+                         int n_thr, uint64_t *counts_dev)
+{
+    static const char *fn = "gl_l2_count_rows_f32";
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && n_rows >= 0 && nq >= 0 && d > 0, "%s: bad sizes", fn);
+    GL_REQUIRE(n_thr >= 1 && n_thr <= GL_COUNT_MAX_T, "%s: n_thr=%d outside [1, %d]", fn, n_thr, GL_COUNT_MAX_T);
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    GL_REQUIRE(thr_dev, "%s: NULL thresholds", fn);
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(thr_dev) & 7) == 0, "%s: the thresholds must be 8-byte aligned", fn);
+    GL_REQUIRE(bank_dev && query_dev && counts_dev, "%s: NULL device pointer", fn);
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(counts_dev) & 7) == 0, "%s: the counters must be 8-byte aligned", fn);
+    const int64_t q_tiles = gl_ceil_div(nq, TQ), n_tiles = gl_ceil_div(n_rows, TN);
+    GL_REQUIRE(q_tiles * n_tiles < (1ll << 31), "%s: grid too large", fn);
+    f32_sink<4> sink;
+    sink.a.thr = reinterpret_cast<const long long *>(thr_dev);
+    sink.a.s_max = 0x7F800000ll;                          // +inf: the largest pattern of a D32 that is not NaN
+    sink.a.n = n_thr;
+    sink.counts = reinterpret_cast<unsigned long long *>(counts_dev);
+    hipLaunchKernelGGL(l2_pairs_f32_kernel<4>, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev, n_rows, query_dev, nq, d,
                        (int)q_tiles, sink);
     GL_LAUNCH_CHECK();
     return GL_OK;

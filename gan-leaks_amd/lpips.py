@@ -354,6 +354,47 @@ def feat_count(bank, queries, thr, n_rows=None, counts=None):
     return counts
 
 
+def feat_count_rows(bank, queries, thr, n_rows=None, counts=None):
+    """feat_count with thresholds PER QUERY, on the uint32 pattern of the distance: counts DeviceArray [Q, T] (uint64),
+    counts[q, t] += #{ n < n_rows : bits(D32(q, n)) <= thr[q, t] }, D32 the float32 distance feat_count compares, bit for bit (same kernel up
+    to the epilogue).  D32 >= +0, so the compare of the patterns is the float compare D32 <= float32(eps) for thr = attack.eps_rows_to_bits(eps).
+    thr: int64 [Q, T] (1 <= T <= 16), every row ascending -- a host array (uploaded here) or a DeviceArray (a streamed bank uploads once for
+    all its chunks); negative entries count nothing, entries >= 0x7F800000 (+inf) every row.  `counts` from an earlier call (another chunk of
+    the bank) is added to.  Row formats and layouts as feat_knn_keys.  Asynchronous unless the thresholds were uploaded here."""
+    from .attack import GL_COUNT_MAX_T, new_counts
+    ctx = bank.ctx
+    roles = _search_pair_roles(bank, queries, "feat_count_rows")
+    if isinstance(thr, DeviceArray):
+        if thr.dtype != np.dtype(np.int64) or len(thr.shape) != 2:
+            raise TypeError("thr must be int64 [Q, T]")
+        thr_dev = thr
+    else:
+        host = np.ascontiguousarray(thr, np.int64)
+        if host.ndim != 2:
+            raise ValueError("thr must be [Q, T], got shape %r" % (host.shape,))
+        if np.any(host[:, 1:] < host[:, :-1]):
+            raise ValueError("every row of thr must be ascending")
+        thr_dev = ctx.to_device(host) if host.size else None
+    shape = tuple(thr.shape)
+    if shape[0] != queries.n or not 1 <= shape[1] <= GL_COUNT_MAX_T:
+        raise ValueError("thr has shape %r for %d queries and 1..%d thresholds" % (shape, queries.n, GL_COUNT_MAX_T))
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if counts is None:
+        counts = new_counts(ctx, queries.n, shape[1])
+    elif tuple(counts.shape) != (max(queries.n, 1), shape[1]) or counts.dtype != np.dtype(np.uint64):
+        raise ValueError("feat_count_rows(counts=...): needs uint64 counters of shape %r" % ((max(queries.n, 1), shape[1]),))
+    thr_ptr = _p(thr_dev.ptr if thr_dev is not None else None)
+    if roles[0]:
+        check(ctx.lib.gl_feat_count_rows_h1_scaled(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr),
+                                                   queries.n, bank.K, bank.scale, thr_ptr, shape[1], _p(counts.ptr)))
+    else:
+        check(ctx.lib.gl_feat_count_rows(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr), queries.n,
+                                         bank.K, thr_ptr, shape[1], _p(counts.ptr)))
+    if thr_dev is not thr:
+        ctx.sync()                           # the uploaded thresholds are released on return
+    return counts
+
+
 def feat_hist(bank, queries, lo, shift, n_bins, n_rows=None, hist=None):
     """histogram of ALL pair distances under the distance feat_knn_keys searches: hist DeviceArray [n_bins, 1] (uint64),
     hist[b] += #{ q, n < n_rows : lo <= bits(D32(q, n)) and (bits(D32(q, n)) - lo) >> shift == b }, bits the uint32 pattern of the float32

@@ -446,6 +446,83 @@ class DeviceGroup:
         return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, lambda n_eff: None,
                          reduce_fn_for, call)
 
+    def _pair_rows_job(self, queries, make_generator, z, bank, batch_size, weights, distance, make_lpips, float_path, generate_kwargs, validate, job):
+        """what pair_kth_distances and pair_ball_counts_rows share: pair_distance_quantiles' plumbing -- the host settles ONE layout for all
+        ranks and all passes from the rows that take part, the [Q, T] counters of every pass are summed across the ranks.
+        job(prepared, shard, ctx, reduce_fn, model, lo, fpath, layout) is the per-rank call."""
+        from ._lib import DeviceArray
+        from .attack import host_rows_kind
+        if distance == "l2":
+            fpath, layout = _group_layout(queries, bank, batch_size, float_path)
+        else:
+            fpath, layout = None, None
+            if getattr(queries, "kind", None) not in ("feat", "u8", "int", "f32"):       # (prepared rows: _run's TypeError)
+                kb = "u8"
+                if bank is not None:
+                    rows = bank.numpy() if isinstance(bank, DeviceArray) else bank
+                    kb = host_rows_kind(rows[:(len(rows) // int(batch_size)) * int(batch_size)])
+                if kb != "u8" or host_rows_kind(queries) != "u8":
+                    layout = "hilo"
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            if comms is not None:
+                return lambda counts: allreduce_sum_counts(counts, comm=comms[rank])
+            if self.world == 1:
+                return None
+            return lambda counts: ctx.to_device(host.merge(rank, counts.numpy(), op="sum"))
+
+        def call(prepared, shard, ctx, reduce_fn, model, lo):
+            if layout == "hilo" and getattr(prepared, "fmt", None) == "lattice":
+                prepared = model.features(queries, role="query", fmt="hilo")
+            return job(prepared, shard, ctx, reduce_fn, model, lo, fpath, layout)
+
+        return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call)
+
+    def pair_kth_distances(self, queries, make_generator=None, z=None, bank=None, k=None, batch_size=64, weights=None, distance="l2-lpips",
+                           make_lpips=None, float_path=None, **generate_kwargs):
+        """attack.pair_kth_distances over the group's contexts, on pair_distance_quantiles' plumbing: rank r counts over rows
+        [bounds[r], bounds[r+1]) of the bank (handed over or generated, as in attack_on_devices); the [Q, 16] counters of every pass of the
+        search are summed across the ranks (allreduce_sum_counts, or on the host where RCCL cannot form the communicator: one rendezvous per
+        pass), and every rank derives the same next thresholds from the summed counts.  (dist float32 [Q, len(k)], key int64 [Q, len(k)],
+        passes), identical to the single-device result.  k is checked against the global n_eff before any rank starts; the host settles
+        one layout for all ranks and passes, as pair_distance_quantiles does.  distance, float_path: as attack.pair_kth_distances."""
+        from .attack import _check_kth, _check_rows_float_path, pair_kth_distances
+        if k is None:
+            raise ValueError("needs k")
+        ks = _check_kth(k)
+        _check_rows_float_path(float_path)
+        if distance not in ("l2", "l2-lpips"):
+            raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+
+        def validate(n_eff):
+            if max(ks) > n_eff:
+                raise ValueError("k=%d exceeds the %d bank rows that take part" % (max(ks), n_eff))
+
+        def job(prepared, shard, ctx, reduce_fn, model, lo, fpath, layout):
+            return pair_kth_distances(prepared, shard, ks, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, lpips=model,
+                                      index_base=lo, float_path=fpath, _layout=layout)
+
+        return self._pair_rows_job(queries, make_generator, z, bank, batch_size, weights, distance, make_lpips, float_path, generate_kwargs, validate, job)
+
+    def pair_ball_counts_rows(self, queries, make_generator=None, z=None, bank=None, eps=None, batch_size=64, weights=None, distance="l2-lpips",
+                              make_lpips=None, float_path=None, **generate_kwargs):
+        """attack.pair_ball_counts_rows over the group's contexts, on pair_distance_quantiles' plumbing: the [Q, T] counters are summed
+        across the ranks.  int64 [Q, T], identical to the single-device result.  distance, float_path: as attack.pair_ball_counts_rows."""
+        from .attack import _check_eps_rows, _check_rows_float_path, pair_ball_counts_rows
+        if eps is None:
+            raise ValueError("needs eps")
+        _check_rows_float_path(float_path)
+        if distance not in ("l2", "l2-lpips"):
+            raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+        e32 = _check_eps_rows(eps, len(queries) if hasattr(queries, "__len__") else None)
+
+        def job(prepared, shard, ctx, reduce_fn, model, lo, fpath, layout):
+            return pair_ball_counts_rows(prepared, shard, e32, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, lpips=model,
+                                         index_base=lo, float_path=fpath, _layout=layout)
+
+        return self._pair_rows_job(queries, make_generator, z, bank, batch_size, weights, distance, make_lpips, float_path, generate_kwargs,
+                                   lambda n_eff: None, job)
+
     def nearest_neighbours(self, queries, make_generator=None, z=None, bank=None, k=None, batch_size=64, weights=None, distance="l2-lpips",
                            make_lpips=None, float_path=None, **generate_kwargs):
         """attack.nearest_neighbours over the group's contexts: rank r keeps the k nearest rows of [bounds[r], bounds[r+1]) of the bank
@@ -656,6 +733,37 @@ def pair_distance_quantiles_on_devices(queries, make_generator=None, z=None, dev
     with DeviceGroup(devices) as group:
         return group.pair_distance_quantiles(queries, make_generator, z, bank, quantiles, batch_size, weights, distance, make_lpips, float_path,
                                              **generate_kwargs)
+
+
+def pair_kth_distances_on_devices(queries, make_generator=None, z=None, devices=None, k=None, batch_size=64, weights=None, bank=None,
+                                  distance="l2-lpips", make_lpips=None, float_path=None, **generate_kwargs):
+    """attack.pair_kth_distances sharded over a DeviceGroup built for the call (arguments as attack_on_devices; distance and float_path as
+    attack.pair_kth_distances): (dist float32 [Q, len(k)], key int64 [Q, len(k)], passes), identical to the single-device result."""
+    from .attack import _check_kth, _check_rows_float_path
+    if k is None:
+        raise ValueError("needs k")
+    _check_kth(k)                            # before any Context
+    _check_rows_float_path(float_path)
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    with DeviceGroup(devices) as group:
+        return group.pair_kth_distances(queries, make_generator, z, bank, k, batch_size, weights, distance, make_lpips, float_path, **generate_kwargs)
+
+
+def pair_ball_counts_rows_on_devices(queries, make_generator=None, z=None, devices=None, eps=None, batch_size=64, weights=None, bank=None,
+                                     distance="l2-lpips", make_lpips=None, float_path=None, **generate_kwargs):
+    """attack.pair_ball_counts_rows sharded over a DeviceGroup built for the call (arguments as attack_on_devices; distance and float_path as
+    attack.pair_ball_counts_rows): int64 [Q, T], identical to the single-device counts."""
+    from .attack import _check_eps_rows, _check_rows_float_path
+    if eps is None:
+        raise ValueError("needs eps")
+    _check_eps_rows(eps, len(queries) if hasattr(queries, "__len__") else None)      # before any Context
+    _check_rows_float_path(float_path)
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    with DeviceGroup(devices) as group:
+        return group.pair_ball_counts_rows(queries, make_generator, z, bank, eps, batch_size, weights, distance, make_lpips, float_path,
+                                           **generate_kwargs)
 
 
 def nearest_neighbours_on_devices(queries, make_generator=None, z=None, devices=None, k=None, batch_size=64, weights=None, bank=None,

@@ -255,6 +255,17 @@ int gl_l2_topk_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, int64_t i
                    uint64_t *topk_keys_dev);
 int gl_l2_count_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const float *thr_host,
                     int n_thr, uint64_t *counts_dev);
+/* gl_l2_count_f32 with thresholds PER QUERY, on the uint32 pattern of D32:
+ *     counts_dev[q * n_thr + t] += #{ n in [0, n_rows) : bits(D32(q, n)) <= thr_dev[q][t] }.
+ * thr_dev: [nq][n_thr] int64 in DEVICE memory, 8-byte aligned, n_thr in 1..GL_COUNT_MAX_T, ascending within each row (the caller's contract,
+ * as for gl_l2_count_rows_i8); a negative value counts nothing, a value >= 0x7F800000 (+inf) every pair whose D32 is not NaN; NaN patterns
+ * exceed every bound, as a float compare would have it.  D32 >= +0, so the compare of the patterns is the float32 compare
+ * D32 <= float(thr) of mean((y - x)**2) (attack_models/utils.py:163): one radius per query (a k-NN density score), and under a host search
+ * over these counts the exact k-th smallest D32 per query for any k (custom_knn, attack_models/fbb.py:73-88, beyond GL_TOPK_MAX).  Sizes,
+ * alignment and NULL checks of gl_l2_count_f32; n_rows == 0 or nq == 0 is GL_OK and touches nothing.  One kernel (the K loop of
+ * gl_l2_knn_f32), asynchronous; like gl_l2_count_f32 it reports under no profiling id. */
+int gl_l2_count_rows_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const int64_t *thr_dev,
+                         int n_thr, uint64_t *counts_dev);
 /* The histogram of ALL pair distances on fp32 rows: the primitive under an exact quantile of the nq x n_rows values D32(q, n) (the K loop of
  * gl_l2_knn_f32 with a binning epilogue, so D32 is the same bits again).  D32 >= +0, so the unsigned order of the uint32 patterns
  * bits(D32) is the order of the floats and a radix-select over windows of patterns finds the exact D32 at any rank.  For a window
@@ -467,6 +478,22 @@ int gl_feat_count_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *
                             uint64_t *counts_dev);
 int gl_feat_count(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev, const float *query_norm_dev,
                   int64_t nq, int64_t K, const float *thr_host, int n_thr, int col0, int pitch, uint64_t *counts_dev);
+/* The same counts with thresholds PER QUERY, on the uint32 pattern of D32 (D32 >= +0: the unsigned order of the patterns is the order of the
+ * floats, so the compare is the float32 compare D32 <= float(thr)):
+ *     counts_dev[q * n_thr + t] += #{ n in [0, n_rows) : bits(D32(q, n)) <= thr_dev[q][t] },  t < n_thr
+ * thr_dev: [nq][n_thr] int64 in DEVICE memory, 8-byte aligned, n_thr in 1..GL_COUNT_MAX_T, ascending within each row (the caller's contract, as
+ * for gl_l2_count_rows_i8: the rows are not read on the host); a negative value counts nothing, a value >= 0x7F800000 (+inf) every pair.
+ * counts_dev [nq][n_thr] uint64 of gl_counts_init, 8-byte aligned.  The primitive under one radius per query and under the exact k-th
+ * smallest distance per query for any k under the distance fbb.main hard-wires (attack_models/fbb.py:148; custom_knn, fbb.py:73-88, beyond
+ * GL_TOPK_MAX): a host search over these counts, 16 thresholds per query and pass.  Row, norm, size and scale arguments, their checks and
+ * the choice between the three kernels as gl_feat_count_h1_scaled / gl_feat_count; n_rows == 0 or nq == 0 is GL_OK and touches nothing.
+ * One kernel (the count's main loop with gl_l2_count_rows_i8's epilogue); the counts do not depend on tile, chunking, query slicing, sharding
+ * or kernel.  Asynchronous.  Reports as GL_PROF_FEAT_COUNT. */
+int gl_feat_count_rows_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,
+                                 const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, const int64_t *thr_dev, int n_thr,
+                                 uint64_t *counts_dev);
+int gl_feat_count_rows(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev,
+                       const float *query_norm_dev, int64_t nq, int64_t K, const int64_t *thr_dev, int n_thr, uint64_t *counts_dev);
 /* The histogram of ALL pair distances under 0.2 LPIPS + L2 (the primitive under an exact quantile of the nq x n_rows values D32(q, n): the
  * percentile heuristic for the radius of the Monte-Carlo attack under the reference's fbb distance).  D32 >= +0 and never NaN, so the
  * unsigned order of the uint32 patterns bits(D32) is the order of the floats.  For a window (lo: uint32, 0 <= shift <= 31,

@@ -88,6 +88,8 @@ SIGNATURES = {
     "gl_l2_count_i8_wide": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
     "gl_l2_count_rows_i8": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
     "gl_l2_count_rows_i8_wide": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
+    "gl_l2_kde_rows_i8": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _p, _i, _p]),
+    "gl_l2_kde_rows_i8_wide": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _p, _i, _p]),
     "gl_counts_add": (_i, [_p, _p, _p, _i64, _i, _i64]),
     "gl_hist_init": (_i, [_p, _p, _i]),
     "gl_l2_hist_i8": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _i, _i, _p]),

@@ -920,6 +920,212 @@ def kth_distances(queries, bank, k, batch_size=64, ctx=None, reduce_fn=None, chu
     return _dist32(S, fq.d, fq.kind), S, passes
 
 
+GL_KDE_FRAC_BITS = 40                        # kde weights are in units of 2^-40 (csrc/gl_kde_epi.h)
+KDE_MAX_ROWS = 1 << 23                       # 2^23 weights of at most 2^40 stay below 2^64
+
+
+def kde_sums(bank, queries, S0, coef, n_rows=None, sums=None):
+    """launch the kernel-density kernel: sums DeviceArray [Q, T] (uint64), sums[q, t] += sum over n < n_rows of
+    kde_weight(S(q, n) - S0[q], coef[t]), the fixed-point weight 2^(-(S - S0) coef) in units of 2^-40 (csrc/gl_kde_epi.h: integer and
+    individually rounded fp32 operations, so the sums are a function of the multiset of S - S0 alone).  S0: int64 [Q], a host array
+    (uploaded here) or a DeviceArray (a streamed bank uploads once for all its chunks); every S(q, n) must be >= S0[q] -- a pair below
+    raises GanLeaksError and leaves the sums unspecified.  coef: 1..16 float32 values, finite, >= 0, descending.  `sums` from an earlier
+    call (another chunk of the bank) is added to; fewer than 2^23 rows may be summed per query in all (the caller's duty).  The refusals
+    of count_balls_rows: exact-integer banks only ('u8' / 'int', either norm width), both sides on one lattice and with one norm width.
+    Returns (sums, the prepared query Bank, the bank's kind).  Waits for its kernel (the library reads the flag of pairs below S0 back)."""
+    ctx = bank.ctx
+    if bank.kind not in ("u8", "int"):
+        raise _OffLattice("kernel-density sums need rows on the 8-bit or the integer lattice (exact-integer L2); this bank is %r" % (bank.kind,))
+    if not isinstance(queries, Bank):
+        queries = Bank.from_images(queries, ctx, keep_u8=True, force_kind=bank.kind, norms64=bank.wide)
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    if queries.kind != bank.kind:
+        raise _OffLattice("kernel-density sums need queries and bank on the same lattice (exact-integer L2); got %r queries, %r bank" %
+                          (queries.kind, bank.kind))
+    if queries.wide != bank.wide:
+        raise ValueError("the query Bank has %s row norms, the bank %s: prepare both with the same norms64" %
+                         ("int64" if queries.wide else "int32", "int64" if bank.wide else "int32"))
+    c32 = np.ascontiguousarray(coef, np.float32)
+    if c32.ndim != 1 or not 1 <= len(c32) <= GL_COUNT_MAX_T:
+        raise ValueError("coef must hold 1..%d values, got shape %r" % (GL_COUNT_MAX_T, c32.shape))
+    if not np.all(np.isfinite(c32)) or np.any(c32 < 0) or np.any(c32[1:] > c32[:-1]):
+        raise ValueError("coef must be finite, >= 0 and descending")
+    if isinstance(S0, DeviceArray):
+        if S0.dtype != np.dtype(np.int64) or int(np.prod(S0.shape, dtype=np.int64)) != max(queries.n, 1):
+            raise TypeError("S0 must be int64 [Q]")
+        s0_dev = S0
+    else:
+        host = np.ascontiguousarray(S0, np.int64).reshape(-1)
+        if len(host) != queries.n:
+            raise ValueError("S0 has %d entries for %d queries" % (len(host), queries.n))
+        s0_dev = ctx.to_device(host) if host.size else None
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    if sums is None:
+        sums = new_counts(ctx, queries.n, len(c32))
+    elif sums.dtype != np.dtype(np.uint64) or tuple(sums.shape) != (max(queries.n, 1), len(c32)):
+        raise ValueError("sums must be uint64 of shape %r" % ((max(queries.n, 1), len(c32)),))
+    fn = ctx.lib.gl_l2_kde_rows_i8_wide if bank.wide else ctx.lib.gl_l2_kde_rows_i8
+    check(fn(ctx.handle, _p(bank.rows_i8.ptr), _p(bank.norms.ptr), n_rows, _p(queries.rows_i8.ptr), _p(queries.norms.ptr), queries.n, bank.d,
+             _p(s0_dev.ptr if s0_dev is not None else None), c32.ctypes.data_as(_p), len(c32), _p(sums.ptr)))
+    return sums, queries, bank.kind
+
+
+def _check_bandwidths(bandwidths):
+    """bandwidths (a number or a sequence of 1..GL_COUNT_MAX_T positive finite numbers) -> float64 [T]; needs no GPU"""
+    h = np.atleast_1d(np.asarray(bandwidths, np.float64))
+    if h.ndim != 1 or not 1 <= len(h) <= GL_COUNT_MAX_T:
+        raise ValueError("bandwidths must hold 1..%d values, got shape %r" % (GL_COUNT_MAX_T, h.shape))
+    if not np.all(np.isfinite(h)) or np.any(h <= 0):
+        raise ValueError("bandwidths must be positive and finite, got %r" % (h.tolist(),))
+    return h
+
+
+def kde_units(d, kind):
+    """S per unit of the distance attack() reports for the exact S: dist = S / kde_units (65025 d / 4 for 8-bit images, d for integer
+    tables; the map of eps_to_ssd / _dist32, in float64)"""
+    return float(d) if kind == "int" else 65025.0 * float(d) / 4.0
+
+
+def kde_coef(bandwidths, d, kind):
+    """(coef float32 [T], h_eff float64 [T]) for bandwidths in units of the distance: coef = fl32(log2(e) / (h kde_units)), what the kernel
+    multiplies S - S0 with, and h_eff the bandwidth that rounded coefficient actually stands for.  ValueError where the coefficient leaves
+    the fp32 range.  Host only."""
+    h = _check_bandwidths(bandwidths)
+    unit = kde_units(d, kind)
+    with np.errstate(over="ignore", under="ignore"):
+        c32 = (np.log2(np.e) / (h * unit)).astype(np.float32)
+    if not np.all(np.isfinite(c32)) or np.any(c32 <= 0):
+        raise ValueError("bandwidths %r give coefficients outside the fp32 range for rows of %d values" % (h.tolist(), int(d)))
+    return c32, np.log2(np.e) / (c32.astype(np.float64) * unit)
+
+
+def kde_loss(W, S0, h_eff, n_eff, d, kind):
+    """the soft-min distance from the integer sums, in float64: loss[q, t] = D0[q] + h_eff[t] (ln n_eff - ln(W[q, t] 2^-40)), evaluated
+    as D0 + h_eff ln(n_eff / (W 2^-40)) -- one quotient, one logarithm -- with D0 = S0 / kde_units.  Host only."""
+    W = np.asarray(W, np.uint64).astype(np.float64)
+    D0 = np.asarray(S0, np.int64).astype(np.float64) / kde_units(d, kind)
+    h = np.asarray(h_eff, np.float64)
+    return D0[:, None] + h[None, :] * np.log(float(n_eff) / (W * 2.0 ** -GL_KDE_FRAC_BITS))     # (the scaling by 2^-40 is exact)
+
+
+def kde_scores(queries, bank, bandwidths, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0, distance="l2"):
+    """the soft-min (Gaussian-kernel density) attack on the exact L2 distance: for every query and bandwidth h
+        L_h(q) = -h ln( 1/n_eff sum_n exp(-D(q, n) / h) ),  D the 'l2' distance attack() reports,
+    the Parzen estimate behind the full-black-box score with all its terms instead of the largest.  L_h -> the nearest-sample distance
+    as h -> 0 (attack()'s score) and -> the mean distance as h -> inf; -L_h / h is the log density up to constants.  Small = member-like.
+
+    bandwidths: a float or 1..16 positive finite floats in units of D, any order; column t of the results belongs to bandwidths[t].
+    returns (loss float64 [Q, T], W uint64 [Q, T], S0 int64 [Q]): S0 the exact S of every query's nearest sample, W[q, t] the integer sum
+              of kde_weight(S(q, n) - S0[q], coef[t]) over the n_eff rows attack() searches (units of 2^-40: gl_l2_kde_rows_i8), and
+              loss = D0 + h' (ln n_eff - ln(W 2^-40)) in float64 with D0 the distance of S0 and h' the bandwidth the rounded fp32
+              coefficient stands for (kde_coef, kde_loss), so the triple is self-consistent.  W and S0 are functions of the multiset of
+              pair distances: bit-identical whatever the chunking, the bank order or the sharding.
+    Two passes over the bank: the exact nearest-neighbour search (knn_keys) for S0, then kde_sums.  A streamed bank is prepared twice
+    and a `GeneratedBank` is GENERATED TWICE.  n_eff = (N // batch_size) * batch_size unless the bank is a shard (attack()'s rule), and
+    n_eff must stay below 2^23 over all chunks and shards together (ValueError: the 64-bit sums could overflow).
+    queries, bank, batch_size, ctx, chunk_bytes, index_base: as ball_counts_rows.
+    reduce_fn: None, or a pair (reduce_min, reduce_sum) of callables for a bank that is one shard: reduce_min(keys DeviceArray [Q] uint64)
+              -> DeviceArray, the cross-shard MIN (shard.allreduce_min_keys), and reduce_sum(counts DeviceArray [Q, T] uint64) ->
+              DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts); the row count is summed through reduce_sum as well.
+    Exact-integer L2 only: rows off both lattices, LPIPS feature rows and distance='l2-lpips' raise NotImplementedError before any GPU
+    work (their distances are rounded floats; a fixed-point sum over them is a follow-up)."""
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    h = _check_bandwidths(bandwidths)        # before any Context: these checks run without a GPU
+    if distance == "l2-lpips":
+        raise NotImplementedError("kernel-density scores are built for the exact-integer L2 search (8-bit images or integer tables on both "
+                                  "sides); distance='l2-lpips' is not (its distances are rounded floats, the fixed-point sum needs an exact S)")
+    unsupported = "kernel-density scores are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError(unsupported + "got LPIPS feature rows")
+    for name, rows in (("queries", queries), ("bank", bank)):
+        if isinstance(rows, Bank):
+            off = rows.kind == "f32"
+        elif isinstance(rows, np.ndarray) or (_is_torch(rows) and rows.device.type == "cpu"):
+            off = len(rows) > 0 and np.asarray(rows[:1]).dtype.kind == "f" and host_rows_kind(rows) == "f32"
+        else:
+            off = False
+        if off:
+            raise _OffLattice(unsupported + "the %s are off both lattices" % name)
+    reduce_min, reduce_sum = reduce_fn if reduce_fn is not None else (None, None)
+    prepared = isinstance(bank, Bank)
+    generated = getattr(bank, "kind", None) == "generated"
+    if prepared or generated:
+        ctx = bank.ctx
+        base = bank.index_base
+    else:
+        base = int(index_base)
+    shard = reduce_fn is not None or base != 0
+    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_rows == 0 and reduce_fn is None:
+        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    if n_rows >= KDE_MAX_ROWS:
+        raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d given): 2^23 weights of 2^40 overflow 64 bits" % n_rows)
+    ctx = ctx or (queries.ctx if isinstance(queries, Bank) else Context.get())
+    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
+    if fq.kind == "f32":
+        raise _OffLattice(unsupported + "the queries are off both lattices")
+    c32, h_eff = kde_coef(h, fq.d, fq.kind)
+    order = np.argsort(-c32, kind="stable")                # the library sees the coefficients descending (bandwidths ascending)
+    if not prepared:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
+
+    def chunks():
+        """the prepared Banks of one pass over the local rows, with the rows of each that take part"""
+        if prepared:
+            if n_rows:
+                yield bank, n_rows
+            return
+        for lo in range(0, n_rows, step):
+            hi = min(lo + step, n_rows)
+            if generated:
+                chunk = bank.rows(lo, hi)
+            elif isinstance(bank, DeviceArray):
+                chunk = bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+            else:
+                chunk = bank[lo:hi]
+            if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
+                raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
+            try:
+                yield Bank.from_images(chunk, ctx, index_base=base + lo, force_kind=fq.kind, norms64=fq.wide), hi - lo
+            except ValueError as e:
+                raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
+
+    # the rows that take part over all shards
+    n_eff = n_rows
+    if reduce_sum is not None:
+        total = ctx.to_device(np.array([[n_rows]], np.uint64))
+        n_eff = int(reduce_sum(total).numpy()[0, 0])
+        if n_eff >= KDE_MAX_ROWS:
+            raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d over all shards)" % n_eff)
+    # pass 1: the exact nearest sample of every query
+    keys = ctx.empty((max(fq.n, 1),), np.uint64)
+    check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), fq.n))
+    for b, n in chunks():
+        if b.kind != fq.kind:
+            raise _OffLattice(unsupported + "got %r queries, %r bank" % (fq.kind, b.kind))
+        knn_keys(b, fq, n, keys=keys)
+        ctx.sync()
+    if reduce_min is not None:               # (a shard without rows takes part with empty keys)
+        keys = reduce_min(keys)
+    shift = min(32, 63 - int(65025 * fq.d).bit_length())     # gl_l2_key_shift: keys are S << shift | index
+    S0 = (keys.numpy()[:fq.n] >> np.uint64(shift)).astype(np.int64)
+    # pass 2: the weights of all rows relative to it
+    sums = new_counts(ctx, fq.n, len(c32))
+    if fq.n:
+        s0_dev = ctx.to_device(S0)
+        for b, n in chunks():
+            kde_sums(b, fq, s0_dev, c32[order], n, sums)
+        ctx.sync()                           # s0_dev is released on return
+    if reduce_sum is not None:
+        sums = reduce_sum(sums)
+    W = np.empty((fq.n, len(c32)), np.uint64)
+    W[:, order] = sums.numpy()[:fq.n]
+    return kde_loss(W, S0, h_eff, n_eff, fq.d, fq.kind), W, S0
+
+
 def density_ratio_loss(S_syn, S_ref):
     """the log density ratio of the calibrated k-NN attack from the exact k-th neighbour S under the synthetic bank and under a reference
     set: 0.5 * (ln max(S_syn, 1) - ln max(S_ref, 1)) in float64 = ln(r_syn / r_ref) with r the k-NN radius -- the k-NN density is

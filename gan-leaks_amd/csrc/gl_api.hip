@@ -143,6 +143,7 @@ int gl_ctx_create(int device, gl_ctx **out_ctx)
     GL_HIP(hipMemsetAsync(c->zero_page, 0, 4096, c->stream));
     GL_HIP(hipMalloc((void **)&c->h3_sat, 64));
     GL_HIP(hipMemsetAsync(c->h3_sat, 0, 64, c->stream));
+    c->kde_flag = c->h3_sat + 8;
     GL_HIP(hipStreamSynchronize(c->stream));
     *out_ctx = c;
     return GL_OK;

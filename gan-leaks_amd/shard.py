@@ -400,6 +400,46 @@ class DeviceGroup:
 
         return self._run(queries, make_generator, z, bank, "l2", batch_size, None, weights, generate_kwargs, validate, reduce_fn_for, call)
 
+    def kde_scores(self, queries, make_generator=None, z=None, bank=None, bandwidths=None, batch_size=64, weights=None, **generate_kwargs):
+        """attack.kde_scores over the group's contexts: rank r searches and sums over rows [bounds[r], bounds[r+1]) of the bank (handed over
+        or generated, as in attack_on_devices; a generated shard is generated twice); the keys of the nearest-sample pass are min-reduced
+        as attack()'s are, the [Q, T] sums of the second pass are summed across the ranks (allreduce_sum_counts, or on the host where RCCL
+        cannot form the communicator), so every rank weighs its rows against the same S0.  (loss float64 [Q, T], W uint64 [Q, T],
+        S0 int64 [Q]), identical to the single-device result bit for bit.  The bandwidths and n_eff < 2^23 are checked before any rank
+        starts; rows off both lattices (or on different ones) raise NotImplementedError on the host, before any context works; the group
+        stays usable."""
+        from ._lib import DeviceArray
+        from .attack import KDE_MAX_ROWS, _OffLattice, _check_bandwidths, host_rows_kind, kde_scores
+        if bandwidths is None:
+            raise ValueError("needs bandwidths")
+        h = _check_bandwidths(bandwidths)
+        if getattr(queries, "kind", None) not in ("feat", "u8", "int", "f32"):           # (prepared rows: _run's TypeError)
+            kb = "u8"
+            if bank is not None:
+                rows = bank.numpy() if isinstance(bank, DeviceArray) else bank
+                kb = host_rows_kind(rows[:(len(rows) // int(batch_size)) * int(batch_size)])
+            kq = host_rows_kind(queries)
+            if kb == "f32" or kq != kb:
+                raise _OffLattice("kernel-density scores are built for the exact-integer L2 search (8-bit images or integer tables on both "
+                                  "sides); got %r queries, %r bank rows" % (kq, kb))
+
+        def validate(n_eff):
+            if n_eff >= KDE_MAX_ROWS:
+                raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d given)" % n_eff)
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            if comms is not None:
+                return comms[rank].allreduce_min_keys, (lambda counts: allreduce_sum_counts(counts, comm=comms[rank]))
+            if self.world == 1:
+                return None
+            return (lambda keys: ctx.to_device(host.merge(rank, keys.numpy())),
+                    lambda counts: ctx.to_device(host.merge(rank, counts.numpy(), op="sum")))
+
+        def call(prepared, shard, ctx, reduce_fn, model, lo):
+            return kde_scores(prepared, shard, h, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, index_base=lo)
+
+        return self._run(queries, make_generator, z, bank, "l2", batch_size, None, weights, generate_kwargs, validate, reduce_fn_for, call)
+
     def pair_distance_quantiles(self, queries, make_generator=None, z=None, bank=None, quantiles=None, batch_size=64, weights=None,
                                 distance="l2-lpips", make_lpips=None, float_path=None, **generate_kwargs):
         """attack.pair_distance_quantiles over the group's contexts, on ball_counts' runner: rank r bins the pairs of rows
@@ -717,6 +757,18 @@ def kth_distances_on_devices(queries, make_generator=None, z=None, devices=None,
     _check_kth(k)                            # before any Context
     with DeviceGroup(devices) as group:
         return group.kth_distances(queries, make_generator, z, bank, k, batch_size, weights, **generate_kwargs)
+
+
+def kde_scores_on_devices(queries, make_generator=None, z=None, devices=None, bandwidths=None, batch_size=64, weights=None, bank=None,
+                          **generate_kwargs):
+    """attack.kde_scores sharded over a DeviceGroup built for the call (arguments as attack_on_devices):
+    (loss float64 [Q, T], W uint64 [Q, T], S0 int64 [Q]), identical to the single-device result."""
+    from .attack import _check_bandwidths
+    if bandwidths is None:
+        raise ValueError("needs bandwidths")
+    _check_bandwidths(bandwidths)            # before any Context
+    with DeviceGroup(devices) as group:
+        return group.kde_scores(queries, make_generator, z, bank, bandwidths, batch_size, weights, **generate_kwargs)
 
 
 def pair_distance_quantiles_on_devices(queries, make_generator=None, z=None, devices=None, quantiles=None, batch_size=64, weights=None, bank=None,

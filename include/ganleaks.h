@@ -205,6 +205,38 @@ int gl_l2_count_rows_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *b
 /* the same for rows prepared by gl_l2_prepare_wide (int64 norms); equal to gl_l2_count_rows_i8 wherever both apply */
 int gl_l2_count_rows_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
                              const int64_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *thr_dev, int n_thr, uint64_t *counts_dev);
+/* ---- kernel-density (soft-min) sums under the same exact distance: the Parzen estimate P(x|G) ~ 1/n sum_i phi(x, G(z_i)) behind the
+ * full-black-box score (attack_models/fbb.py:73-88 keeps its largest term, the nearest sample) with a Gaussian kernel, for n_coef
+ * bandwidths in one pass over the bank:
+ *     sums[q][t] += sum over n in [0, n_rows) of kde_weight(S(q, n) - S0[q], coef[t]),  S as in gl_l2_knn_i8.
+ * kde_weight(delta, c) is a fixed-point stand-in for 2^(-delta c) in units of 2^-40, defined once in csrc/gl_kde_epi.h (gl_kde_weight) from
+ * integer operations and individually rounded fp32 multiplies and adds: x = fl32(fl32(delta) c); 0 for x >= 41; else with n = floor(x),
+ * f = x - n the truncation of p(f) 2^(40 - n), p a degree-6 polynomial for 2^-f with p(0) = 1.  kde_weight(0, c) == 2^40 exactly and no
+ * weight is larger.  Accuracy against 2^(-delta c): the truncation costs at most one unit of 2^-40, on top of a relative error of at most
+ * 2 x 2^-24 ln 2 (the two fp32 roundings behind x; 3.3e-6 at x = 40) plus the polynomial's 1.9e-7.  Measured (tests/test_kde_cpu.py): 4.4e-7
+ * relative for x <= 8, and 9.77e-4 = 2^-10 relative over all weights of at least 2^-30, where the truncation dominates.
+ * S0_dev: [nq] int64 in DEVICE memory, 8-byte aligned, the offset of every query -- the exact S of its nearest row over everything that
+ *   will be summed (chunks and shards together), so that the largest weight is 2^40.  A pair with S < S0[q] is the caller's error: the
+ *   kernel raises a device flag, the call returns GL_ERR_INVALID with the reason in gl_last_error(), and the sums of that call are
+ *   unspecified (nothing is clamped); the flag is cleared, the context stays usable.
+ * coef_host: n_coef (1..GL_COUNT_MAX_T) fp32 values in HOST memory, finite, >= 0, descending (bandwidths ascending); for the bandwidth h in
+ *   units of the distance D = S / s_unit, coef = log2(e) / (h s_unit).  coef = 0 gives 2^40 per pair.
+ * sums_dev: [nq][n_coef] uint64 (gl_counts_init); accumulated into with 64-bit integer adds only, so a streamed bank adds up chunk by
+ *   chunk, shards are summed with gl_counts_add, and the result is a function of the multiset of S - S0 alone: it does not depend on tile,
+ *   chunking, query slicing, bank order or sharding.  No overflow while fewer than 2^23 rows are summed per query (2^23 2^40 < 2^64): the
+ *   caller's duty.
+ * The kernels and the tile rule of gl_l2_count_rows_i8 (the same K loops) with another epilogue: one compare per pair against
+ * S0[q] + cut(coef[n_coef - 1]) (gl_kde_cut: from there on every weight is 0), workgroups and waves without a pair inside leave; the others
+ * reduce per (query, t) in registers, across lanes, through a 64-bit LDS table, and add one value per non-zero entry and workgroup.  Sizes,
+ * alignment and NULL checks as gl_l2_count_rows_i8; n_rows == 0 or nq == 0 is GL_OK and touches nothing.  One kernel, no workspace, no
+ * pairwise value is written to memory.  Profiled under GL_PROF_L2_COUNT.  Synchronises: the flag is read back before the call returns. */
+int gl_l2_kde_rows_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
+                      const int32_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *S0_dev, const float *coef_host, int n_coef,
+                      uint64_t *sums_dev);
+/* the same for rows prepared by gl_l2_prepare_wide (int64 norms); equal to gl_l2_kde_rows_i8 wherever both apply */
+int gl_l2_kde_rows_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
+                           const int64_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *S0_dev, const float *coef_host, int n_coef,
+                           uint64_t *sums_dev);
 /* dst[q][t] += sum over l < n_lists of src[l][q][t]; src_dev is [n_lists][nq][n_thr] (e.g. what gl_allgather_rows delivers from the ranks of a
  * sharded bank): the cross-shard sum, the counterpart of gl_topk_merge. */
 int gl_counts_add(gl_ctx *ctx, uint64_t *dst_dev, const uint64_t *src_dev, int64_t nq, int n_thr, int64_t n_lists);

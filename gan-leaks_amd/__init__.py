@@ -18,3 +18,4 @@ from .attack import Bank, GeneratedBank, attack, ball_counts, distance_quantiles
 from .attack import ball_counts_rows, count_balls_rows, eps_to_ssd_rows, kth_distances, select_kth_rows  # noqa: F401
 from .attack import count_balls_rows_f32, density_ratio_loss, density_ratio_loss_f32, eps_rows_to_bits, pair_ball_counts_rows, pair_kth_distances  # noqa: F401
 from .attack import kde_coef, kde_loss, kde_scores, kde_sums  # noqa: F401
+from .attack import kde_cut_bits_rows, kde_sums_f32, pair_kde_scores  # noqa: F401

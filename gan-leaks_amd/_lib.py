@@ -90,6 +90,7 @@ SIGNATURES = {
     "gl_l2_count_rows_i8_wide": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
     "gl_l2_kde_rows_i8": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _p, _i, _p]),
     "gl_l2_kde_rows_i8_wide": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _p, _i, _p]),
+    "gl_kde_cut_bits_rows": (_i, [_p, _i64, ctypes.c_float, _p]),
     "gl_counts_add": (_i, [_p, _p, _p, _i64, _i, _i64]),
     "gl_hist_init": (_i, [_p, _p, _i]),
     "gl_l2_hist_i8": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _i64, _i, _i, _p]),
@@ -99,6 +100,7 @@ SIGNATURES = {
     "gl_l2_topk_f32": (_i, [_p, _p, _i64, _i64, _p, _i64, _i64, _i, _p]),
     "gl_l2_count_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p, _i, _p]),
     "gl_l2_count_rows_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p, _i, _p]),
+    "gl_l2_kde_rows_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p, _p, _p, _i, _p]),
     "gl_l2_hist_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, ctypes.c_uint32, _i, _i, _p]),
     "gl_keys_unpack_f32": (_i, [_p, _p, _i64, _p, _p]),
     "gl_l2_rows_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p]),
@@ -159,6 +161,8 @@ SIGNATURES = {
     "gl_feat_count": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _i, _i, _p]),
     "gl_feat_count_rows_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _i, _p]),
     "gl_feat_count_rows": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _i, _p]),
+    "gl_feat_kde_rows_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _p, _p, _i, _p]),
+    "gl_feat_kde_rows": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, _p, _p, _p, _i, _p]),
     "gl_feat_hist_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, ctypes.c_uint32, _i, _i, _p]),
     "gl_feat_hist": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_uint32, _i, _i, _p]),
     "gl_feat_pair_dist_h1_scaled": (_i, [_p, _p, _p, _i64, _p, _p, _i64, _i64, ctypes.c_float, _p, _i64]),

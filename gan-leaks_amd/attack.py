@@ -16,7 +16,7 @@ import ctypes
 
 import numpy as np
 
-from ._lib import Context, DeviceArray, as_device, check
+from ._lib import Context, DeviceArray, as_device, check, load
 
 _p = ctypes.c_void_p
 
@@ -983,7 +983,10 @@ def _check_bandwidths(bandwidths):
 
 def kde_units(d, kind):
     """S per unit of the distance attack() reports for the exact S: dist = S / kde_units (65025 d / 4 for 8-bit images, d for integer
-    tables; the map of eps_to_ssd / _dist32, in float64)"""
+    tables; the map of eps_to_ssd / _dist32, in float64).  On the float paths (kind 'f32': fp32 rows, 'feat': 0.2 LPIPS + L2) the kernels
+    weigh the reported float32 distance itself: the unit is 1, whatever d."""
+    if kind in ("f32", "feat"):
+        return 1.0
     return float(d) if kind == "int" else 65025.0 * float(d) / 4.0
 
 
@@ -1002,9 +1005,13 @@ def kde_coef(bandwidths, d, kind):
 
 def kde_loss(W, S0, h_eff, n_eff, d, kind):
     """the soft-min distance from the integer sums, in float64: loss[q, t] = D0[q] + h_eff[t] (ln n_eff - ln(W[q, t] 2^-40)), evaluated
-    as D0 + h_eff ln(n_eff / (W 2^-40)) -- one quotient, one logarithm -- with D0 = S0 / kde_units.  Host only."""
+    as D0 + h_eff ln(n_eff / (W 2^-40)) -- one quotient, one logarithm -- with D0 = S0 / kde_units (kind 'f32' / 'feat': S0 is the float32
+    nearest distance D0 and is taken as it is, in float64).  Host only."""
     W = np.asarray(W, np.uint64).astype(np.float64)
-    D0 = np.asarray(S0, np.int64).astype(np.float64) / kde_units(d, kind)
+    if kind in ("f32", "feat"):              # the float paths: S0 is the float32 nearest distance D0 itself
+        D0 = np.asarray(S0, np.float32).astype(np.float64)
+    else:
+        D0 = np.asarray(S0, np.int64).astype(np.float64) / kde_units(d, kind)
     h = np.asarray(h_eff, np.float64)
     return D0[:, None] + h[None, :] * np.log(float(n_eff) / (W * 2.0 ** -GL_KDE_FRAC_BITS))     # (the scaling by 2^-40 is exact)
 
@@ -1029,7 +1036,7 @@ def kde_scores(queries, bank, bandwidths, batch_size=64, ctx=None, reduce_fn=Non
               -> DeviceArray, the cross-shard MIN (shard.allreduce_min_keys), and reduce_sum(counts DeviceArray [Q, T] uint64) ->
               DeviceArray, the cross-shard SUM (shard.allreduce_sum_counts); the row count is summed through reduce_sum as well.
     Exact-integer L2 only: rows off both lattices, LPIPS feature rows and distance='l2-lpips' raise NotImplementedError before any GPU
-    work (their distances are rounded floats; a fixed-point sum over them is a follow-up)."""
+    work (their distances are rounded floats: pair_kde_scores weighs those)."""
     if distance not in ("l2", "l2-lpips"):
         raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
     h = _check_bandwidths(bandwidths)        # before any Context: these checks run without a GPU
@@ -2011,10 +2018,37 @@ def count_balls_rows_f32(bank, queries, thr, n_rows=None, counts=None):
     return counts
 
 
-def _pair_rows_counter_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
-    """the per-query counts on fp32 rows: _pair_quantiles_f32's rows, chunks and n_eff.  Returns (ctx, nq, n_rows, count_pass) with
-    count_pass(thr int64 [Q, T] on patterns, rows ascending) -> int64 [Q, T], summed over the chunks and -- through reduce_fn -- the shards.
-    A bank of one chunk is uploaded once, a longer one once per pass."""
+def _slice_rows(arr, a, b):
+    """rows [a, b) of a DeviceArray whose first axis runs over the queries"""
+    rest = tuple(arr.shape[1:])
+    row_bytes = arr.dtype.itemsize * int(np.prod(rest, dtype=np.int64))
+    return arr.view((b - a,) + rest, offset_bytes=a * row_bytes)
+
+
+def _count_launch_f32(b, fq, per_query, n, out):
+    count_balls_rows_f32(b, fq, per_query[0], n, out)
+
+
+def _count_launch_lpips(b, fq, per_query, n, out):
+    from . import lpips as _lp
+    _lp.feat_count_rows(b, fq, per_query[0], n, out)
+
+
+def _counter_of(ctx, nq, reduce_fn, launch, run_pass):
+    """count_pass(thr int64 [Q, T] on patterns, rows ascending) -> int64 [Q, T] on a walker's run_pass"""
+    def count_pass(thr):
+        thr = np.ascontiguousarray(thr, np.int64)
+        counts = run_pass(lambda: new_counts(ctx, nq, thr.shape[1]), [thr], launch, reduce_fn)
+        return counts.numpy()[:nq].astype(np.int64)
+    return count_pass
+
+
+def _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """one pass over the fp32 rows of a bank, whatever is reduced from the pairs: _pair_quantiles_f32's rows, chunks and n_eff.  Returns
+    (ctx, nq, n_rows, run_pass) with run_pass(new_out, per_query, launch, reduce) -> DeviceArray: new_out() makes the fresh output of the
+    pass (first axis: the queries), per_query is a list of host arrays [Q, ...] that are uploaded once for all chunks, and
+    launch(bank rows, query rows, per_query DeviceArrays, n_rows or None, out) is the per-chunk launch that adds to `out`; reduce (or
+    None) is the cross-shard reduction of the output.  A bank of one chunk is uploaded once, a longer one once per pass."""
     if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
         raise NotImplementedError("distance='l2' takes images or tables; got LPIPS feature rows")
     prepared = isinstance(bank, Bank)
@@ -2047,30 +2081,36 @@ def _pair_rows_counter_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_byte
     if resident is None and 0 < n_rows <= step:
         resident = Bank.from_images(rows(0, n_rows), ctx, index_base=base, force_kind="f32")
 
-    def count_pass(thr):
-        thr = np.ascontiguousarray(thr, np.int64)
-        counts = new_counts(ctx, fq.n, thr.shape[1])         # fresh counters per pass
+    def run_pass(new_out, per_query, launch, reduce):
+        out = new_out()                                      # fresh per pass
         if fq.n and n_rows:
-            thr_dev = ctx.to_device(thr)
+            dev = [ctx.to_device(np.ascontiguousarray(a)) for a in per_query]
             if resident is not None:
-                count_balls_rows_f32(resident, fq, thr_dev, n_rows, counts)
+                launch(resident, fq, dev, n_rows, out)
             else:
                 for r0 in range(0, n_rows, step):
                     b = Bank.from_images(rows(r0, min(r0 + step, n_rows)), ctx, index_base=base + r0, force_kind="f32")
-                    count_balls_rows_f32(b, fq, thr_dev, counts=counts)
+                    launch(b, fq, dev, None, out)
                     ctx.sync()
-            ctx.sync()                                       # thr_dev is released on return
-        if reduce_fn is not None:            # (a shard without rows takes part with zeros)
-            counts = reduce_fn(counts)
-        return counts.numpy()[:fq.n].astype(np.int64)
+            ctx.sync()                                       # the uploads are released on return
+        if reduce is not None:               # (a shard without rows takes part with an untouched output)
+            out = reduce(out)
+        return out
 
-    return ctx, fq.n, n_rows, count_pass
+    return ctx, fq.n, n_rows, run_pass
 
 
-def _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
-    """the per-query counts under 'l2-lpips': _pair_quantiles_lpips' resident / streamed decision, row preparation, query slices and single
-    row layout per call, one lpips.feat_count_rows pass per call of count_pass.  Returns (ctx, nq, n_rows, count_pass) as
-    _pair_rows_counter_f32 does."""
+def _pair_rows_counter_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """the per-query counts on fp32 rows, on _pair_rows_walker_f32.  Returns (ctx, nq, n_rows, count_pass) with count_pass(thr int64 [Q, T]
+    on patterns, rows ascending) -> int64 [Q, T], summed over the chunks and -- through reduce_fn -- the shards."""
+    ctx, nq, n_rows, run_pass = _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    return ctx, nq, n_rows, _counter_of(ctx, nq, reduce_fn, _count_launch_f32, run_pass)
+
+
+def _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
+    """one pass over the 'l2-lpips' rows of a bank, whatever is reduced from the pairs: _pair_quantiles_lpips' resident / streamed
+    decision, row preparation, query slices and single row layout per call.  Returns (ctx, nq, n_rows, run_pass) as
+    _pair_rows_walker_f32 does; the launch sees FeatureBanks, and of the per-query arrays and the output the rows of its query slice."""
     from . import lpips as _lp
     prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
     q_feat = getattr(queries, "kind", None) == "feat"
@@ -2095,20 +2135,19 @@ def _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, model, c
             fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
         nq = fq.n
 
-        def count_pass(thr):
-            thr = np.ascontiguousarray(thr, np.int64)
-            counts = new_counts(ctx, nq, thr.shape[1])           # fresh counters per pass
+        def run_pass(new_out, per_query, launch, reduce):
+            out = new_out()                                      # fresh per pass
             if nq and n_rows:
-                thr_dev = ctx.to_device(thr)
-                _lp.feat_count_rows(fb, fq, thr_dev, n_rows, counts)
-                ctx.sync()                                       # thr_dev is released on return
-            if reduce_fn is not None:
-                counts = reduce_fn(counts)
-            return counts.numpy()[:nq].astype(np.int64)
+                dev = [ctx.to_device(np.ascontiguousarray(a)) for a in per_query]
+                launch(fb, fq, dev, n_rows, out)
+                ctx.sync()                                       # the uploads are released on return
+            if reduce is not None:
+                out = reduce(out)
+            return out
     else:
         # The stream of _pair_quantiles_lpips, once per pass.  One row layout for ALL passes: 8-bit codes give lattice rows until a query
-        # slice or a bank chunk turns out to be off-lattice floats; then the pass starts over with fresh counters in the hi / lo layout,
-        # and every later pass starts there.  Nothing of an abandoned layout survives in a counter.
+        # slice or a bank chunk turns out to be off-lattice floats; then the pass starts over with a fresh output in the hi / lo layout,
+        # and every later pass starts there.  Nothing of an abandoned layout survives in an output.
         def rows(lo, hi):
             if generated:
                 return bank.rows(lo, hi)
@@ -2133,7 +2172,7 @@ def _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, model, c
                 state["fq"] = fq
             return fq
 
-        def stream(thr_dev, n_thr, counts):
+        def stream(dev, launch, out):
             """False: an off-lattice slice or chunk met lattice rows"""
             for a, b in slices:
                 if b == a:
@@ -2150,9 +2189,9 @@ def _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, model, c
                 step = max(1, int(chunk_bytes // (fq.K * (2 if fq.role else 4))))
                 if fq.role:
                     step = _lp.preferred_bank_rows(step, fq.n)
-                # the slice's rows of the thresholds and of the counters
-                thr_s = thr_dev.view((b - a, n_thr), offset_bytes=a * n_thr * 8)
-                cnt_s = counts.view((b - a, n_thr), offset_bytes=a * n_thr * 8)
+                # the slice's rows of the per-query arrays and of the output
+                dev_s = [_slice_rows(x, a, b) for x in dev]
+                out_s = _slice_rows(out, a, b)
                 buf = None
                 for r0 in range(0, n_rows, step):
                     try:
@@ -2162,27 +2201,32 @@ def _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, model, c
                         if q_feat or getattr(fq, "fmt", None) != "lattice":
                             raise
                         return False
-                    _lp.feat_count_rows(buf, fq, thr_s, counts=cnt_s)
+                    launch(buf, fq, dev_s, None, out_s)
                     ctx.sync()
             return True
 
-        def count_pass(thr):
-            thr = np.ascontiguousarray(thr, np.int64)
-            n_thr = thr.shape[1]
-            counts = new_counts(ctx, nq, n_thr)
+        def run_pass(new_out, per_query, launch, reduce):
+            out = new_out()
             if nq and n_rows:
-                thr_dev = ctx.to_device(thr)                 # once per pass, for all slices and chunks
-                if not stream(thr_dev, n_thr, counts):
+                dev = [ctx.to_device(np.ascontiguousarray(a)) for a in per_query]      # once per pass, for all slices and chunks
+                if not stream(dev, launch, out):
                     state["fmt"], state["fq"] = "hilo", None
-                    counts = new_counts(ctx, nq, n_thr)      # the counters of the abandoned layout are dropped
-                    if not stream(thr_dev, n_thr, counts):
+                    out = new_out()                          # the output of the abandoned layout is dropped
+                    if not stream(dev, launch, out):
                         raise AssertionError("unreachable")
-                ctx.sync()                                   # thr_dev is released on return
-            if reduce_fn is not None:        # (a shard without rows takes part with zeros)
-                counts = reduce_fn(counts)
-            return counts.numpy()[:nq].astype(np.int64)
+                ctx.sync()                                   # the uploads are released on return
+            if reduce is not None:           # (a shard without rows takes part with an untouched output)
+                out = reduce(out)
+            return out
 
-    return ctx, nq, n_rows, count_pass
+    return ctx, nq, n_rows, run_pass
+
+
+def _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
+    """the per-query counts under 'l2-lpips', on _pair_rows_walker_lpips: one lpips.feat_count_rows pass per call of count_pass.  Returns
+    (ctx, nq, n_rows, count_pass) as _pair_rows_counter_f32 does."""
+    ctx, nq, n_rows, run_pass = _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout)
+    return ctx, nq, n_rows, _counter_of(ctx, nq, reduce_fn, _count_launch_lpips, run_pass)
 
 
 def _pair_rows_counter(queries, bank, distance, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, layout):
@@ -2292,6 +2336,157 @@ def pair_kth_distances(queries, bank, k, distance="l2-lpips", batch_size=64, ctx
         passes += p
     key = np.stack([found[kk] for kk in ks], axis=1) if nq else np.empty((0, len(ks)), np.int64)
     return key.astype(np.uint32).view(np.float32), key, passes
+
+
+def kde_cut_bits_rows(D0, coef):
+    """gl_kde_cut_bits per query (csrc/gl_kde_epi.h, through the library's one definition): uint32 [Q], the smallest pattern from which on
+    a pair of query q weighs nothing under the coefficient `coef`; D0 float32 [Q] finite and >= 0, coef finite and >= 0.  Host only."""
+    d0 = np.ascontiguousarray(D0, np.float32).reshape(-1)
+    out = np.empty(d0.shape, np.uint32)
+    check(load().gl_kde_cut_bits_rows(d0.ctypes.data_as(_p), d0.size, float(np.float32(coef)), out.ctypes.data_as(_p)))
+    return out
+
+
+def _kde_f32_operands(ctx, nq, D0, bound, coef, sums, who):
+    """what kde_sums_f32 and lpips.feat_kde_rows check and upload: (D0 DeviceArray or None, bound DeviceArray or None, coef float32 [T],
+    sums DeviceArray [Q, T], uploaded: whether anything was uploaded here)"""
+    c32 = np.ascontiguousarray(coef, np.float32)
+    if c32.ndim != 1 or not 1 <= len(c32) <= GL_COUNT_MAX_T:
+        raise ValueError("coef must hold 1..%d values, got shape %r" % (GL_COUNT_MAX_T, c32.shape))
+    if not np.all(np.isfinite(c32)) or np.any(c32 < 0) or np.any(c32[1:] > c32[:-1]):
+        raise ValueError("coef must be finite, >= 0 and descending")
+    dev, uploaded = [], False
+    for name, arr, dtype in (("D0", D0, np.float32), ("bound", bound, np.uint32)):
+        if isinstance(arr, DeviceArray):
+            if arr.dtype != np.dtype(dtype) or int(np.prod(arr.shape, dtype=np.int64)) != nq:
+                raise TypeError("%s: %s must be %s [Q]" % (who, name, np.dtype(dtype).name))
+            dev.append(arr)
+        else:
+            host = np.ascontiguousarray(arr, dtype).reshape(-1)
+            if len(host) != nq:
+                raise ValueError("%s: %s has %d entries for %d queries" % (who, name, len(host), nq))
+            dev.append(ctx.to_device(host) if host.size else None)
+            uploaded = True
+    if sums is None:
+        sums = new_counts(ctx, nq, len(c32))
+    elif sums.dtype != np.dtype(np.uint64) or tuple(sums.shape) != (max(nq, 1), len(c32)):
+        raise ValueError("%s: sums must be uint64 of shape %r" % (who, (max(nq, 1), len(c32))))
+    return dev[0], dev[1], c32, sums, uploaded
+
+
+def kde_sums_f32(bank, queries, D0, bound, coef, n_rows=None, sums=None):
+    """kde_sums on fp32 rows: sums DeviceArray [Q, T] (uint64), sums[q, t] += sum over n < n_rows of
+    gl_kde_weight_f32(D32(q, n), D0[q], coef[t]) (gl_l2_kde_rows_f32; csrc/gl_kde_epi.h), D32 the fixed-order float32 distance of
+    knn_keys(fpath='exact').  D0: float32 [Q], the distance of every query's nearest row; bound: uint32 [Q], kde_cut_bits_rows(D0, coef[-1])
+    -- host arrays (uploaded here) or DeviceArrays (a streamed bank uploads once for all its chunks).  coef: 1..16 float32 values, finite,
+    >= 0, descending.  A pair below D0 and a NaN distance raise GanLeaksError and leave the sums unspecified; a pair at +inf weighs
+    nothing.  `sums` from an earlier call (another chunk of the bank) is added to; fewer than 2^23 rows per query in all (the caller's
+    duty).  'f32' Banks on both sides (Bank.as_f32()).  Waits for its kernel (the library reads the flag back)."""
+    ctx = bank.ctx
+    if bank.kind != "f32" or queries.kind != "f32":
+        raise ValueError("kde_sums_f32 takes 'f32' Banks (Bank.as_f32()), got %r queries, %r bank" % (queries.kind, bank.kind))
+    if queries.d != bank.d:
+        raise ValueError("query images have %d values, bank images %d" % (queries.d, bank.d))
+    d0_dev, bound_dev, c32, sums, _ = _kde_f32_operands(ctx, queries.n, D0, bound, coef, sums, "kde_sums_f32")
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    check(ctx.lib.gl_l2_kde_rows_f32(ctx.handle, _p(bank.rows_f32.ptr), n_rows, _p(queries.rows_f32.ptr), queries.n, bank.d,
+                                     _p(d0_dev.ptr if d0_dev is not None else None), _p(bound_dev.ptr if bound_dev is not None else None),
+                                     c32.ctypes.data_as(_p), len(c32), _p(sums.ptr)))
+    return sums
+
+
+def _knn_launch_f32(b, fq, per_query, n, out):
+    knn_keys(b, fq, n, keys=out, fpath="exact")
+
+
+def _knn_launch_lpips(b, fq, per_query, n, out):
+    from . import lpips as _lp
+    _lp.feat_knn_keys(b, fq, n, keys=out)
+
+
+def pair_kde_scores(queries, bank, bandwidths, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, index_base=0,
+                    float_path=None, _layout=None):
+    """kde_scores -- the soft-min (Gaussian-kernel density) attack, L_h(q) = -h ln(1/n_eff sum_n exp(-D(q, n) / h)) -- under any distance
+    and arithmetic path nearest_neighbours() searches on.  kde_scores is the older spelling and stays exact-integer only; this function is
+    the way in for 'l2-lpips' -- the distance fbb.main hard-wires, hence the default -- and for rows off both lattices.
+
+    bandwidths: a float or 1..16 positive finite floats in units of the reported distance, any order; column t belongs to bandwidths[t].
+    returns (loss float64 [Q, T], W uint64 [Q, T], key int64 [Q]): key[q] the uint32 pattern of D0[q], the float32 distance of the
+              query's nearest sample (column 0 of nearest_neighbours(..., 1)); W[q, t] the integer sum of
+              gl_kde_weight_f32(D32(q, n), D0[q], coef[t]) over the n_eff rows attack() searches, in units of 2^-40 (csrc/gl_kde_epi.h: one
+              rounded subtraction, one rounded product with coef = fl32(log2(e) / h), then kde_scores' fixed-point arithmetic); and
+              loss = D0 + h' ln(n_eff / (W 2^-40)) in float64 with h' = log2(e) / coef, the bandwidth the rounded coefficient stands for.
+              D32 of a pair is the same bits wherever the pair sits, so W and key are functions of the multiset of distances:
+              bit-identical whatever the chunking, the bank order, the query slicing or the sharding.  A pair at +inf weighs nothing.
+    distance='l2-lpips': D32 the float32 distance attack(distance='l2-lpips') minimises, bit for bit.  Accepts what pair_ball_counts_rows
+              accepts: u8 or float images, prepared FeatureBanks on either side, a GeneratedBank; banks beyond `chunk_bytes` are streamed,
+              query sets beyond the query budget go in slices, one row layout per call (both passes).
+    distance='l2': both sides on one lattice: kde_scores, unchanged (key = S0).  Otherwise float_path='exact' is needed (without it: the
+              NotImplementedError of kde_scores) and the WHOLE call runs on fp32 rows (kde_sums_f32).  A NaN distance raises GanLeaksError,
+              a query whose nearest distance is not finite ValueError.  'mfma' raises NotImplementedError, anything else ValueError.
+    TWO PASSES OVER THE BANK: the nearest-sample search for D0, then the sums (D0 and the per-query cut-offs are uploaded once for all
+    chunks).  A streamed bank is prepared -- under 'l2-lpips' featurised -- twice, and a GeneratedBank is GENERATED AND FEATURISED TWICE,
+    once more per query slice: where the rows fit, materialise them with model.features(bank, role="bank") and hand over that FeatureBank.
+    reduce_fn: None, or (reduce_min, reduce_sum) as in kde_scores (shard.allreduce_min_keys on the [Q] keys of pass 1,
+              shard.allreduce_sum_counts on the [Q, T] sums); the row count is summed through reduce_sum, and n_eff must stay below 2^23
+              over all shards (ValueError).  index_base, ctx, chunk_bytes, batch_size, n_eff: as kde_scores."""
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    h = _check_bandwidths(bandwidths)        # before any Context: these checks run without a GPU
+    float_path = _check_rows_float_path(float_path)
+    if distance == "l2" and (float_path is None or _layout != "f32"):
+        try:
+            return kde_scores(queries, bank, h, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, chunk_bytes=chunk_bytes, index_base=index_base)
+        except _OffLattice:
+            if float_path is None:
+                raise                        # nothing of the integer passes survives: the fp32 rows start over
+    reduce_min, reduce_sum = reduce_fn if reduce_fn is not None else (None, None)
+    base = getattr(bank, "index_base", None)
+    base = int(index_base) if base is None else int(base)
+    n_local = len(bank) if (reduce_fn is not None or base != 0) else (len(bank) // int(batch_size)) * int(batch_size)
+    if n_local >= KDE_MAX_ROWS:
+        raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d given): 2^23 weights of 2^40 overflow 64 bits" % n_local)
+    c32, h_eff = kde_coef(h, 1, "f32")
+    order = np.argsort(-c32, kind="stable")                # the library sees the coefficients descending (bandwidths ascending)
+    coef = np.ascontiguousarray(c32[order])
+    if distance == "l2-lpips":
+        from . import lpips as _lp
+        ctx, nq, n_rows, run_pass = _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, _layout)
+        knn_launch = _knn_launch_lpips
+
+        def kde_launch(b, fq, per_query, n, out):
+            _lp.feat_kde_rows(b, fq, per_query[0], per_query[1], coef, n, out)
+    else:
+        ctx, nq, n_rows, run_pass = _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+        knn_launch = _knn_launch_f32
+
+        def kde_launch(b, fq, per_query, n, out):
+            kde_sums_f32(b, fq, per_query[0], per_query[1], coef, n, out)
+    # the rows that take part over all shards
+    n_eff = n_rows
+    if reduce_sum is not None:
+        n_eff = int(reduce_sum(ctx.to_device(np.array([[n_rows]], np.uint64))).numpy()[0, 0])
+        if n_eff >= KDE_MAX_ROWS:
+            raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d over all shards)" % n_eff)
+
+    # pass 1: the nearest sample of every query; the key's upper half is the pattern of its float32 distance
+    def new_keys():
+        keys = ctx.empty((max(nq, 1),), np.uint64)
+        check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), nq))
+        return keys
+
+    keys = run_pass(new_keys, [], knn_launch, reduce_min)
+    key = (keys.numpy()[:nq] >> np.uint64(32)).astype(np.int64)
+    D0 = key.astype(np.uint32).view(np.float32)
+    if not np.all(np.isfinite(D0)):
+        q = int(np.argmin(np.isfinite(D0)))
+        raise ValueError("the nearest distance of query %d is %r: kernel-density scores need a finite nearest distance for every query" % (q, float(D0[q])))
+    # pass 2: the weights of all rows relative to it; nothing at or beyond the cut-off of the smallest coefficient weighs anything
+    bound = kde_cut_bits_rows(D0, coef[-1])
+    sums = run_pass(lambda: new_counts(ctx, nq, len(coef)), [D0, bound], kde_launch, reduce_sum)
+    W = np.empty((nq, len(c32)), np.uint64)
+    W[:, order] = sums.numpy()[:nq]
+    return kde_loss(W, D0, h_eff, n_eff, 1, "f32"), W, key
 
 
 def density_ratio_loss_f32(d_syn, d_ref):

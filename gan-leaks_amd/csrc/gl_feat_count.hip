@@ -28,10 +28,16 @@
 //          gl_count_epi.h's second count_epilogue (rows_args) on the uint32 pattern of D32 with s_max = 0x7F800000 (+inf): D32 >= +0 (see
 //          EPI = 2), so the unsigned compare of the patterns IS the float compare D32 <= float(thr), and a host search over integer brackets
 //          (attack.select_kth_rows) finds the exact D32 of any rank per query.  Same commuting integer adds as EPI = 0.
+// EPI = 5: sums[q][t] += sum over n < n_rows of gl_kde_weight_f32(D32(q, n), D0[q], coef[t]), the soft-min (kernel-density) sums of
+//          gl_kde.hip on the float distance, through gl_kde_epi.h's kde_epilogue_f32 on the uint32 pattern of D32: one compare per pair
+//          against its query's bound (gl_kde_cut_bits under the smallest coefficient, from device memory like D0), an LDS table, one 64-bit
+//          atomicAdd per non-zero (query, t).  The weight is a pure function of (D32, D0, coef) and D32 does not depend on where the pair
+//          sits: the sums are functions of the multiset of D32 values.  A pair below D0 raises bit 1 of the context's kde flag.
 #include "gl_conv.h"
 #include "gl_count_epi.h"
 #include "gl_feat_pair.h"
 #include "gl_hist_epi.h"
+#include "gl_kde_epi.h"
 #include "gl_pair256.h"
 #include "gl_topk_sel.h"
 #include <cmath>
@@ -60,10 +66,14 @@ template <> struct pair_sink<4> {
     gl_count::rows_args a;           // thr[nq][a.n] on the bit pattern of D32, s_max = 0x7F800000
     unsigned long long *counts;      // [nq][a.n]
 };
+template <> struct pair_sink<5> {
+    gl_kde::kde_f32_args a;          // D0[nq], bound[nq] on the bit pattern of D32, coef[a.n] descending
+    unsigned long long *sums;        // [nq][a.n]
+};
 
 // The epilogue of one tile.  acc holds the dot products of the lane's NI x 4 tiles of 16 x 16 (column = query qcol0 + j * 16 + (lane & 15) of
 // the tile, row = bank row nbase + i * 16 + r); D32 replaces them in place, so that no norm stays live next to the accumulators.
-// Every thread of the workgroup must call this (EPI = 0, EPI = 3 and EPI = 4 have barriers and use smem).
+// Every thread of the workgroup must call this (EPI = 0, EPI = 3, EPI = 4 and EPI = 5 have barriers and use smem).
 // EPI = 2: acc[i][j] is 4 consecutive bank rows (from a multiple of 4) of one query = one piece, a 16-byte store; the 16 lanes of a column
 // group are 16 consecutive queries = 256 contiguous bytes.  Pieces whose first row is past n_rows are not written; rows past n_rows inside a
 // written piece hold whatever the clamped operands gave (the selection masks n < n_rows).
@@ -98,6 +108,9 @@ __device__ __forceinline__ void finish_tile(v4f (&acc)[NI][4], const float *__re
     } else if constexpr (EPI == 4) {
         auto s_of = [&](int i, int j, int r) -> unsigned { return __float_as_uint(acc[i][j][r]); };
         gl_count::count_epilogue<NI, unsigned>(s_of, n_left, q0, qcol0, q_left, tile_q, sink.a, sink.counts, smem, lane);
+    } else if constexpr (EPI == 5) {
+        auto s_of = [&](int i, int j, int r) -> unsigned { return __float_as_uint(acc[i][j][r]); };
+        gl_kde::kde_epilogue_f32<NI>(s_of, n_left, q0, qcol0, q_left, tile_q, sink.a, sink.sums, smem, lane);
     } else if constexpr (EPI == 2) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -160,11 +173,11 @@ feat_pairs_h1_kernel(const char *__restrict__ bank, const float *__restrict__ ba
         for (int i = 0; i < 8; ++i)
 #pragma unroll
             for (int j = 0; j < 4; ++j) acc[i][j] = (v4f){0.f, 0.f, 0.f, 0.f};
-        // The binning epilogue is the one with the most live values next to the accumulators.  The lane's LDS offsets of the main loop are
+        // The binning epilogue is the one with the most live values next to the accumulators (the kernel-density one, EPI = 5, likewise).  The lane's LDS offsets of the main loop are
         // invariants of the tile loop; kept across that epilogue they are spilled and reloaded inside the K loop.  Formed per tile from a
         // copy of `lane` the compiler cannot see through, they end with the K loop (a few VALU instructions per tile).
         int mlane = lane;
-        if constexpr (EPI == 3) asm volatile("" : "+v"(mlane));
+        if constexpr (EPI == 3 || EPI == 5) asm volatile("" : "+v"(mlane));
         for (int seg = 0; seg < nseg; ++seg) {
             meet();
             if (!active) continue;
@@ -187,7 +200,7 @@ feat_pairs_h1_kernel(const char *__restrict__ bank, const float *__restrict__ ba
             }
         }
         if (!active) return;
-        if constexpr (EPI == 3) {
+        if constexpr (EPI == 3 || EPI == 5) {
             int elane = lane;                            // (as mlane: what the epilogue derives from the lane is formed after the K loop)
             asm volatile("" : "+v"(elane));
             finish_tile<EPI, 8>(acc, bank_norm, n_rows, n0 + wn * 128 + (elane >> 4) * 4, query_norm, nq, q0, wq * 64, GT, inv_s2, sink, smem, elane);
@@ -393,6 +406,34 @@ int make_rows_sink(const char *fn, const int64_t *thr_dev, int n_thr, uint64_t *
     return GL_OK;
 }
 
+// D0, bounds and coefficients of gl_feat_kde_rows*: the checks of gl_kde.hip's kde_rows_impl
+int make_kde_sink(const char *fn, gl_ctx *ctx, const float *d0_dev, const uint32_t *bound_dev, const float *coef, int n_coef, uint64_t *sums,
+                  bool need_ptrs, pair_sink<5> &s)
+{
+    static_assert(gl_kde::KDE_F32_LDS_BYTES <= 4 * GOPER && gl_kde::KDE_F32_LDS_BYTES <= 4 * FOPER, "sums, D0 and bounds must fit the slice buffers");
+    static_assert(GT <= 256 && FT <= 256, "the LDS layout of kde_epilogue_f32 holds 256 queries");
+    GL_REQUIRE(n_coef >= 1 && n_coef <= GL_COUNT_MAX_T, "%s: n_coef=%d outside [1, %d]", fn, n_coef, GL_COUNT_MAX_T);
+    GL_REQUIRE(coef, "%s: NULL coefficients", fn);
+    for (int t = 0; t < GL_COUNT_MAX_T; ++t) s.a.coef[t] = 0.0f;
+    for (int t = 0; t < n_coef; ++t) {
+        GL_REQUIRE(coef[t] >= 0.0f && coef[t] <= 3.402823466e38f, "%s: coef[%d] is not a finite value >= 0", fn, t);
+        GL_REQUIRE(t == 0 || coef[t] <= coef[t - 1], "%s: the coefficients must be descending (coef[%d] > coef[%d])", fn, t, t - 1);
+        s.a.coef[t] = coef[t];
+    }
+    if (need_ptrs) {
+        GL_REQUIRE(d0_dev && bound_dev, "%s: NULL offsets or bounds", fn);
+        GL_REQUIRE(((reinterpret_cast<uintptr_t>(d0_dev) | reinterpret_cast<uintptr_t>(bound_dev)) & 3) == 0, "%s: offsets and bounds must be 4-byte aligned", fn);
+        GL_REQUIRE(sums, "%s: NULL sums", fn);
+        GL_REQUIRE((reinterpret_cast<uintptr_t>(sums) & 7) == 0, "%s: the sums must be 8-byte aligned", fn);
+    }
+    s.a.d0 = d0_dev;
+    s.a.bound = bound_dev;
+    s.a.flag = ctx->kde_flag;
+    s.a.n = n_coef;
+    s.sums = reinterpret_cast<unsigned long long *>(sums);
+    return GL_OK;
+}
+
 // the dispatch of gl_feat_knn_h1_scaled: clusters on a whole MI355X, the cluster-free persistent form on a device with fewer compute units
 // (tuning builds: GL_PAIR_VARIANT=5 forces the latter).  Either way the same bits.
 bool h1_clustered(const gl_ctx *ctx, int64_t K1)
@@ -562,6 +603,34 @@ int gl_feat_count_rows(gl_ctx *ctx, const float *bank_V_dev, const float *bank_n
     if (const int rc = make_rows_sink(fn, thr_dev, n_thr, counts_dev, n_rows > 0 && nq > 0, sink)) return rc;
     if (n_rows == 0 || nq == 0) return GL_OK;
     return launch_split<4>(ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, sink);
+}
+
+int gl_feat_kde_rows_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,
+                               const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, const float *D0_dev, const uint32_t *bound_dev,
+                               const float *coef_host, int n_coef, uint64_t *sums_dev)
+{
+    static const char *fn = "gl_feat_kde_rows_h1_scaled";
+    gl_make_current(ctx);
+    pair_sink<5> sink;
+    if (const int rc = check_rows(fn, ctx, bank_V16_dev, bank_norm_dev, n_rows, query_V16_dev, query_norm_dev, nq, K1, 64)) return rc;
+    if (const int rc = make_kde_sink(fn, ctx, D0_dev, bound_dev, coef_host, n_coef, sums_dev, n_rows > 0 && nq > 0, sink)) return rc;
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    if (const int rc = launch_h1<5>(fn, ctx, bank_V16_dev, bank_norm_dev, n_rows, query_V16_dev, query_norm_dev, nq, K1, row_scale, sink)) return rc;
+    return gl_kde_flag_check(fn, ctx);
+}
+
+int gl_feat_kde_rows(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev,
+                     const float *query_norm_dev, int64_t nq, int64_t K, const float *D0_dev, const uint32_t *bound_dev, const float *coef_host,
+                     int n_coef, uint64_t *sums_dev)
+{
+    static const char *fn = "gl_feat_kde_rows";
+    gl_make_current(ctx);
+    pair_sink<5> sink;
+    if (const int rc = check_rows(fn, ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, 32)) return rc;
+    if (const int rc = make_kde_sink(fn, ctx, D0_dev, bound_dev, coef_host, n_coef, sums_dev, n_rows > 0 && nq > 0, sink)) return rc;
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    if (const int rc = launch_split<5>(ctx, bank_V_dev, bank_norm_dev, n_rows, query_V_dev, query_norm_dev, nq, K, sink)) return rc;
+    return gl_kde_flag_check(fn, ctx);
 }
 
 int gl_feat_hist_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,

@@ -141,4 +141,15 @@ int gl_l2_kde_rows_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t
                                   coef_host, n_coef, sums_dev);
 }
 
+int gl_kde_cut_bits_rows(const float *D0, int64_t n, float c, uint32_t *out)
+{
+    GL_REQUIRE(n >= 0 && (n == 0 || (D0 && out)), "gl_kde_cut_bits_rows: bad arguments");
+    GL_REQUIRE(c >= 0.0f && c <= 3.402823466e38f, "gl_kde_cut_bits_rows: the coefficient is not a finite value >= 0");
+    for (int64_t i = 0; i < n; ++i) {
+        GL_REQUIRE(D0[i] >= 0.0f && D0[i] <= 3.402823466e38f, "gl_kde_cut_bits_rows: D0[%lld] is not a finite value >= 0", (long long)i);
+        out[i] = gl_kde_cut_bits(D0[i], c);
+    }
+    return GL_OK;
+}
+
 }  // extern "C"

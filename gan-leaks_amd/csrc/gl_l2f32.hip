@@ -14,6 +14,7 @@
 // K slices of 32 floats staged through LDS (row stride 36 floats: conflict-free float4 reads).
 #include "gl_count_epi.h"
 #include "gl_hist_epi.h"
+#include "gl_kde_epi.h"
 #include "gl_topk_sel.h"
 #include <cmath>
 
@@ -56,6 +57,10 @@ template <> struct f32_sink<3> {
 template <> struct f32_sink<4> {
     gl_count::rows_args a;           // thr[nq][a.n] on the bit pattern of D32, s_max = 0x7F800000 (+inf)
     unsigned long long *counts;      // [nq][a.n]
+};
+template <> struct f32_sink<5> {
+    gl_kde::kde_f32_args a;          // D0[nq], bound[nq] on the bit pattern of D32, coef[a.n] descending
+    unsigned long long *sums;        // [nq][a.n]
 };
 
 // The K loop of one 64 x 64 tile, shared by every epilogue: dist[a][b] = D32(query q0 + tq * 4 + a, bank row n0 + tn + 16 * b), the chain of
@@ -139,6 +144,14 @@ __device__ __forceinline__ void pair_tile_f32(const float *__restrict__ bank, in
 //        it holds nothing within (a query lives in one wave: no barrier is needed for that), so tiles without a hit cost one compare per
 //        pair; the others count per bound, fold with two shuffles and add ONE value per non-zero (query, t) with a 64-bit atomicAdd.
 //        Queries beyond nq get the bound 0, which nothing meets.
+// EPI 5: sums[q][t] += sum over n of gl_kde_weight_f32(D32(q, n), D0[q], coef[t]) (gl_kde_epi.h), the soft-min sums of gl_kde.hip on this
+//        distance, in EPI 4's shape: the tile reduced to one bit right behind the K loop (here: "holds a pattern that is not NaN" -- padding
+//        gives finite distances, so a tile without one consists of real NaN pairs and raises the NaN bit of the flag), then turned through
+//        LDS as patterns, masked pairs as +inf, which lies at or above every bound and weighs nothing.  D0 and the bound of the query
+//        (gl_kde_cut_bits under the smallest coefficient) are read after the K loop; a pattern above +inf raises the NaN bit, one below
+//        bits(D0) the below-offset bit.  A wave without a pattern below a bound leaves; the others form D32 - D0 once per pair, sum the
+//        weights per coefficient, fold with two 64-bit shuffles and add ONE value per non-zero (query, t) with a 64-bit atomicAdd (a query
+//        lives in one wave: no LDS table).  Integer adds of a pure function of (D32, D0, coef): nothing depends on tile, chunk or shard.
 template <int EPI>
 __global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__restrict__ bank, int64_t n_rows, const float *__restrict__ query, int64_t nq,
                                                                 int64_t d, int q_tiles, const f32_sink<EPI> sink)
@@ -174,7 +187,7 @@ __global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__re
     } else {
         const int n_left = gl_count::rows_left(n_rows, n0), q_left = gl_count::rows_left(nq, q0);
         unsigned valid = 0;                           // bit a * 4 + b: the pair is a real one
-        if constexpr (EPI != 4) {
+        if constexpr (EPI != 4 && EPI != 5) {
 #pragma unroll
             for (int a = 0; a < 4; ++a)
 #pragma unroll
@@ -274,6 +287,69 @@ __global__ void __launch_bounds__(THREADS) l2_pairs_f32_kernel(const float *__re
                 c += __shfl_xor(c, 1, 64);
                 c += __shfl_xor(c, 2, 64);
                 if (part == 0 && c != 0u) atomicAdd(&sink.counts[(q0 + ql) * n_thr + t], (unsigned long long)c);
+            }
+        } else if constexpr (EPI == 5) {
+            int alive = 0;
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b) alive |= __float_as_uint(dist[a][b]) <= 0x7F800000u ? 1 : 0;
+            if (!__syncthreads_or(alive)) {
+                if (tid == 0) atomicOr(sink.a.flag, gl_kde::KDE_FLAG_NAN);     // nothing but NaN: no padded pair among them, all are real
+                return;
+            }
+            int etid = tid;                                         // (the opaque copy: see EPI 4)
+            asm volatile("" : "+v"(etid));
+            const int etq = etid >> 4, etn = etid & 15;
+
+            constexpr int TS = TN + 4;
+            static_assert(TQ * TS + GL_COUNT_MAX_T <= (TQ + TN) * LDS_STRIDE, "the turned tile and the coefficients must fit the slice buffers");
+            unsigned *turn = reinterpret_cast<unsigned *>(smem);   // [TQ][TS]
+            float *coef = smem + TQ * TS;                           // a run-time index into kernel arguments would cost registers
+#pragma unroll
+            for (int a = 0; a < 4; ++a)
+#pragma unroll
+                for (int b = 0; b < 4; ++b)
+                    turn[(etq * 4 + a) * TS + etn + 16 * b] =
+                        (etq * 4 + a < q_left && etn + 16 * b < n_left) ? __float_as_uint(dist[a][b]) : 0x7F800000u;
+            if (etid == 0) {
+#pragma unroll
+                for (int t = 0; t < GL_COUNT_MAX_T; ++t) coef[t] = sink.a.coef[t];
+            }
+            __syncthreads();
+            const int ql = etid >> 2, part = etid & 3;
+            uint4 v[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) v[i] = *reinterpret_cast<const uint4 *>(&turn[ql * TS + part * 16 + i * 4]);
+            // D0 and the bound of the lane's query, here and not before: neither is live in the K loop
+            const float d0 = ql < q_left ? sink.a.d0[q0 + ql] : 0.0f;
+            const unsigned top = ql < q_left ? sink.a.bound[q0 + ql] : 0u;
+            const unsigned b0 = __float_as_uint(d0);
+            float delta[16];                                        // D32 - D0 of the pairs that take part
+            unsigned in = 0;                                        // bit k: pair k takes part
+            int bad = 0;
+#pragma unroll
+            for (int k = 0; k < 16; ++k) {
+                const uint4 &p = v[k >> 2];
+                const unsigned s = (k & 3) == 0 ? p.x : ((k & 3) == 1 ? p.y : ((k & 3) == 2 ? p.z : p.w));
+                if (s > 0x7F800000u) bad |= gl_kde::KDE_FLAG_NAN;
+                if (s < top && s < b0) bad |= gl_kde::KDE_FLAG_BELOW;
+                const bool take = s < top && s >= b0;
+                in |= (take ? 1u : 0u) << k;
+                delta[k] = gl_kde_add(__uint_as_float(s), -d0);
+            }
+            if (bad) atomicOr(sink.a.flag, bad);
+            if (!__any(in != 0u)) return;                           // (no barrier follows)
+            const int n_coef = sink.a.n;
+            for (int t = n_coef - 1; t >= 0; --t) {
+                const float c = coef[t];
+                unsigned long long w = 0ull;
+#pragma unroll
+                for (int k = 0; k < 16; ++k)
+                    if ((in >> k) & 1u) w += gl_kde_weight_x(gl_kde_mul(delta[k], c));      // = gl_kde_weight_f32(D32, D0, c)
+                w += __shfl_xor(w, 1, 64);
+                w += __shfl_xor(w, 2, 64);
+                if (part == 0 && w != 0ull) atomicAdd(&sink.sums[(q0 + ql) * n_coef + t], w);
             }
         } else if constexpr (EPI == 3) {
             const unsigned lo = sink.a.lo, hi = sink.a.hi;
@@ -432,6 +508,39 @@ int gl_l2_count_rows_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, con
                        (int)q_tiles, sink);
     GL_LAUNCH_CHECK();
     return GL_OK;
+}
+
+int gl_l2_kde_rows_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const float *D0_dev,
+                       const uint32_t *bound_dev, const float *coef_host, int n_coef, uint64_t *sums_dev)
+{
+    static const char *fn = "gl_l2_kde_rows_f32";
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && n_rows >= 0 && nq >= 0 && d > 0, "%s: bad sizes", fn);
+    GL_REQUIRE(n_coef >= 1 && n_coef <= GL_COUNT_MAX_T, "%s: n_coef=%d outside [1, %d]", fn, n_coef, GL_COUNT_MAX_T);
+    GL_REQUIRE(coef_host, "%s: NULL coefficients", fn);
+    f32_sink<5> sink;
+    for (int t = 0; t < GL_COUNT_MAX_T; ++t) sink.a.coef[t] = 0.0f;
+    for (int t = 0; t < n_coef; ++t) {
+        GL_REQUIRE(coef_host[t] >= 0.0f && coef_host[t] <= 3.402823466e38f, "%s: coef[%d] is not a finite value >= 0", fn, t);
+        GL_REQUIRE(t == 0 || coef_host[t] <= coef_host[t - 1], "%s: the coefficients must be descending (coef[%d] > coef[%d])", fn, t, t - 1);
+        sink.a.coef[t] = coef_host[t];
+    }
+    if (n_rows == 0 || nq == 0) return GL_OK;
+    GL_REQUIRE(D0_dev && bound_dev, "%s: NULL offsets or bounds", fn);
+    GL_REQUIRE(((reinterpret_cast<uintptr_t>(D0_dev) | reinterpret_cast<uintptr_t>(bound_dev)) & 3) == 0, "%s: offsets and bounds must be 4-byte aligned", fn);
+    GL_REQUIRE(bank_dev && query_dev && sums_dev, "%s: NULL device pointer", fn);
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(sums_dev) & 7) == 0, "%s: the sums must be 8-byte aligned", fn);
+    const int64_t q_tiles = gl_ceil_div(nq, TQ), n_tiles = gl_ceil_div(n_rows, TN);
+    GL_REQUIRE(q_tiles * n_tiles < (1ll << 31), "%s: grid too large", fn);
+    sink.a.d0 = D0_dev;
+    sink.a.bound = bound_dev;
+    sink.a.flag = ctx->kde_flag;
+    sink.a.n = n_coef;
+    sink.sums = reinterpret_cast<unsigned long long *>(sums_dev);
+    hipLaunchKernelGGL(l2_pairs_f32_kernel<5>, dim3((unsigned)(q_tiles * n_tiles)), dim3(THREADS), 0, ctx->stream, bank_dev, n_rows, query_dev, nq, d,
+                       (int)q_tiles, sink);
+    GL_LAUNCH_CHECK();
+    return gl_kde_flag_check(fn, ctx);
 }
 
 int gl_l2_hist_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, uint32_t lo, int shift, int n_bins,

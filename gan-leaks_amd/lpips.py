@@ -395,6 +395,29 @@ def feat_count_rows(bank, queries, thr, n_rows=None, counts=None):
     return counts
 
 
+def feat_kde_rows(bank, queries, D0, bound, coef, n_rows=None, sums=None):
+    """kernel-density (soft-min) sums under the distance feat_knn_keys searches: sums DeviceArray [Q, T] (uint64),
+    sums[q, t] += sum over n < n_rows of gl_kde_weight_f32(D32(q, n), D0[q], coef[t]) (csrc/gl_kde_epi.h), D32 the float32 distance
+    feat_count compares, bit for bit (same kernel up to the epilogue).  D0: float32 [Q], the distance of every query's nearest row;
+    bound: uint32 [Q], attack.kde_cut_bits_rows(D0, coef[-1]) -- host arrays (uploaded here) or DeviceArrays (a streamed bank uploads once
+    for all its chunks).  coef: 1..16 float32 values, finite, >= 0, descending.  A pair below D0 raises GanLeaksError and leaves the sums
+    unspecified.  `sums` from an earlier call (another chunk of the bank) is added to.  Row formats and layouts as feat_knn_keys.  Waits
+    for its kernel (the library reads the flag back)."""
+    from .attack import _kde_f32_operands
+    ctx = bank.ctx
+    roles = _search_pair_roles(bank, queries, "feat_kde_rows")
+    d0_dev, bound_dev, c32, sums, _ = _kde_f32_operands(ctx, queries.n, D0, bound, coef, sums, "feat_kde_rows")
+    n_rows = bank.n if n_rows is None else int(n_rows)
+    d0_ptr, bound_ptr = _p(d0_dev.ptr if d0_dev is not None else None), _p(bound_dev.ptr if bound_dev is not None else None)
+    if roles[0]:
+        check(ctx.lib.gl_feat_kde_rows_h1_scaled(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr),
+                                                 queries.n, bank.K, bank.scale, d0_ptr, bound_ptr, c32.ctypes.data_as(_p), len(c32), _p(sums.ptr)))
+    else:
+        check(ctx.lib.gl_feat_kde_rows(ctx.handle, _p(bank.V.ptr), _p(bank.norms.ptr), n_rows, _p(queries.V.ptr), _p(queries.norms.ptr), queries.n,
+                                       bank.K, d0_ptr, bound_ptr, c32.ctypes.data_as(_p), len(c32), _p(sums.ptr)))
+    return sums
+
+
 def feat_hist(bank, queries, lo, shift, n_bins, n_rows=None, hist=None):
     """histogram of ALL pair distances under the distance feat_knn_keys searches: hist DeviceArray [n_bins, 1] (uint64),
     hist[b] += #{ q, n < n_rows : lo <= bits(D32(q, n)) and (bits(D32(q, n)) - lo) >> shift == b }, bits the uint32 pattern of the float32

@@ -486,10 +486,12 @@ class DeviceGroup:
         return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, lambda n_eff: None,
                          reduce_fn_for, call)
 
-    def _pair_rows_job(self, queries, make_generator, z, bank, batch_size, weights, distance, make_lpips, float_path, generate_kwargs, validate, job):
+    def _pair_rows_job(self, queries, make_generator, z, bank, batch_size, weights, distance, make_lpips, float_path, generate_kwargs, validate, job,
+                       reduce_fn_for=None):
         """what pair_kth_distances and pair_ball_counts_rows share: pair_distance_quantiles' plumbing -- the host settles ONE layout for all
         ranks and all passes from the rows that take part, the [Q, T] counters of every pass are summed across the ranks.
-        job(prepared, shard, ctx, reduce_fn, model, lo, fpath, layout) is the per-rank call."""
+        job(prepared, shard, ctx, reduce_fn, model, lo, fpath, layout) is the per-rank call.  reduce_fn_for: another cross-shard reduction
+        than the sum (pair_kde_scores hands over a min and a sum)."""
         from ._lib import DeviceArray
         from .attack import host_rows_kind
         if distance == "l2":
@@ -504,7 +506,7 @@ class DeviceGroup:
                 if kb != "u8" or host_rows_kind(queries) != "u8":
                     layout = "hilo"
 
-        def reduce_fn_for(rank, ctx, comms, host):
+        def sum_reduce_fn_for(rank, ctx, comms, host):
             if comms is not None:
                 return lambda counts: allreduce_sum_counts(counts, comm=comms[rank])
             if self.world == 1:
@@ -516,7 +518,8 @@ class DeviceGroup:
                 prepared = model.features(queries, role="query", fmt="hilo")
             return job(prepared, shard, ctx, reduce_fn, model, lo, fpath, layout)
 
-        return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate, reduce_fn_for, call)
+        return self._run(queries, make_generator, z, bank, distance, batch_size, make_lpips, weights, generate_kwargs, validate,
+                         reduce_fn_for or sum_reduce_fn_for, call)
 
     def pair_kth_distances(self, queries, make_generator=None, z=None, bank=None, k=None, batch_size=64, weights=None, distance="l2-lpips",
                            make_lpips=None, float_path=None, **generate_kwargs):
@@ -543,6 +546,41 @@ class DeviceGroup:
                                       index_base=lo, float_path=fpath, _layout=layout)
 
         return self._pair_rows_job(queries, make_generator, z, bank, batch_size, weights, distance, make_lpips, float_path, generate_kwargs, validate, job)
+
+    def pair_kde_scores(self, queries, make_generator=None, z=None, bank=None, bandwidths=None, batch_size=64, weights=None, distance="l2-lpips",
+                        make_lpips=None, float_path=None, **generate_kwargs):
+        """attack.pair_kde_scores over the group's contexts, on pair_kth_distances' plumbing with kde_scores' reductions: rank r searches and
+        sums over rows [bounds[r], bounds[r+1]) of the bank (handed over or generated, as in attack_on_devices; a generated shard is
+        generated and featurised twice); the keys of the nearest-sample pass are min-reduced, the [Q, T] sums of the second pass summed
+        across the ranks, so every rank weighs its rows against the same D0.  (loss float64 [Q, T], W uint64 [Q, T], key int64 [Q]),
+        identical to the single-device result bit for bit.  The bandwidths and n_eff < 2^23 are checked before any rank starts; the host
+        settles one layout for all ranks and both passes.  distance, float_path: as attack.pair_kde_scores."""
+        from .attack import KDE_MAX_ROWS, _check_bandwidths, _check_rows_float_path, pair_kde_scores
+        if bandwidths is None:
+            raise ValueError("needs bandwidths")
+        h = _check_bandwidths(bandwidths)
+        _check_rows_float_path(float_path)
+        if distance not in ("l2", "l2-lpips"):
+            raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+
+        def validate(n_eff):
+            if n_eff >= KDE_MAX_ROWS:
+                raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d given)" % n_eff)
+
+        def reduce_fn_for(rank, ctx, comms, host):
+            if comms is not None:
+                return comms[rank].allreduce_min_keys, (lambda counts: allreduce_sum_counts(counts, comm=comms[rank]))
+            if self.world == 1:
+                return None
+            return (lambda keys: ctx.to_device(host.merge(rank, keys.numpy())),
+                    lambda counts: ctx.to_device(host.merge(rank, counts.numpy(), op="sum")))
+
+        def job(prepared, shard, ctx, reduce_fn, model, lo, fpath, layout):
+            return pair_kde_scores(prepared, shard, h, distance=distance, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, lpips=model,
+                                   index_base=lo, float_path=fpath, _layout=layout)
+
+        return self._pair_rows_job(queries, make_generator, z, bank, batch_size, weights, distance, make_lpips, float_path, generate_kwargs, validate, job,
+                                   reduce_fn_for)
 
     def pair_ball_counts_rows(self, queries, make_generator=None, z=None, bank=None, eps=None, batch_size=64, weights=None, distance="l2-lpips",
                               make_lpips=None, float_path=None, **generate_kwargs):
@@ -800,6 +838,21 @@ def pair_kth_distances_on_devices(queries, make_generator=None, z=None, devices=
         raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
     with DeviceGroup(devices) as group:
         return group.pair_kth_distances(queries, make_generator, z, bank, k, batch_size, weights, distance, make_lpips, float_path, **generate_kwargs)
+
+
+def pair_kde_scores_on_devices(queries, make_generator=None, z=None, devices=None, bandwidths=None, batch_size=64, weights=None, bank=None,
+                               distance="l2-lpips", make_lpips=None, float_path=None, **generate_kwargs):
+    """attack.pair_kde_scores sharded over a DeviceGroup built for the call (arguments as attack_on_devices; distance and float_path as
+    attack.pair_kde_scores): (loss float64 [Q, T], W uint64 [Q, T], key int64 [Q]), identical to the single-device result."""
+    from .attack import _check_bandwidths, _check_rows_float_path
+    if bandwidths is None:
+        raise ValueError("needs bandwidths")
+    _check_bandwidths(bandwidths)            # before any Context
+    _check_rows_float_path(float_path)
+    if distance not in ("l2", "l2-lpips"):
+        raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
+    with DeviceGroup(devices) as group:
+        return group.pair_kde_scores(queries, make_generator, z, bank, bandwidths, batch_size, weights, distance, make_lpips, float_path, **generate_kwargs)
 
 
 def pair_ball_counts_rows_on_devices(queries, make_generator=None, z=None, devices=None, eps=None, batch_size=64, weights=None, bank=None,

@@ -237,6 +237,11 @@ int gl_l2_kde_rows_i8(gl_ctx *ctx, const int8_t *bank_i8_dev, const int32_t *ban
 int gl_l2_kde_rows_i8_wide(gl_ctx *ctx, const int8_t *bank_i8_dev, const int64_t *bank_norm_dev, int64_t n_rows, const int8_t *query_i8_dev,
                            const int64_t *query_norm_dev, int64_t nq, int64_t d, const int64_t *S0_dev, const float *coef_host, int n_coef,
                            uint64_t *sums_dev);
+/* The float sibling of the cut-off under gl_l2_kde_rows_i8, for the kernel-density sums on float distances (gl_l2_kde_rows_f32,
+ * gl_feat_kde_rows*): out[i] = the smallest uint32 pattern b in [bits(D0[i]), 0x7F800000] at which fl32(fl32(float(b) - D0[i]) c) is not below
+ * 41, i.e. from which on every pair of query i has the weight 0 under the coefficient c (csrc/gl_kde_epi.h gl_kde_cut_bits, with the
+ * monotonicity argument).  Host arrays, no context, no GPU: D0 finite and >= 0, c finite and >= 0 (else GL_ERR_INVALID). */
+int gl_kde_cut_bits_rows(const float *D0, int64_t n, float c, uint32_t *out);
 /* dst[q][t] += sum over l < n_lists of src[l][q][t]; src_dev is [n_lists][nq][n_thr] (e.g. what gl_allgather_rows delivers from the ranks of a
  * sharded bank): the cross-shard sum, the counterpart of gl_topk_merge. */
 int gl_counts_add(gl_ctx *ctx, uint64_t *dst_dev, const uint64_t *src_dev, int64_t nq, int n_thr, int64_t n_lists);
@@ -298,6 +303,20 @@ int gl_l2_count_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const fl
  * gl_l2_knn_f32), asynchronous; like gl_l2_count_f32 it reports under no profiling id. */
 int gl_l2_count_rows_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const int64_t *thr_dev,
                          int n_thr, uint64_t *counts_dev);
+/* Kernel-density (soft-min) sums on fp32 rows, gl_l2_kde_rows_i8 on the float32 distance of gl_l2_knn_f32:
+ *     sums_dev[q * n_coef + t] += sum over n in [0, n_rows) of gl_kde_weight_f32(D32(q, n), D0_dev[q], coef_host[t]),
+ * the fixed-point weight 2^(-(D32 - D0) coef) in units of 2^-40 (csrc/gl_kde_epi.h: one rounded subtraction, one rounded product, then the
+ * integer path's arithmetic; a pure function of (D32, D0, coef), so the sums are a function of the multiset of distances: tile, chunking,
+ * bank order and sharding do not matter).  D0_dev: [nq] float32 in DEVICE memory, the distance of every query's nearest row (finite, >= 0);
+ * bound_dev: [nq] uint32 in DEVICE memory, gl_kde_cut_bits_rows(D0, coef_host[n_coef - 1]): a pair takes part when bits(D32) < bound, so a
+ * pair at +inf weighs nothing; both 4-byte aligned.  coef_host: n_coef in 1..GL_COUNT_MAX_T finite values >= 0, DESCENDING.  sums_dev
+ * [nq][n_coef] uint64 of gl_counts_init, 8-byte aligned; fewer than 2^23 rows per query in all (the caller's duty).
+ * Two errors are found by the kernel and reported through a device flag that the call reads back and clears (so the next call on the
+ * context is unaffected; the sums of the failing call are unspecified): a pair with bits(D32) < bits(D0) (GL_ERR_INVALID, "below the offset":
+ * its weight would exceed 2^40) and a pair whose D32 is NaN (GL_ERR_INVALID, "NaN").  Other checks as gl_l2_count_rows_f32; n_rows == 0 or
+ * nq == 0 is GL_OK and touches nothing.  One kernel (the K loop of gl_l2_knn_f32).  Synchronises. */
+int gl_l2_kde_rows_f32(gl_ctx *ctx, const float *bank_dev, int64_t n_rows, const float *query_dev, int64_t nq, int64_t d, const float *D0_dev,
+                       const uint32_t *bound_dev, const float *coef_host, int n_coef, uint64_t *sums_dev);
 /* The histogram of ALL pair distances on fp32 rows: the primitive under an exact quantile of the nq x n_rows values D32(q, n) (the K loop of
  * gl_l2_knn_f32 with a binning epilogue, so D32 is the same bits again).  D32 >= +0, so the unsigned order of the uint32 patterns
  * bits(D32) is the order of the floats and a radix-select over windows of patterns finds the exact D32 at any rank.  For a window
@@ -526,6 +545,19 @@ int gl_feat_count_rows_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const fl
                                  uint64_t *counts_dev);
 int gl_feat_count_rows(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev,
                        const float *query_norm_dev, int64_t nq, int64_t K, const int64_t *thr_dev, int n_thr, uint64_t *counts_dev);
+/* Kernel-density (soft-min) sums under 0.2 LPIPS + L2, the distance fbb.main hard-wires (attack_models/fbb.py:148):
+ *     sums_dev[q * n_coef + t] += sum over n in [0, n_rows) of gl_kde_weight_f32(D32(q, n), D0_dev[q], coef_host[t]),
+ * D32 the float32 distance gl_feat_knn* minimises and gl_feat_count* counts, bit for bit (the same main loop with another epilogue).
+ * D0_dev, bound_dev, coef_host, sums_dev, the below-offset error, the flag and the synchronisation: as gl_l2_kde_rows_f32 (D32 is never NaN
+ * here).  Row, norm, size and scale arguments, their checks and the choice between the three kernels as gl_feat_count_rows_h1_scaled /
+ * gl_feat_count_rows; n_rows == 0 or nq == 0 is GL_OK and touches nothing.  The sums do not depend on tile, chunking, query slicing,
+ * sharding or kernel.  Reports as GL_PROF_FEAT_COUNT. */
+int gl_feat_kde_rows_h1_scaled(gl_ctx *ctx, const void *bank_V16_dev, const float *bank_norm_dev, int64_t n_rows, const void *query_V16_dev,
+                               const float *query_norm_dev, int64_t nq, int64_t K1, float row_scale, const float *D0_dev, const uint32_t *bound_dev,
+                               const float *coef_host, int n_coef, uint64_t *sums_dev);
+int gl_feat_kde_rows(gl_ctx *ctx, const float *bank_V_dev, const float *bank_norm_dev, int64_t n_rows, const float *query_V_dev,
+                     const float *query_norm_dev, int64_t nq, int64_t K, const float *D0_dev, const uint32_t *bound_dev, const float *coef_host,
+                     int n_coef, uint64_t *sums_dev);
 /* The histogram of ALL pair distances under 0.2 LPIPS + L2 (the primitive under an exact quantile of the nq x n_rows values D32(q, n): the
  * percentile heuristic for the radius of the Monte-Carlo attack under the reference's fbb distance).  D32 >= +0 and never NaN, so the
  * unsigned order of the uint32 patterns bits(D32) is the order of the floats.  For a window (lo: uint32, 0 <= shift <= 31,

@@ -7,7 +7,9 @@ that the 256-channel tile never runs was added to its epilogue (round 2).  tests
     python tools/check_loop_spills.py            one line per kernel; exit status 1 if any count is non-zero
     python tools/check_loop_spills.py --kernels gl_feat_count.hip:feat_pairs_h1_kernelILi0ELb1E,... [--pipelined file:name,...]
                                                  the same checks for the kernels named instead of the lists below: --kernels counts spills inside
-                                                 the K loop, --pipelined checks the hand-placed fragment reads of a gl_pair256.h kernel
+                                                 the K loop, --pipelined checks the hand-placed fragment reads of a gl_pair256.h kernel.
+                                                 name@opcode brackets the K loop by that opcode prefix instead of v_mfma, for a VALU kernel:
+                                                 gl_l2f32.hip:l2_pairs_f32_kernelILi5E@v_fma (over-counts if the epilogue uses it too)
 """
 import os
 import re
@@ -37,13 +39,15 @@ PIPELINED = {"gl_l2knn.hip": ["l2_knn_i8_256p_kernelILi0ELi8E"], "gl_lpips.hip":
 
 
 def loop_spills(asm, needle):
+    needle, _, opcode = needle.partition("@")
+    opcode = opcode or "v_mfma"
     m = re.search(r"^(_Z\S*%s\S*):" % re.escape(needle), asm, re.M)
     if not m:
         return None
     name = m.group(1)
     body = asm[m.end():asm.index(".amdhsa_kernel " + name)]
     lines = body.split("\n")
-    mfma = [i for i, l in enumerate(lines) if "v_mfma" in l]
+    mfma = [i for i, l in enumerate(lines) if opcode in l]
     if not mfma:
         return None
     return sum(1 for i, l in enumerate(lines) if "scratch_" in l and mfma[0] < i < mfma[-1])

@@ -105,6 +105,9 @@ SIGNATURES = {
     "gl_keys_unpack_f32": (_i, [_p, _p, _i64, _p, _p]),
     "gl_l2_rows_f32": (_i, [_p, _p, _i64, _p, _i64, _i64, _p]),
     "gl_fbb_knn_l2_host": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64, _p, _p]),
+    "gl_pbb_candidates": (_i, [_p, _p, _p, _i64, _i64, _i64, ctypes.c_uint64, ctypes.c_uint32, _i64, ctypes.c_float, _p]),
+    "gl_pbb_group_min": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "gl_pbb_accept": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p]),
     "gl_dcgan_create": (_i, [_p, _i, _i, _i, _pp]),
     "gl_dcgan_destroy": (_i, [_p]),
     "gl_dcgan_set_conv_weight": (_i, [_p, _i, _p]),

@@ -339,6 +339,43 @@ int gl_l2_rows_f32(gl_ctx *ctx, const float *x_hat_dev, int64_t b, const float *
 int gl_fbb_knn_l2_host(gl_ctx *ctx, const uint8_t *bank_u8_host, int64_t n_bank, const uint8_t *queries_u8_host, int64_t nq,
                        int64_t d, int64_t batch_size, float *dist_host, int64_t *idx_host);
 
+/* ---------------------------------------------------------------- partial-black-box attack: gradient-free latent search
+ * GAN-Leaks' second attack (section 5.3 of the paper; the reference fork ships only fbb.py): the attacker holds the generator, searches
+ * z* = argmin_z L(x, G(z)) without gradients and scores the query by L(x, G(z*)).  Built as a (1 + lambda) evolution strategy per query:
+ * a round is gl_pbb_candidates -> the generator on all nq * lambda latents -> gl_pbb_group_min -> gl_pbb_accept, with everything resident on
+ * the device.  All three run on the context's stream, do not synchronise, return GL_OK for nq == 0 and read no tuning variable. */
+/* the bit pattern of C = float32(1 / (65536 sqrt(8/3))) = 9.344062e-06, the scale of the noise below */
+#define GL_PBB_NOISE_SCALE_BITS 0x371CC471u
+/* out[(q * lambda + j) * nz + c] = clamp(fl32(z[q * nz + c] + fl32(sigma[q] * eps)), -z_max, z_max), each operation rounded on its own (no
+ * fma).  eps(seed, round, query_base + q, j, c) is a pure function of its five indices, from integer arithmetic only: ONE Philox4x32-10
+ * call with key (seed & 0xffffffff, seed >> 32) and counter (c, j, (query_base + q) & 0xffffffff, round); its four words are cut into eight
+ * 16-bit halves h0..h7; t = 2 (h0 + ... + h7) - 524280, an int32 with |t| < 2^24; eps = fl32(float(t) * C).  That is Irwin-Hall with n = 8:
+ * mean 0, variance 1, support +-4.9.  Candidates therefore do not depend on how the queries are blocked or sharded (query_base is the
+ * global index of query 0 of this call).  z_dev [nq][nz], sigma_dev [nq], out_dev [nq * lambda][nz], fp32.  query_base + nq <= 2^32;
+ * z_max finite and positive. */
+int gl_pbb_candidates(gl_ctx *ctx, const float *z_dev, const float *sigma_dev, int64_t nq, int64_t nz, int64_t lambda, uint64_t seed, uint32_t round,
+                      int64_t query_base, float z_max, float *out_dev);
+/* Every query against its OWN lambda candidate images (a grouped distance, not all pairs): S(q, j) = sum_k (queries[q][k] -
+ * cand[q * lambda + j][k])^2 exactly, out_S[q] = min_j S(q, j), out_j[q] = the smallest j that attains it.  Raw image codes on both sides: no
+ * prepare step, no norms.  queries_u8_dev [nq][d], cand_u8_dev [nq * lambda][d], d <= gl_l2_max_d(1); out_S_dev [nq] uint64 (8-byte
+ * aligned), out_j_dev [nq] int32.  A streaming kernel: workgroup (q, g) takes GL_PBB_GROUP candidates of query q, the query row goes
+ * through LDS in chunks, each wave owns whole candidates, reads them once with 16-byte loads (bytes when d is no multiple of 16 or a base
+ * pointer is not 16-byte aligned) and squares with the 8-bit dot instruction into 64-bit totals; no pairwise value reaches memory.
+ * workspace_dev: GL_PBB_PARTIAL_BYTES * nq * ceil(lambda / GL_PBB_GROUP) bytes, 16-byte aligned, holding one (S, j) per workgroup, which a
+ * second small kernel of the same call combines in ascending j (no atomics). */
+#define GL_PBB_GROUP 16
+#define GL_PBB_PARTIAL_BYTES 16
+int gl_pbb_group_min(gl_ctx *ctx, const uint8_t *queries_u8_dev, const uint8_t *cand_u8_dev, int64_t nq, int64_t lambda, int64_t d, uint64_t *out_S_dev,
+                     int32_t *out_j_dev, void *workspace_dev);
+/* The elitist (1 + lambda) step.  Where S_new[q] < S_cur[q], strictly: z[q] = cand_z[q * lambda + j_new[q]], S_cur[q] = S_new[q],
+ * sigma[q] = fl32(sigma[q] * up), accepted[q] = 1; otherwise sigma[q] = fl32(sigma[q] * down), accepted[q] = 0 and z, S_cur stay.  Then
+ * sigma[q] is clamped to [sigma_min, sigma_max].  z_dev [nq][nz], sigma_dev [nq], cand_z_dev [nq * lambda][nz] fp32; S_cur_dev, S_new_dev
+ * [nq] uint64; j_new_dev [nq] int32 in [0, lambda) (a value outside is not accepted); accepted_dev [nq] bytes.  up, down, sigma_min <=
+ * sigma_max finite and positive. */
+int gl_pbb_accept(gl_ctx *ctx, float *z_dev, float *sigma_dev, uint64_t *S_cur_dev, const float *cand_z_dev, const uint64_t *S_new_dev,
+                  const int32_t *j_new_dev, int64_t nq, int64_t nz, int64_t lambda, float up, float down, float sigma_min, float sigma_max,
+                  uint8_t *accepted_dev);
+
 /* ---------------------------------------------------------------- sharded bank: the cross-GPU minimum (RCCL over xGMI) */
 /* The reference runs on one device (attack_models/fbb.py:40) and takes the minimum over the whole bank with torch.min (fbb.py:86).  With the bank
  * sharded over GPUs every rank holds keys[q] = min over ITS rows, global indices inside; the minimum over ranks of the unsigned

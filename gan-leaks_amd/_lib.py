@@ -108,6 +108,7 @@ SIGNATURES = {
     "gl_pbb_candidates": (_i, [_p, _p, _p, _i64, _i64, _i64, ctypes.c_uint64, ctypes.c_uint32, _i64, ctypes.c_float, _p]),
     "gl_pbb_group_min": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "gl_pbb_accept": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p]),
+    "gl_wb_adam_step": (_i, [_p, _p, _p, _p, _p, _i64, _i64] + [ctypes.c_float] * 7),
     "gl_dcgan_create": (_i, [_p, _i, _i, _i, _pp]),
     "gl_dcgan_destroy": (_i, [_p]),
     "gl_dcgan_set_conv_weight": (_i, [_p, _i, _p]),
@@ -122,6 +123,8 @@ SIGNATURES = {
     "gl_dcgan_set_spectral_hold": (_i, [_p, _i]),
     "gl_dcgan_set_fuse_tail": (_i, [_p, _i]),
     "gl_dcgan_set_attention": (_i, [_p, _p, _p, _p, _p, _p, _p, ctypes.c_float]),
+    "gl_dcgan_vjp_z": (_i, [_p, _p, _i64, _p, _p, _p]),
+    "gl_dcgan_l2_grad_z": (_i, [_p, _p, _p, _i64, _p, _p]),
     "gl_pggan_create": (_i, [_p, _i, _i, _i, _pp]),
     "gl_pggan_destroy": (_i, [_p]),
     "gl_pggan_set_initial": (_i, [_p, _p, _p, _p, _p]),

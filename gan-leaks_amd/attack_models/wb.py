@@ -1,0 +1,141 @@
+"""[build] The white-box attack of GAN-Leaks (section 5.4 of the paper) on the data fbb.py reads.
+
+The attacker holds the generator's weights: for every query x, z* = argmin_z L(x, G(z)) is found by gradient descent (Adam on the exact
+gradient through the generator) and the query is scored by L(x, G(z*)), L the L2 distance of Loss('l2') (attack_models/utils.py:161-164).
+The reference fork has no driver for it; the data flags, the YAML overlay, the start and the layout of the result directory are pbb.py's,
+so that eval_roc.py scores the result unchanged.  The search is ganleaks_amd.wb.wb_attack, started from the nearest of a bank of latents
+(the full-black-box answer), which it can only improve on.
+
+    python -m ganleaks_amd.attack_models.wb --local_config config_attack_fbb.yaml --gan {dcgan,wgangp} --generator_path generator.pth
+           [--nz --ngf] [--noise_path npz | --num_init N --init_seed s] [--steps --lr --beta1 --beta2] [--BATCH_SIZE]
+
+--gan, --generator_path  the generator class and its state dict (what the training scripts save as generator.pth); PGGAN and VAEGAN have
+                         no backward pass and are refused
+--nz, --ngf              latent length and width (features_g)
+--noise_path             the .npz the generate branches write under npz_noise/ (array `noise`): the latents of the sample bank
+--num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
+--BATCH_SIZE             only the first (N // BATCH_SIZE) * BATCH_SIZE latents take part in the start, as in fbb.py:77
+--steps, --lr, --beta1, --beta2   the descent (ganleaks_amd.wb.wb_attack)
+Files under ./wb_attack/<exp_name>/:
+    {pos,neg}_loss.npy float64 [n, 1]: L(x, G(z*)); {pos,neg}_z.npy float32 [n, nz]: z*; {pos,neg}_S.npy int64 [n, 1]: the exact sum of
+    squared differences behind the loss; {pos,neg}_init_loss.npy float64 [n, 1]: the full-black-box score the descent started from;
+    {pos,neg}_trace.npy int64 [steps + 1, n]: the best S after every step; params.txt.  Small = member-like:
+    `eval_roc --attack_type wb -ldir wb_attack/<exp_name>` scores the attack.
+One GPU.
+"""
+from __future__ import annotations
+
+import argparse
+import os
+import warnings
+
+import numpy as np
+
+from ..attack import _dist32
+from ..pbb import pbb_init_from_bank
+from ..wb import wb_attack
+from .fbb import update_args  # noqa: F401  (the YAML overlay of the command line)
+from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, save_files
+
+
+def parse_arguments(argv=None):
+    parser = argparse.ArgumentParser()
+    data_root = os.path.join(os.getcwd(), 'data', 'miniCelebA')
+    parser.add_argument('--exp_name', '-name', type=str, default='debug', help='experiment name; results go to ./wb_attack/<exp_name>')
+    parser.add_argument('--pos_data_dir', type=str, default=os.path.join(data_root, 'train'), help='folder with the member (training) query images')
+    parser.add_argument('--neg_data_dir', type=str, default=os.path.join(data_root, 'test'), help='folder with the non-member (held-out) query images')
+    parser.add_argument('--resolution', '-resolution', type=int, default=64, help='images that differ are resized to this square size')
+    parser.add_argument('--BATCH_SIZE', type=int, default=30)
+    parser.add_argument('--local_config', type=str, default=None)
+    parser.add_argument('--gan', type=str, default='dcgan', help='the generator class: dcgan or wgangp')
+    parser.add_argument('--generator_path', type=str, default=None, help="the generator's state dict (generator.pth)")
+    parser.add_argument('--nz', type=int, default=100, help='length of a latent vector')
+    parser.add_argument('--ngf', type=int, default=64, help='width parameter of the generator (features_g)')
+    parser.add_argument('--nc', type=int, default=3, help='image channels')
+    parser.add_argument('--noise_path', type=str, default=None, help="npz with the bank's latents (array 'noise'), as the generate branches write it")
+    parser.add_argument('--num_init', type=int, default=None, help='without --noise_path: draw this many starting latents')
+    parser.add_argument('--init_seed', type=int, default=0, help='seed of the drawn starting latents')
+    parser.add_argument('--steps', type=int, default=64, help='gradient steps')
+    parser.add_argument('--lr', type=float, default=0.05, help="Adam's step size")
+    parser.add_argument('--beta1', type=float, default=0.9)
+    parser.add_argument('--beta2', type=float, default=0.999)
+    return parser.parse_args(argv)
+
+
+def _request(args):
+    """what can be refused before any file is read"""
+    if args.gan not in ("dcgan", "wgangp"):
+        raise SystemExit("--gan must be dcgan or wgangp, got %r: the backward pass is built for the DCGAN / WGAN-GP generator only (PGGAN and "
+                         "VAEGAN are not)" % (args.gan,))
+    if getattr(args, "generator_path", None) is None:
+        raise SystemExit("--generator_path is needed: the white-box attacker holds the generator")
+    if (getattr(args, "noise_path", None) is None) == (getattr(args, "num_init", None) is None):
+        raise SystemExit("give exactly one of --noise_path (the bank's latents) and --num_init (draw that many)")
+    if args.num_init is not None and int(args.num_init) < 1:
+        raise SystemExit("--num_init must be at least 1, got %s" % (args.num_init,))
+    if int(args.steps) < 0 or not (np.isfinite(args.lr) and args.lr > 0) or not (0 <= args.beta1 < 1) or not (0 <= args.beta2 < 1):
+        raise SystemExit("--steps must be >= 0, --lr positive and --beta1, --beta2 in [0, 1), got %s, %s, %s, %s"
+                         % (args.steps, args.lr, args.beta1, args.beta2))
+
+
+def load_generator(args):
+    """-> (generator, nz)"""
+    import torch
+    from ..gan_models.dcgan.model_torch import Generator     # wgangp shares it (gan_models/wgangp/model.py)
+    sd = torch.load(args.generator_path, map_location="cpu", weights_only=True)
+    nz = int(args.nz)
+    gen = Generator(nz, int(args.nc), int(args.ngf))
+    gen.load_state_dict(sd)
+    return gen, nz
+
+
+def main(args):
+    _request(args)
+    assert os.path.exists(args.generator_path)
+    save_dir = check_folder(os.path.join(os.getcwd(), 'wb_attack', args.exp_name))
+    lines = ["%s:%s" % (key, value) for key, value in vars(args).items()]
+    with open(os.path.join(save_dir, 'params.txt'), 'w') as handle:
+        handle.write("".join(line + "\n" for line in lines))
+    print("\n".join(lines))
+
+    resolution = args.resolution
+    pos_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.pos_data_dir, ext='png'), resolution)
+    neg_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.neg_data_dir, ext='png'), resolution)
+    both = np.concatenate([pos_query_imgs, neg_query_imgs])
+    n_pos = len(pos_query_imgs)
+
+    gen, nz = load_generator(args)
+    if args.noise_path is not None:
+        with np.load(args.noise_path) as data:
+            z_bank = np.asarray(data["noise"], np.float32)
+        z_bank = z_bank.reshape(len(z_bank), -1)
+        if z_bank.shape[1] != nz:
+            raise SystemExit("--noise_path holds latents of length %d, the generator takes %d" % (z_bank.shape[1], nz))
+    else:
+        z_bank = np.random.default_rng(int(args.init_seed)).standard_normal((int(args.num_init), nz)).astype(np.float32)
+    if len(z_bank) < int(args.BATCH_SIZE):
+        raise SystemExit("the %d starting latents hold no full batch of %d" % (len(z_bank), args.BATCH_SIZE))
+
+    z_init, _ = pbb_init_from_bank(both, gen, z_bank, batch_size=int(args.BATCH_SIZE))
+    dist, z_star, S, trace = wb_attack(both, gen, z_init, steps=int(args.steps), lr=float(args.lr), beta1=float(args.beta1), beta2=float(args.beta2),
+                                       history=True)
+    d = int(np.prod(both.shape[1:]))
+    init = _dist32(trace[0], d, "u8")                                                 # attack()'s float32 for the starting S
+    loss, init_loss, S = dist.astype(np.float64).reshape(-1, 1), init.astype(np.float64).reshape(-1, 1), S.reshape(-1, 1)
+    save_files(save_dir, ['pos_loss', 'neg_loss'], [np.ascontiguousarray(loss[:n_pos]), np.ascontiguousarray(loss[n_pos:])])
+    save_files(save_dir, ['pos_z', 'neg_z'], [np.ascontiguousarray(z_star[:n_pos]), np.ascontiguousarray(z_star[n_pos:])])
+    save_files(save_dir, ['pos_S', 'neg_S'], [np.ascontiguousarray(S[:n_pos]), np.ascontiguousarray(S[n_pos:])])
+    save_files(save_dir, ['pos_init_loss', 'neg_init_loss'], [np.ascontiguousarray(init_loss[:n_pos]), np.ascontiguousarray(init_loss[n_pos:])])
+    save_files(save_dir, ['pos_trace', 'neg_trace'], [np.ascontiguousarray(trace[:, :n_pos]), np.ascontiguousarray(trace[:, n_pos:])])
+    return save_dir, loss[:n_pos], loss[n_pos:], z_star, S
+
+
+if __name__ == '__main__':
+    import yaml
+    cli = parse_arguments()
+    if cli.local_config is None:
+        warnings.warn("No config file was provided. Using default parameters.")
+    else:
+        with open(str(cli.local_config)) as handle:
+            update_args(cli, yaml.safe_load(handle))
+    main(cli)

@@ -4,45 +4,11 @@
 // Layer l = 0..3: ConvTranspose2d(bias=False) -> BatchNorm2d (eval: running stats) -> ReLU
 // Layer 4:        ConvTranspose2d(+bias) -> tanh           (-> 8-bit code of the generate branch)
 // Activations are NHWC fp32 and stay resident in HBM for a whole pass of `chunk` images.
-#include "gl_conv.h"
+#include "gl_dcgan.h"
 #include <cmath>
 #include <cstdlib>
 #include <vector>
 
-struct gl_dcgan {
-    gl_ctx *ctx;
-    int z_dim, z_pad, nc, fg;
-    int cin[5], cout[5];
-    float *wpack[5];           // device, packed
-    float *scale[4], *shift[4];
-    float *bias_out;
-    bool have_w[5], have_bn[4], have_bias;
-    int64_t chunk, ws_chunk;   // requested / allocated images per pass
-    float *ws_z, *ws_a[4];     // z padded; outputs of layers 0..3
-    float *ws_p;               // scatter-form output of layer 4: [img][H*W][16 taps * nc]
-    float *ident_scale, *ident_shift;   // epilogue constants (1, 0) for the layer-4 GEMM
-    // optional self-attention on the output of layer 2 (VAEGAN: gan_models/vaegan/ops.py:86-120)
-    bool have_att;
-    float *att_w, *att_wsplit, *att_bias, *att_ones, *att_scale_h3, att_gamma;   // [q | k | v] 1x1 convolutions as one GEMM
-    int att_cols, att_cols_pad, att_wexp;
-    float *ws_att, *ws_qkv;
-    // split-fp16 path (gl_conv_h3.hip): weights in the split layout scaled by 2^wexp, epilogue constants folded for it
-    // optional spectral normalisation of layers 0..3 (VAEGAN: gan_models/vaegan/ops.py:23-75): w_bar as [C_in][C_out * 16], the power-iteration
-    // state u [C_in], v [C_out * 16] and gamma / sqrt(var + eps) per output channel stay on the device; every forward advances u, v and
-    // rewrites the epilogue scale as bn_scale / sigma
-    bool have_sn[4];
-    float *sn_w[4], *sn_u[4], *sn_v[4], *sn_wv[4], *sn_bns[4];
-    int sn_iters;
-    bool sn_hold;              // next forward(s) reuse the current sigma (a re-run of the same call)
-    int precision;             // 0 = fp32 MFMA (exact fp32 products), 1 = split-fp16 (three fp16 MFMAs per product, ~22-bit operands)
-    float *wsplit[5];
-    bool fuse_tail;            // default on (gl_dcgan_set_fuse_tail)
-    void *tail_w;              // layer 4 packed for the epilogue of layer 3 (gl_pack_tail_weights_host), when layer 3 has 64 or 128 channels
-    int wexp[5];
-    std::vector<float> h_scale[4], h_shift[4];
-    float *scale_h3[5], *shift_h3[5];
-    bool h3_dirty;
-};
 
 // activations of the split path are stored multiplied by this power of two (keeps small values out of the fp16 subnormals)
 static const float kActScale = 16.0f;
@@ -339,6 +305,12 @@ int gl_dcgan_create(gl_ctx *ctx, int z_dim, int channels_img, int features_g, gl
     g->att_cols = g->att_cols_pad = g->att_wexp = 0;
     g->ws_att = g->ws_qkv = nullptr;
     g->ident_scale = g->ident_shift = nullptr;
+    g->fwd_last_m = 0;
+    g->grad_dirty = true;
+    g->gws_chunk = 0;
+    g->gws_y = g->gws_g4 = g->gws_patch = nullptr;
+    for (int l = 0; l < 5; ++l) g->gw[l] = nullptr;
+    for (int l = 0; l < 4; ++l) g->gws_da[l] = g->gws_gp[l] = nullptr;
     {
         std::vector<float> one(16 * channels_img, 1.0f), zero(16 * channels_img, 0.0f);
         int rc = upload(ctx, &g->ident_scale, one);
@@ -366,6 +338,9 @@ int gl_dcgan_destroy(gl_dcgan *g)
     (void)hipFree(g->ident_scale);
     (void)hipFree(g->ident_shift);
     (void)hipFree(g->tail_w);
+    for (int l = 0; l < 5; ++l) (void)hipFree(g->gw[l]);
+    (void)hipFree(g->gws_y); (void)hipFree(g->gws_g4); (void)hipFree(g->gws_patch);
+    for (int l = 0; l < 4; ++l) { (void)hipFree(g->gws_da[l]); (void)hipFree(g->gws_gp[l]); }
     for (int l = 0; l < 4; ++l) { (void)hipFree(g->sn_w[l]); (void)hipFree(g->sn_u[l]); (void)hipFree(g->sn_v[l]); (void)hipFree(g->sn_wv[l]); (void)hipFree(g->sn_bns[l]); }
     delete g;
     return GL_OK;
@@ -448,6 +423,8 @@ int gl_dcgan_set_conv_weight(gl_dcgan *g, int layer, const float *w)
         }
         g->h3_dirty = true;
     }
+    g->h_w[layer].assign(w, w + (size_t)ci_n * co_n * 16);
+    g->grad_dirty = true;
     g->have_w[layer] = true;
     return GL_OK;
 }
@@ -680,6 +657,7 @@ int gl_dcgan_forward(gl_dcgan *g, const float *z_dev, int64_t n, float *out_f32_
     const int64_t per_pass = g->ws_chunk >= 512 ? g->ws_chunk - g->ws_chunk % 512 : gl_ceil_div(n, passes);
     for (int64_t i0 = 0; i0 < n; i0 += per_pass) {
         const int64_t m = (n - i0 < per_pass) ? n - i0 : per_pass;
+        g->fwd_last_m = m;
         if (h3) {
             rc = gl_launch_split_rows(ctx, z_dev + i0 * g->z_dim, m, g->z_dim, g->z_pad, kActScale, g->ws_z);
             if (rc != GL_OK) return rc;

@@ -152,6 +152,35 @@ class Generator:
         return u8
 
 
+    # ---- gradients with respect to z (csrc/gl_dcgan_grad.hip): the white-box attack
+    def vjp_z(self, z, cot, want_output=False):
+        """grad_z = (dG/dz)^T cot for cot [N,C,64,64] float32 -> DeviceArray [N, z_dim]; with want_output also G(z) of the fp32-product
+        forward the gradient belongs to, as a DeviceArray [N,C,64,64].  The generator's precision, chunk and fuse_tail stay as they are."""
+        if not self._loaded:
+            raise RuntimeError("Generator: load_state_dict() has not been called")
+        zd, n = self._z_device(z)
+        cd = as_device(self.ctx, cot, np.float32)
+        if cd.nbytes != n * self.channels_img * 64 * 64 * 4:
+            raise ValueError("expected a cotangent of shape [%d,%d,64,64], got %s" % (n, self.channels_img, cd.shape))
+        grad = self.ctx.empty((n, self.z_dim), np.float32)
+        out = self.ctx.empty((n, self.channels_img, 64, 64), np.float32) if want_output else None
+        check(self.ctx.lib.gl_dcgan_vjp_z(self._handle, _p(zd.ptr), n, _p(cd.ptr), _p(grad.ptr), _p(out.ptr if out else 0)))
+        return (grad, out) if want_output else grad
+
+    def l2_grad_z(self, z, targets_u8):
+        """loss[i] = sum (G(z_i) - x_i)^2 over the image, x = 2 u / 255 - 1 of targets_u8 [N,C,64,64] uint8, and grad = d loss / d z:
+        -> (grad DeviceArray [N, z_dim], loss DeviceArray [N]), float32"""
+        if not self._loaded:
+            raise RuntimeError("Generator: load_state_dict() has not been called")
+        zd, n = self._z_device(z)
+        td = as_device(self.ctx, targets_u8, np.uint8)
+        if td.nbytes != n * self.channels_img * 64 * 64:
+            raise ValueError("expected targets of shape [%d,%d,64,64] uint8, got %s" % (n, self.channels_img, td.shape))
+        grad, loss = self.ctx.empty((n, self.z_dim), np.float32), self.ctx.empty((n,), np.float32)
+        check(self.ctx.lib.gl_dcgan_l2_grad_z(self._handle, _p(zd.ptr), _p(td.ptr), n, _p(grad.ptr), _p(loss.ptr)))
+        return grad, loss
+
+
 class stackGenerators:
     """model_torch.py:99-108: num_generators independent generators; forward(x, i) runs generator i.
     state_dict keys are `gen.{i}.gen.{...}` (the reference generates from i = 0, privDCGAN.py:192)."""

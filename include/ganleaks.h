@@ -376,6 +376,17 @@ int gl_pbb_accept(gl_ctx *ctx, float *z_dev, float *sigma_dev, uint64_t *S_cur_d
                   const int32_t *j_new_dev, int64_t nq, int64_t nz, int64_t lambda, float up, float down, float sigma_min, float sigma_max,
                   uint8_t *accepted_dev);
 
+/* ---------------------------------------------------------------- white-box attack: gradient descent on the latent
+ * GAN-Leaks' third attack (section 5.4 of the paper): z* = argmin_z L(x, G(z)) by gradient descent with the generator's weights in hand.
+ * A step is gl_dcgan_l2_grad_z -> gl_wb_adam_step -> the generator's 8-bit images of the new iterate -> gl_pbb_group_min (lambda = 1) ->
+ * gl_pbb_accept (lambda = 1) into a separate best-so-far (z, S), so that the reported score is the exact integer S of the other attacks. */
+/* One Adam update per element, fp32, every operation rounded on its own (no fma; correctly rounded quotient and square root):
+ *   m = fl(fl(beta1 m) + fl(fl(1 - beta1) g)),  v = fl(fl(beta2 v) + fl(fl(fl(1 - beta2) g) g)),
+ *   z = clamp(fl(z - fl(fl(lr fl(m c1)) / fl(sqrt(fl(v c2)) + eps))), -z_max, z_max)
+ * with c1 = 1 / (1 - beta1^t), c2 = 1 / (1 - beta2^t) computed by the caller in double and passed as floats.  z, m, v, grad [nq][nz]. */
+int gl_wb_adam_step(gl_ctx *ctx, float *z_dev, float *m_dev, float *v_dev, const float *grad_dev, int64_t nq, int64_t nz, float lr, float beta1,
+                    float beta2, float eps, float c1, float c2, float z_max);
+
 /* ---------------------------------------------------------------- sharded bank: the cross-GPU minimum (RCCL over xGMI) */
 /* The reference runs on one device (attack_models/fbb.py:40) and takes the minimum over the whole bank with torch.min (fbb.py:86).  With the bank
  * sharded over GPUs every rank holds keys[q] = min over ITS rows, global indices inside; the minimum over ranks of the unsigned
@@ -448,6 +459,21 @@ int gl_dcgan_get_spectral_state(gl_dcgan *g, int layer, float *u_host, float *v_
 int gl_dcgan_set_spectral_hold(gl_dcgan *g, int hold);
 int gl_dcgan_set_attention(gl_dcgan *g, const float *wq_host, const float *bq_host, const float *wk_host, const float *bk_host, const float *wv_host,
                            const float *bv_host, float gamma);
+/* The generator's gradient with respect to its latent input (the white-box attack's hot path, csrc/gl_dcgan_grad.hip).  Both calls run
+ * their OWN forward with fp32 products, whatever gl_dcgan_set_precision says, keep its post-ReLU activations and go backwards through the
+ * same fp32 tap-gather GEMMs: tanh', then per layer the ReLU mask and the BatchNorm scale followed by Conv2d(k4 s2 p1) with the layer's own
+ * weights (the data gradient of ConvTranspose2d(k4 s2 p1)), then one GEMM to z_dim columns.  All products are fp32; every output element is
+ * one fixed-order sum (no atomics, no split K), so the gradient row of an image does not depend on which images share the call or the pass.
+ * Passes honour gl_dcgan_set_chunk and the 3 GiB-per-tensor cap.  The transposed weight packs and the gradient workspaces are allocated on
+ * the first gradient call, not before; precision, fuse_tail and chunk are left as found.  Generators with self-attention or spectral
+ * normalisation (VAEGAN) are refused with GL_ERR_STATE.  n = 0 returns GL_OK; on the context's stream, no synchronisation. */
+/* vector-Jacobian product: grad_z[n][z_dim] = (dG/dz)^T cot, cot [n][3][64][64] fp32 (NCHW, 16-byte aligned).  out_f32_dev (may be NULL;
+ * 16-byte aligned) receives G(z) of the fp32-product forward: the values gl_dcgan_forward gives under precision 0 */
+int gl_dcgan_vjp_z(gl_dcgan *g, const float *z_dev, int64_t n, const float *cot_dev, float *grad_z_dev, float *out_f32_dev);
+/* loss[i] = sum over the image of (G(z_i) - x_i)^2, x = 2 u/255 - 1 of target_u8 [n][3][64][64] (4-byte aligned); grad_z = d loss / d z.
+ * The cotangent 2 (y - x) is formed between the forward and the backward of each pass and never stored for the whole call; the squares
+ * are added in double */
+int gl_dcgan_l2_grad_z(gl_dcgan *g, const float *z_dev, const uint8_t *target_u8_dev, int64_t n, float *grad_z_dev, float *loss_dev);
 
 /* ---------------------------------------------------------------- PGGAN generator */
 /* gan_models/pggan/model_torch.py:49-88 Generator(z_dim, in_channels, img_channels).forward(x, steps, alpha)

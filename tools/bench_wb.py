@@ -1,0 +1,133 @@
+#!/usr/bin/env python3
+"""Timing of the white-box attack's gradient and step (ganleaks_amd.wb), and its result next to the partial-black-box search from the same
+start.  ONE process on the shipped library, run it under the caller's `timeout`:
+    python tools/bench_wb.py [--rounds 7] [--queries 4096] [--ngf 64] [--compare_queries 1024] [--steps 64]
+DCGAN-64 with synthetic weights.  Timed with device events on the context's stream, every variant warmed up once, then the variants
+ALTERNATE inside every round (median, smallest, largest):
+  forward fp32    gl_dcgan_forward at precision 0, fp32 output: the forward half of the gradient call
+  l2_grad_z       gl_dcgan_l2_grad_z: that forward, the cotangent and the backward pass; x_forward is its ratio to `forward fp32`
+  scoring         generate_u8 at the generator's own precision (split-fp16), the extra forward of a step
+  step            l2_grad_z + gl_wb_adam_step + generate_u8 + gl_pbb_group_min + gl_pbb_accept: one step of wb_attack; scoring_share is
+                  `scoring` / `step`, steps_per_s the inverse of the median
+Then, on --compare_queries queries (half images of latents 0.5 away from a bank latent, half images of unrelated latents) started from
+pbb_init_from_bank: the final S of wb_attack(steps) beside pbb_attack(rounds=32, population=64) -- `steps` gradient passes against 2048
+forwards per query.  One JSON line per variant and one for the comparison."""
+import argparse
+import ctypes
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--queries", type=int, default=4096)
+    ap.add_argument("--ngf", type=int, default=64)
+    ap.add_argument("--compare_queries", type=int, default=1024)
+    ap.add_argument("--steps", type=int, default=64)
+    args = ap.parse_args()
+    import ganleaks_amd as gl
+    from ganleaks_amd._lib import check
+    from ganleaks_amd.gan_models.dcgan.model_torch import Generator
+    if gl.device_count() < 1:
+        raise SystemExit("bench_wb.py needs a GPU")
+    ctx = gl.Context.get()
+    lib = ctx.lib
+    p, f = ctypes.c_void_p, ctypes.c_float
+    ev = [p(), p()]
+    for e in ev:
+        check(lib.gl_event_create(ctypes.byref(e)))
+
+    def timed(fn):
+        check(lib.gl_event_record(ctx.handle, ev[0]))
+        fn()
+        check(lib.gl_event_record(ctx.handle, ev[1]))
+        ms = ctypes.c_float()
+        check(lib.gl_event_elapsed_ms(ev[0], ev[1], ctypes.byref(ms)))
+        return ms.value
+
+    Q, nz, d = args.queries, 100, 3 * 64 * 64
+    sd = gl.synth.dcgan_state_dict(1234, features_g=args.ngf)
+    gen, gen0 = Generator(nz, 3, args.ngf), Generator(nz, 3, args.ngf)
+    gen.load_state_dict(sd)
+    gen0.load_state_dict(sd)
+    gen0.set_precision(0)
+    queries = gen.generate_u8(gl.synth.latent(2, Q))
+    z = ctx.to_device(gl.synth.latent(1, Q).reshape(Q, nz))
+    z_best = ctx.to_device(gl.synth.latent(1, Q).reshape(Q, nz))
+    m, v = ctx.zeros((Q, nz), np.float32), ctx.zeros((Q, nz), np.float32)
+    grad, loss, out = ctx.empty((Q, nz), np.float32), ctx.empty((Q,), np.float32), ctx.empty((Q, 3, 64, 64), np.float32)
+    one = ctx.to_device(np.ones((Q,), np.float32))
+    S_best, S_new = ctx.to_device(np.full((Q,), np.iinfo(np.int64).max, np.uint64)), ctx.empty((Q,), np.uint64)
+    j_new, accepted, work = ctx.empty((Q,), np.int32), ctx.empty((Q,), np.uint8), ctx.empty((16 * Q,), np.uint8)
+    state = {"t": 0, "images": None}
+
+    def forward32():
+        check(lib.gl_dcgan_forward(gen0._handle, p(z.ptr), Q, p(out.ptr), p(0)))
+
+    def l2_grad():
+        check(lib.gl_dcgan_l2_grad_z(gen._handle, p(z.ptr), p(queries.ptr), Q, p(grad.ptr), p(loss.ptr)))
+
+    def scoring():
+        state["images"] = gen.forward_device(z, False, True, check_range=False)[1]
+
+    def step():
+        state["t"] += 1
+        t = state["t"]
+        l2_grad()
+        check(lib.gl_wb_adam_step(ctx.handle, p(z.ptr), p(m.ptr), p(v.ptr), p(grad.ptr), Q, nz, f(0.05), f(0.9), f(0.999), f(1e-8),
+                                  f(1.0 / (1.0 - 0.9 ** t)), f(1.0 / (1.0 - 0.999 ** t)), f(4.0)))
+        scoring()
+        check(lib.gl_pbb_group_min(ctx.handle, p(queries.ptr), p(state["images"].ptr), Q, 1, d, p(S_new.ptr), p(j_new.ptr), p(work.ptr)))
+        check(lib.gl_pbb_accept(ctx.handle, p(z_best.ptr), p(one.ptr), p(S_best.ptr), p(z.ptr), p(S_new.ptr), p(j_new.ptr), Q, nz, 1, f(1.0), f(1.0),
+                                f(1.0), f(1.0), p(accepted.ptr)))
+
+    variants = [("forward fp32", forward32), ("l2_grad_z", l2_grad), ("scoring", scoring), ("step", step)]
+    for _, fn in variants:                       # warm-up: code object load, first touch, the workspaces and the transposed packs
+        fn()
+        ctx.sync()
+    ms = {label: [] for label, _ in variants}
+    for _ in range(args.rounds):
+        for label, fn in variants:
+            ms[label].append(timed(fn))
+    med = {label: float(np.median(t)) for label, t in ms.items()}
+    for label, _ in variants:
+        t = ms[label]
+        row = {"variant": label, "queries": Q, "ngf": args.ngf, "median_ms": round(med[label], 4), "min_ms": round(min(t), 4),
+               "max_ms": round(max(t), 4), "x_forward": round(med[label] / med["forward fp32"], 4), "rounds": args.rounds}
+        if label == "step":
+            row["scoring_share"] = round(med["scoring"] / med[label], 4)
+            row["steps_per_s"] = round(1e3 / med[label], 3)
+        print(json.dumps(row), flush=True)
+
+    # ---- the result: gradient descent against the gradient-free search, same start
+    n = args.compare_queries
+    if n > 0:
+        z_bank = gl.synth.latent(11, n).reshape(n, nz)
+        z_img = gl.synth.latent(12, n).reshape(n, nz)
+        z_img[: n // 2] = z_bank[: n // 2] + np.float32(0.5) * gl.synth.latent(13, n // 2).reshape(n // 2, nz)
+        q = gen.generate_u8(z_img).numpy()
+        z_init, _ = gl.pbb_init_from_bank(q, gen, z_bank, batch_size=64)
+        t0 = time.perf_counter()
+        _, _, S_wb, tr = gl.wb_attack(q, gen, z_init, steps=args.steps, history=True)
+        t_wb = time.perf_counter() - t0
+        t0 = time.perf_counter()
+        _, _, S_pbb = gl.pbb_attack(q, gen, z_init, rounds=32, population=64)
+        t_pbb = time.perf_counter() - t0
+        half = n // 2
+        print(json.dumps({"comparison": "final S from the same start", "queries": n, "ngf": args.ngf, "wb_steps": args.steps, "pbb_rounds": 32,
+                          "pbb_population": 64, "median_S_start_near": float(np.median(tr[0][:half])), "median_S_wb_near": float(np.median(S_wb[:half])),
+                          "median_S_pbb_near": float(np.median(S_pbb[:half])), "median_S_start_far": float(np.median(tr[0][half:])),
+                          "median_S_wb_far": float(np.median(S_wb[half:])), "median_S_pbb_far": float(np.median(S_pbb[half:])),
+                          "wb_below_pbb": int((S_wb < S_pbb).sum()), "wb_wall_s": round(t_wb, 3), "pbb_wall_s": round(t_pbb, 3)}), flush=True)
+
+
+if __name__ == "__main__":
+    main()

@@ -28,6 +28,14 @@ using gl_h3::v4f;
 
 constexpr int HBK_BYTES = 128;          // one K slice of 32 channels: 64 B hi + 64 B lo
 
+// XONCE (the 128 x 128 tile on a 16 x 16 grid = 8 rows of ONE image, 4 taps within one pixel: DCGAN's last hidden layer): the X half of a
+// buffer holds a 32-channel chunk of the band ONCE, in padded coordinates, for all 4 tap slices of the chunk.  Padded row P = 1..8 is band row
+// P - 1, P = 0 / 9 the image row above / below the band (the other half-image's, or zeros at the image border); LDS row of (P, x) is
+// 17 P + x + 1: row stride 17 with ONE shared zero column (x = 16 of a row is x = -1 of the next).  A tap (dy, dx) is then the row 17 dy + dx
+// further, zeros included: no per-piece select, no DMA for pixels outside the image, 4 + (2 of 4 waves: 1) X pieces per wave and chunk
+// instead of 16 (W: 16 as before).  The swizzle key of a row is its pixel's x & 7, which a shifted read recomputes.
+constexpr int h3_x_rows(int htp, bool xonce) { return xonce ? 10 * 17 + 1 : htp; }
+
 // WC x WP waves (channel direction x position direction), each owning TC x TP tiles of 16 x 16:
 //   <2,2,4,4>: 128 channels x 128 positions, 4 waves of 64 x 64, 64 KiB LDS (2 workgroups per CU)
 //   <1,4,4,4>: 64 channels x 256 positions, 4 waves, 80 KiB LDS (2 workgroups per CU): layers with <= 64 output columns
@@ -39,7 +47,11 @@ constexpr int HBK_BYTES = 128;          // one K slice of 32 channels: 64 B hi +
 // weight tile, DMA pieces spread over the weight tiles: bit-identical, 2-3 % SLOWER on every generator -- round 2), a 128 x 256
 // tile with 8 waves of 64 x 64, 256 x 256 with 4 waves of 128 x 128 (1 wave per SIMD), 128 x 512 / 128 x 256 tiles for 128-column
 // layers (and, round 2, the 128 x 512 tile WITH the fused RGB tail for DCGAN's last hidden layer, K loop free of spills: 193 -> 211-220 ms per step; that layer's K is only 32 slices long, and one 8-wave workgroup per CU cannot hide its long epilogue behind another workgroup's main loop the way two 128 x 128 ones do), a ring of three slices with counted s_waitcnt vmcnt(N), 4 workgroups per CU, staggered staging of the two wave halves,
-// halo staging (one staged pixel range per channel chunk, taps as shifted rows).  Also tried (round 2): GEMM rows in border-sorted order (the 9
+// halo staging on raster tiles with per-fragment register masks (one staged pixel range per channel chunk, taps as shifted rows: -36 % LDS-DMA
+// bytes, 1 % slower -- round 2; round 4 kept the idea where guard rows of zeros in LDS replace the masks, XONCE below, and measured it on the
+// two 256 x 256 forms as well, A/B in one process, DCGAN-64 forward of 16 384 images, 29.8 ms with a spread of 0.2 - 0.7 ms inside an arm: the
+// T4 form with a shifted tap read as another whole fragment, 32 -> 20 DMA pieces per wave and chunk, 0.06 ms slower / 0.16 ms faster in two runs; whole 8 x 8
+// images in padded coordinates, 32 -> 20 pieces in 147.5 KiB of LDS, 0.13 / 0.27 ms faster: both inside the spread, taken out again).  Also tried (round 2): GEMM rows in border-sorted order (the 9
 // classes first / inner / last row x column), so that tiles inside one class SKIP the K slices of their outside taps -- 23 % of the MFMAs of
 // DCGAN's 4 x 4 -> 8 x 8 layer, 12 % of the next one, bit-identical outputs.  Measured with clean K loops (tools/check_loop_spills.py): the
 // headline step went from 192 to 210-222 ms.  A class-pure tile of 256 rows spans 64 to 256 images instead of 16, and the re-use of an input
@@ -54,14 +66,16 @@ constexpr int HBK_BYTES = 128;          // one K slice of 32 channels: 64 B hi +
 //   convolution; every wave skips (nearly) the same number per slice, so the SIMDs stay in step.  Same images per tile as the raster
 //   order, hence the same L2 footprint (the border-sorted order above lost exactly that).  Adding a zero product changes no bit: outputs are
 //   identical to the raster form's (tests/test_gpu_dcgan.py).
-template <int WC, int WP, int TC = 4, int TP = 4, bool FUSE_TAIL = false, bool UP = false, bool T4 = false>
+template <int WC, int WP, int TC = 4, int TP = 4, bool FUSE_TAIL = false, bool UP = false, bool T4 = false, bool XONCE = false>
 __global__ void __launch_bounds__(64 * WC * WP, 2) gather_conv_h3_kernel(const GlGatherConv p, int m_tiles, int n_tiles, int phases)
 {
 #if __HIP_DEVICE_COMPILE__
     constexpr int HTC = 16 * TC * WC, HTP = 16 * TP * WP;        // tile: channels x positions (a wave owns TC x TP tiles of 16 x 16)
-    constexpr int W_BYTES = HTC * HBK_BYTES, X_BYTES = HTP * HBK_BYTES, BUF = W_BYTES + X_BYTES;
+    constexpr int XROWS = h3_x_rows(HTP, XONCE);
+    constexpr int W_BYTES = HTC * HBK_BYTES, X_BYTES = XROWS * HBK_BYTES, BUF = W_BYTES + X_BYTES;
     constexpr int NW = WC * WP;
     constexpr int PW = (HTC / 8) / NW, PX = (HTP / 8) / NW;   // 1-KiB staging pieces per wave and slice
+    static_assert(!XONCE || (WC == 2 && WP == 2 && TC == 4 && TP == 4 && PX == 4 && !UP && !T4), "XONCE: the 128 x 128 tile, position-waves of 4 image rows");
     static_assert(!T4 || (HTP == 256 && TP == 4 && WP == 4 && PX == 4 && !UP && !FUSE_TAIL), "T4: the 256-position tile with 4 position-waves of 4 fragments");
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [2][W | X]
 
@@ -157,6 +171,30 @@ __global__ void __launch_bounds__(64 * WC * WP, 2) gather_conv_h3_kernel(const G
         }
     };
 
+    // XONCE: the weights of slice kt alone; piece i of this wave = half (i & 1) of band row 2 wave + (i >> 1), unshifted; and the image row
+    // above (which = 0) / below (1) the band, one half per wave.  Rows outside the image are zeroed with the guards, once.
+    const int band = XONCE ? (int)((m0 >> 7) & 1) : 0;
+    auto stage_w = [&](int kt, char *buf) {
+#pragma unroll
+        for (int i = 0; i < PW; ++i)
+            __builtin_amdgcn_raw_ptr_buffer_load_lds(w_rsrc, (gl_lptr)(buf + (wave * PW + i) * 1024), 16, w_voff0, (unsigned)kt * 128u + (unsigned)i * w_step, 0, 0);
+    };
+    auto stage_x1 = [&](int cc, int i, char *buf) {
+        const int prow = (1 + 2 * wave + (i >> 1)) * 17 + (i & 1) * 8 + 1;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (gl_lptr)(buf + W_BYTES + prow * HBK_BYTES), 16, x_voff0,
+                                                 lead_bytes + (unsigned)cc * 128u + (unsigned)i * x_step, 0, 0);
+    };
+    auto stage_halo = [&](int cc, char *buf) {
+        const int which = wave >> 1, half = wave & 1;
+        if (which == band) return;                         // above the first band / below the second: outside the image
+        // x_voff0 is the lane's pixel of the wave's first piece, 32 * wave positions into the tile: the halo pixel lies `delta` positions from it
+        // (inside the image, so the sum is a true offset even where delta is negative)
+        const int delta = (which ? 128 : -16) + half * 8 - wave * 32;
+        const int prow = (which ? 9 : 0) * 17 + half * 8 + 1;
+        const unsigned voff = x_voff0 == kOOB ? kOOB : x_voff0 + (unsigned)(delta * p.Cin * 4);
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(x_rsrc, (gl_lptr)(buf + W_BYTES + prow * HBK_BYTES), 16, voff, lead_bytes + (unsigned)cc * 128u, 0, 0);
+    };
+
     v4f acc[TC][TP];
 #pragma unroll
     for (int i = 0; i < TC; ++i)
@@ -164,10 +202,19 @@ __global__ void __launch_bounds__(64 * WC * WP, 2) gather_conv_h3_kernel(const G
         for (int j = 0; j < TP; ++j) acc[i][j] = (v4f){0.f, 0.f, 0.f, 0.f};
 
     const int frow0 = lane0 & 15, fk0 = lane0 >> 4;
-    auto compute = [&](const char *cur, int kt) {
+    // XONCE: xcur is the buffer whose X half holds the chunk, xtap the slice's tap
+    auto compute = [&](const char *cur, int kt, const char *xcur = nullptr, int xtap = 0) {
         const char *lw = cur + (wc * 16 * TC) * HBK_BYTES;
-        const char *lx = cur + W_BYTES + (wp_ * 16 * TP) * HBK_BYTES;
+        const char *lx = XONCE ? xcur + W_BYTES : cur + W_BYTES + (wp_ * 16 * TP) * HBK_BYTES;
         v8h w_hi[TC], w_lo[TC], x_hi[TP], x_lo[TP];
+        int xr_hi = 0, xr_lo = 0;                          // XONCE: the lane's shifted row of fragment 0 (a fragment is one image row), with its slot
+        if constexpr (XONCE) {
+            const int dy = (int)((tdy >> (2 * xtap)) & 3u) - 1, dx = (int)((tdx >> (2 * xtap)) & 3u) - 1;
+            const int key = (frow0 + dx) & 7;              // x + dx = -1 or 16 is the zero column: any slot
+            const int row = (1 + 4 * wp_ + dy) * 17 + dx + 1 + frow0;
+            xr_hi = row * HBK_BYTES + ((fk0 ^ key) << 4);
+            xr_lo = row * HBK_BYTES + (((4 + fk0) ^ key) << 4);
+        }
         unsigned skip = 0;                                 // T4: bit j = fragment j of this wave lies outside the image for this slice's tap
         if constexpr (T4) {
             const int tap = kt % p.ntaps;
@@ -187,8 +234,13 @@ __global__ void __launch_bounds__(64 * WC * WP, 2) gather_conv_h3_kernel(const G
 #pragma unroll
         for (int j = 0; j < TP; ++j) {
             const int r = j * 16 + frow0;
-            x_hi[j] = *reinterpret_cast<const v8h *>(lx + r * HBK_BYTES + ((fk0 ^ (r & 7)) << 4));
-            x_lo[j] = *reinterpret_cast<const v8h *>(lx + r * HBK_BYTES + (((4 + fk0) ^ (r & 7)) << 4));
+            if constexpr (XONCE) {
+                x_hi[j] = *reinterpret_cast<const v8h *>(lx + xr_hi + j * 17 * HBK_BYTES);
+                x_lo[j] = *reinterpret_cast<const v8h *>(lx + xr_lo + j * 17 * HBK_BYTES);
+            } else {
+                x_hi[j] = *reinterpret_cast<const v8h *>(lx + r * HBK_BYTES + ((fk0 ^ (r & 7)) << 4));
+                x_lo[j] = *reinterpret_cast<const v8h *>(lx + r * HBK_BYTES + (((4 + fk0) ^ (r & 7)) << 4));
+            }
         }
         if constexpr (T4) {
             // fragment-major, so that a skipped fragment is one wave-uniform branch around 3 TC MFMAs (the zero products it drops change no bit)
@@ -213,11 +265,40 @@ __global__ void __launch_bounds__(64 * WC * WP, 2) gather_conv_h3_kernel(const G
                 }
         }
     };
-    stage(0, smem);
-    for (int kt = 0; kt < nk; ++kt) {
-        __syncthreads();
-        if (kt + 1 < nk) stage(kt + 1, smem + ((kt + 1) & 1) * BUF);
-        compute(smem + (kt & 1) * BUF, kt);
+    if constexpr (XONCE) {
+        // the zero column and the halo row outside the image, in both X images, once: no DMA piece ever targets them
+        for (int e = tid0; e < XROWS * 8; e += 64 * NW) {
+            const int q = (e >> 3) - 1;                    // 17 P + x
+            if (q < 0 || q % 17 == 16 || q / 17 == (band ? 9 : 0)) {
+                *reinterpret_cast<uint4 *>(smem + W_BYTES + e * 16) = make_uint4(0u, 0u, 0u, 0u);
+                *reinterpret_cast<uint4 *>(smem + BUF + W_BYTES + e * 16) = make_uint4(0u, 0u, 0u, 0u);
+            }
+        }
+        // the X half of buffer (cc & 1) holds chunk cc for its 4 slices; the pieces of chunk cc + 1 go out one per slice of chunk cc (the halo
+        // piece with the second), into the half that chunk cc - 1 was last read from before this chunk's first barrier
+        stage_w(0, smem);
+#pragma unroll
+        for (int i = 0; i < PX; ++i) stage_x1(0, i, smem);
+        stage_halo(0, smem);
+        const int nchunks = p.Cin / 32;
+        int tap = 0, cc = 0;
+        for (int kt = 0; kt < nk; ++kt) {
+            __syncthreads();
+            if (kt + 1 < nk) stage_w(kt + 1, smem + ((kt + 1) & 1) * BUF);
+            if (cc + 1 < nchunks) {
+                stage_x1(cc + 1, tap, smem + ((cc + 1) & 1) * BUF);
+                if (tap == 1) stage_halo(cc + 1, smem + ((cc + 1) & 1) * BUF);
+            }
+            compute(smem + (kt & 1) * BUF, kt, smem + (cc & 1) * BUF, tap);
+            if (++tap == 4) { tap = 0; ++cc; }
+        }
+    } else {
+        stage(0, smem);
+        for (int kt = 0; kt < nk; ++kt) {
+            __syncthreads();
+            if (kt + 1 < nk) stage(kt + 1, smem + ((kt + 1) & 1) * BUF);
+            compute(smem + (kt & 1) * BUF, kt);
+        }
     }
 
     // ---- epilogue.  C tile (16 x 16): column (position) = lane & 15, row (channel) = 4 * (lane >> 4) + reg.
@@ -340,7 +421,13 @@ __global__ void __launch_bounds__(256) split_rows_kernel(const float *__restrict
 
 }  // namespace
 
-template <int WC, int WP, int TC = 4, int TP = 4, bool FUSE_TAIL = false, bool UP = false, bool T4 = false>
+#ifdef GL_TUNING
+// tuning build only: how many launches took the staged-once form (tests/test_gpu_conv_xonce.py: the A/B arms really differ)
+static long long h3_xonce_launches = 0;
+extern "C" long long gl_tune_h3_xonce_launches(void) { return h3_xonce_launches; }
+#endif
+
+template <int WC, int WP, int TC = 4, int TP = 4, bool FUSE_TAIL = false, bool UP = false, bool T4 = false, bool XONCE = false>
 static int launch_h3(gl_ctx *ctx, const GlGatherConv &p, int phases)
 {
     if constexpr (!UP && !FUSE_TAIL && !T4) {
@@ -351,15 +438,28 @@ static int launch_h3(gl_ctx *ctx, const GlGatherConv &p, int phases)
         const bool plain = !p.up && !p.tail_w && !p.tap_V && !p.rgb_out && p.pixnorm_act == 0.0f && !p.planar;
         if (plain && p.H == 4 && p.W == 4 && gl_tuning_int("GL_H3_T4", 1)) return launch_h3<WC, WP, TC, TP, false, false, true>(ctx, p, phases);
     }
+    if constexpr (WC == 2 && WP == 2 && TC == 4 && TP == 4 && !UP && FUSE_TAIL && !T4 && !XONCE) {
+        // 8 rows of one 16 x 16 image per tile and a ConvTranspose phase (4 taps, all within one pixel): the input chunk staged once per tile
+        bool near = p.ntaps == 4;
+        for (int ph = 0; ph < phases && near; ++ph)
+            for (int t = 0; t < 4; ++t) near = near && ((p.tap_dy[ph] >> (2 * t)) & 3u) != 3u && ((p.tap_dx[ph] >> (2 * t)) & 3u) != 3u;
+        const bool plain = !p.up && !p.tap_V && !p.rgb_out && p.pixnorm_act == 0.0f && !p.planar;
+        // positions % 256 == 0: every 128-position tile is a whole half-image (the kernel takes the band from the tile index and the halo row
+        // from the same image)
+        if (plain && near && p.H == 16 && p.W == 16 && p.positions % 256 == 0 && gl_tuning_int("GL_H3_XONCE", 1)) return launch_h3<WC, WP, TC, TP, true, false, false, true>(ctx, p, phases);
+    }
     constexpr int HTC = 16 * TC * WC, HTP = 16 * TP * WP;
     const int64_t m_tiles = gl_ceil_div(p.positions, HTP);
     const int n_tiles = (int)gl_ceil_div(p.cols, HTC);       // weight rows are padded to cols_pad >= n_tiles * HTC
     GL_REQUIRE(m_tiles * n_tiles * phases < (1ll << 31), "gather_conv_h3: grid too large");
-    constexpr int lds = 2 * (HTC + HTP) * HBK_BYTES;
-    auto kern = gather_conv_h3_kernel<WC, WP, TC, TP, FUSE_TAIL, UP, T4>;
+    constexpr int lds = 2 * (HTC + h3_x_rows(HTP, XONCE)) * HBK_BYTES;
+    auto kern = gather_conv_h3_kernel<WC, WP, TC, TP, FUSE_TAIL, UP, T4, XONCE>;
     GL_ONCE_PER_DEVICE(ctx, \
         GL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds)););
     gl_prof_scope prof_(ctx, GL_PROF_GATHER_CONV);
+#ifdef GL_TUNING
+    if (XONCE) ++h3_xonce_launches;
+#endif
     hipLaunchKernelGGL(kern, dim3((unsigned)(m_tiles * n_tiles * phases)), dim3(64 * WC * WP), lds, ctx->stream, p, (int)m_tiles, n_tiles, phases);
     GL_LAUNCH_CHECK();
     return GL_OK;

@@ -112,6 +112,16 @@ void gl_pack_tail_weights_host(const float *w48xC, int channels, float scale, vo
 static inline int64_t gl_conv_k_index(int tap, int ci, int ntaps) { return ((int64_t)(ci / 32) * ntaps + tap) * 32 + (ci % 32); }
 
 int gl_launch_gather_conv(gl_ctx *ctx, const GlGatherConv &p, int phases);
+#ifdef GL_TUNING
+// tuning build only: which instantiation the last convolution launch took (gl_tune_conv_layer reports it; tests/test_gpu_conv_layers.py asserts
+// it for every case, so that a moved dispatch threshold cannot put a case onto another kernel unnoticed)
+//   fp32:  0x100 | 0 (<2,2,2,2>) or 1 (<4,1,1,2>)
+//   split: 0x200 | tile (0 <2,2>, 1 <1,4>, 2 <2,4,8,4>, 5 <1,8,8,4>, 3 / 4 the fused-tail forms of 0 / 1) | 0x10 UP | 0x20 T4 | 0x40 XONCE
+//   halo:  0x400 | wave columns (1 or 2) | 0x10 RING
+extern int gl_tune_conv_form;
+// gl_launch_gather_conv + the fp32 id (set from the dispatch rule, not inside launch_gather: see the end of gl_conv.hip)
+int gl_tune_gather_conv(gl_ctx *ctx, const GlGatherConv &p, int phases);
+#endif
 
 // split-fp16 variant (gl_conv_h3.hip): `in` and `wpack` are in the split layout (see that file); same parameter block
 int gl_launch_gather_conv_h3(gl_ctx *ctx, const GlGatherConv &p, int phases);

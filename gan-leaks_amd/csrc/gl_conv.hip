@@ -400,3 +400,17 @@ int gl_launch_col2im_rgb_tanh(gl_ctx *ctx, const float *P, int64_t ldp, int64_t 
     GL_LAUNCH_CHECK();
     return GL_OK;
 }
+
+#ifdef GL_TUNING
+// Tuning build only (gl_conv.h: gl_tune_conv_form).  launch_h3 and launch_halo record the instantiation they launch.  launch_gather cannot:
+// any line added above gl_launch_col2im_rgb_tanh moves the __LINE__ inside its GL_LAUNCH_CHECK(), and the production object has to stay
+// byte for byte what it was.  So the fp32 id is set here, at the end of the file, from the one property gl_launch_gather_conv dispatches on;
+// whoever changes that rule changes this line with it.
+int gl_tune_conv_form = 0;
+int gl_tune_gather_conv(gl_ctx *ctx, const GlGatherConv &p, int phases)
+{
+    const int rc = gl_launch_gather_conv(ctx, p, phases);
+    if (rc == GL_OK && p.positions > 0) gl_tune_conv_form = 0x100 | (p.cols_pad % 128 == 0 ? 0 : 1);
+    return rc;
+}
+#endif

@@ -458,7 +458,7 @@ static int launch_h3(gl_ctx *ctx, const GlGatherConv &p, int phases)
         GL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds)););
     gl_prof_scope prof_(ctx, GL_PROF_GATHER_CONV);
 #ifdef GL_TUNING
-    if (XONCE) ++h3_xonce_launches;
+    if (XONCE) ++h3_xonce_launches; gl_tune_conv_form = 0x200 | (TC == 8 ? (WC == 2 ? 2 : 5) : (WC == 2 ? 0 : 1) + (FUSE_TAIL ? 3 : 0)) | (UP ? 0x10 : 0) | (T4 ? 0x20 : 0) | (XONCE ? 0x40 : 0);   // on this line: a line more would move the __LINE__ of the checks below and with it the production object
 #endif
     hipLaunchKernelGGL(kern, dim3((unsigned)(m_tiles * n_tiles * phases)), dim3(64 * WC * WP), lds, ctx->stream, p, (int)m_tiles, n_tiles, phases);
     GL_LAUNCH_CHECK();

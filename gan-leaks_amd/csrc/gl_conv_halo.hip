@@ -247,6 +247,9 @@ int launch_halo(gl_ctx *ctx, const GlGatherConv &p)
     gl_prof_scope prof_(ctx, GL_PROF_GATHER_CONV);
     hipLaunchKernelGGL(kern, dim3((unsigned)total), dim3(256 * WC), lds, ctx->stream, p, bx, bx * by, (unsigned)total, gl_tuning_int("GL_HALO_DIAG", 0));
     GL_LAUNCH_CHECK();
+#ifdef GL_TUNING      // below the file's last __LINE__ (GL_LAUNCH_CHECK): the production object stays what it was
+    gl_tune_conv_form = 0x400 | WC | (RING ? 0x10 : 0);
+#endif
     return GL_OK;
 }
 

@@ -1,4 +1,6 @@
 // TUNING BUILD ONLY (linked into libganleaks_hip_tuning.so, never into libganleaks_hip.so; not part of include/ganleaks.h).
+// Two entries: gl_tune_winograd_bound (a timing experiment, below) and gl_tune_conv_layer (one convolution launch on host arrays, for the
+// per-layer tests; at the end of the file).
 //
 // gl_tune_winograd_bound: the measured UPPER bound of what Winograd F(2x2,3x3) could buy on the split-fp16 convolution path (VERDICT r2
 // "Next 1").  F(2x2,3x3) replaces a 3x3 convolution over P positions by 16 independent GEMMs  M_j = U_j (C_out x C_in) . V_j (C_in x P/4)
@@ -123,4 +125,160 @@ extern "C" int gl_tune_winograd_bound(gl_ctx *ctx, int Cin, int Cout, int H, int
 #undef TUNE_HIP
     cleanup();
     return rc;
+}
+
+// gl_tune_conv_layer: ONE launch of gl_launch_gather_conv (kernel 0) or gl_launch_gather_conv_h3 (kernel 1) on a problem given as plain host
+// arrays, for tests/test_gpu_conv_layers.py, which compares the whole output tensor with a float64 convolution.  The entry packs the operands the
+// way production code does (fp32: gl_conv_k_index order padded to cols_pad; split: gl_split_weights_host / gl_launch_split_rows /
+// gl_pack_tail_weights_host with the scale conventions of dcgan_prepare_h3 -- stored activations carry kTuneActScale, weights 2^wexp,
+// scale' = s / 2^wexp, shift' = t * kTuneActScale; fp32 output of the split kernel holds true values: scale' = s / (2^wexp * kTuneActScale)),
+// and returns the RAW output bytes: decoding the split and planar layouts is the test's job, so the layouts are under test as well.
+// Input and output each sit inside a larger allocation: in_guard bytes of `poison` (fp32 values, split like the input on the split path) on
+// both sides of the input -- a read that should have been a zero fill returns poison, not something arbitrary -- and 4 KiB of `sentinel` bytes on
+// both sides of the output, which is itself pre-filled with `sentinel`; the guards come back so that the caller can see they are untouched.
+struct GlTuneConvLayer {                 // mirrored field by field in tests/conv_layer_common.py
+    int32_t kernel, phases, ntaps, up;
+    int64_t n_img;
+    int32_t H, W, Cin, cols, cols_pad;
+    int32_t Ho, Wo, omul;
+    uint32_t tap_dy[4], tap_dx[4];
+    int32_t oy[4], ox[4];
+    int32_t planar, out_mode, cmod, act;
+    int64_t ld_planar;
+    int32_t wexp, tail_wexp;
+    const float *in;                     // [n_img][H >> up][W >> up][Cin]
+    const float *w;                      // natural order [phases][cols][ntaps][Cin]
+    const float *scale, *shift;          // [cmod], true values
+    const float *residual;               // nullptr or [n_img][Ho][Wo][cols]
+    const float *tail_w;                 // nullptr or [48][cols]: the fused tail; the output is then tail_out [48][n_img * Ho * Wo]
+    float poison;
+    int32_t sentinel;                    // byte value
+    int64_t in_guard;                    // bytes of each input guard: >= 2 (W + 1) Cin 4 rounded up to 4 KiB, a multiple of Cin * 4
+    int64_t out_bytes;                   // must be what the problem writes (checked)
+    void *out;                           // <- out_bytes
+    void *in_guards;                     // <- 2 * in_guard bytes: below | above the input, read back after the launch
+    void *out_guards;                    // <- 2 * 4096 bytes: below | above the output
+    int64_t sat_delta;                   // <- change of the context's split-store saturation counter
+    int32_t form;                        // <- gl_tune_conv_form of the launch
+    int32_t reserved_i[7];               // room for the fused PixelNorm / toRGB / LPIPS tap fields
+    void *reserved_p[8];
+};
+
+static const float kTuneActScale = 16.0f;        // gl_dcgan.hip kActScale
+
+extern "C" int gl_tune_conv_layer(gl_ctx *ctx, GlTuneConvLayer *q)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && q && q->in && q->w && q->scale && q->shift && q->out && q->in_guards && q->out_guards, "gl_tune_conv_layer: NULL argument");
+    GL_REQUIRE((q->kernel == 0 || q->kernel == 1) && q->phases >= 1 && q->phases <= 4 && q->ntaps >= 1 && q->ntaps <= 16 && q->n_img > 0 && q->H > 0 &&
+                   q->W > 0 && q->Cin > 0 && q->Cin % 32 == 0 && q->cols > 0 && q->cols <= q->cols_pad && q->cmod > 0 && (q->up == 0 || q->up == 1) &&
+                   q->Ho > 0 && q->Wo > 0 && q->omul >= 1,
+               "gl_tune_conv_layer: bad problem");
+    GL_REQUIRE(q->kernel == 1 || (!q->tail_w && q->out_mode == 0), "gl_tune_conv_layer: split output and the fused tail are the split kernel's");
+    GL_REQUIRE(!q->tail_w || q->cols == 64 || q->cols == 128, "gl_tune_conv_layer: the fused tail takes 64 or 128 channels");
+    for (int ph = 0; ph < q->phases; ++ph)
+        GL_REQUIRE(q->oy[ph] >= 0 && q->ox[ph] >= 0 && (q->H - 1) * q->omul + q->oy[ph] < q->Ho && (q->W - 1) * q->omul + q->ox[ph] < q->Wo,
+                   "gl_tune_conv_layer: the output map of phase %d leaves the %d x %d output", ph, q->Ho, q->Wo);
+    const bool h3 = q->kernel == 1;
+    const int Hs = q->H >> q->up, Ws = q->W >> q->up, K = q->ntaps * q->Cin;
+    const int64_t positions = q->n_img * q->H * q->W, opos = q->n_img * q->Ho * q->Wo;
+    const int64_t in_bytes = q->n_img * Hs * Ws * q->Cin * 4;
+    const int64_t lead = ((2ll * (q->W + 1) * q->Cin * 4) + 4095) / 4096 * 4096;
+    GL_REQUIRE(q->in_guard >= lead && q->in_guard % (q->Cin * 4) == 0, "gl_tune_conv_layer: in_guard=%lld must be >= %lld and a multiple of Cin * 4",
+               (long long)q->in_guard, (long long)lead);
+    if (q->planar) GL_REQUIRE(q->ld_planar >= opos && opos == positions, "gl_tune_conv_layer: planar output needs ld_planar >= positions and an identity map");
+    const int64_t out_bytes = q->tail_w ? 48 * opos * 4 : q->planar ? (int64_t)q->cols * q->ld_planar * 4 : opos * q->cols * 4;
+    GL_REQUIRE(q->out_bytes == out_bytes, "gl_tune_conv_layer: out_bytes=%lld, the problem writes %lld", (long long)q->out_bytes, (long long)out_bytes);
+    constexpr int64_t OG = 4096;
+    const int64_t in_total = in_bytes + 2 * q->in_guard;
+    const size_t w_elems = (size_t)q->phases * q->cols_pad * K;
+
+    char *d_in = nullptr, *d_split = nullptr, *d_out = nullptr, *d_tail = nullptr;
+    float *d_w = nullptr, *d_scale = nullptr, *d_shift = nullptr, *d_res = nullptr;
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d_in); (void)hipFree(d_split); (void)hipFree(d_out); (void)hipFree(d_tail);
+        (void)hipFree(d_w); (void)hipFree(d_scale); (void)hipFree(d_shift); (void)hipFree(d_res);
+    };
+#define TUNE_HIP(e) do { if ((e) != hipSuccess) { gl_set_error("gl_tune_conv_layer: %s failed", #e); cleanup(); return GL_ERR_HIP; } } while (0)
+#define TUNE_RC(e) do { const int rc_ = (e); if (rc_ != GL_OK) { cleanup(); return rc_; } } while (0)
+    TUNE_HIP(hipMalloc((void **)&d_in, (size_t)in_total));
+    if (h3) TUNE_HIP(hipMalloc((void **)&d_split, (size_t)in_total));
+    TUNE_HIP(hipMalloc((void **)&d_out, (size_t)(out_bytes + 2 * OG)));
+    TUNE_HIP(hipMalloc((void **)&d_w, w_elems * 4));
+    TUNE_HIP(hipMalloc((void **)&d_scale, (size_t)q->cmod * 4));
+    TUNE_HIP(hipMalloc((void **)&d_shift, (size_t)q->cmod * 4));
+    if (q->residual) TUNE_HIP(hipMalloc((void **)&d_res, (size_t)(opos * q->cols * 4)));
+    if (q->tail_w) TUNE_HIP(hipMalloc((void **)&d_tail, 24 * 1024));
+    {
+        // input: [guard | tensor | guard] as fp32 rows of Cin values; the split path converts all of it, guards included
+        std::vector<float> guard((size_t)(q->in_guard / 4), q->poison);
+        TUNE_HIP(hipMemcpyAsync(d_in, guard.data(), (size_t)q->in_guard, hipMemcpyHostToDevice, ctx->stream));
+        TUNE_HIP(hipMemcpyAsync(d_in + q->in_guard, q->in, (size_t)in_bytes, hipMemcpyHostToDevice, ctx->stream));
+        TUNE_HIP(hipMemcpyAsync(d_in + q->in_guard + in_bytes, guard.data(), (size_t)q->in_guard, hipMemcpyHostToDevice, ctx->stream));
+        TUNE_HIP(hipStreamSynchronize(ctx->stream));
+        if (h3) TUNE_RC(gl_launch_split_rows(ctx, reinterpret_cast<const float *>(d_in), in_total / (q->Cin * 4), q->Cin, q->Cin, kTuneActScale, d_split));
+        // weights: natural [phase][col][tap][ci] -> [phase][cols_pad][gl_conv_k_index(tap, ci)], rows beyond cols zero
+        std::vector<float> pk(w_elems, 0.0f);
+        for (int ph = 0; ph < q->phases; ++ph)
+            for (int c = 0; c < q->cols; ++c)
+                for (int t = 0; t < q->ntaps; ++t)
+                    for (int ci = 0; ci < q->Cin; ++ci)
+                        pk[((size_t)ph * q->cols_pad + c) * K + gl_conv_k_index(t, ci, q->ntaps)] = q->w[(((size_t)ph * q->cols + c) * q->ntaps + t) * q->Cin + ci];
+        if (h3) {
+            std::vector<float> sp(w_elems);
+            gl_split_weights_host(pk.data(), (size_t)q->phases * q->cols_pad, (size_t)K, std::ldexp(1.0f, q->wexp), sp.data());
+            pk.swap(sp);
+        }
+        TUNE_HIP(hipMemcpy(d_w, pk.data(), w_elems * 4, hipMemcpyHostToDevice));
+        std::vector<float> sc(q->scale, q->scale + q->cmod), sh(q->shift, q->shift + q->cmod);
+        if (h3) {
+            const bool stored = q->out_mode == 2 || q->tail_w;      // the output (or the tail's operand) carries kTuneActScale
+            for (int i = 0; i < q->cmod; ++i) {
+                sc[i] = std::ldexp(sc[i], -q->wexp) / (stored ? 1.0f : kTuneActScale);
+                sh[i] = stored ? sh[i] * kTuneActScale : sh[i];
+            }
+        }
+        TUNE_HIP(hipMemcpy(d_scale, sc.data(), (size_t)q->cmod * 4, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_shift, sh.data(), (size_t)q->cmod * 4, hipMemcpyHostToDevice));
+        if (q->residual) TUNE_HIP(hipMemcpy(d_res, q->residual, (size_t)(opos * q->cols * 4), hipMemcpyHostToDevice));
+        if (q->tail_w) {
+            std::vector<float> img(24 * 1024 / 4, 0.0f);
+            gl_pack_tail_weights_host(q->tail_w, q->cols, std::ldexp(1.0f, q->tail_wexp), img.data());
+            TUNE_HIP(hipMemcpy(d_tail, img.data(), 24 * 1024, hipMemcpyHostToDevice));
+        }
+    }
+    TUNE_HIP(hipMemsetAsync(d_out, q->sentinel & 0xFF, (size_t)(out_bytes + 2 * OG), ctx->stream));
+    int sat0 = 0, sat1 = 0;
+    TUNE_HIP(hipStreamSynchronize(ctx->stream));
+    TUNE_HIP(hipMemcpy(&sat0, ctx->h3_sat, 4, hipMemcpyDeviceToHost));
+
+    GlGatherConv p = {};
+    p.in = reinterpret_cast<const float *>((h3 ? d_split : d_in) + q->in_guard);
+    p.positions = positions; p.H = q->H; p.W = q->W; p.Cin = q->Cin; p.up = q->up;
+    p.wpack = d_w; p.cols = q->cols; p.cols_pad = q->cols_pad; p.ntaps = q->ntaps;
+    for (int i = 0; i < 4; ++i) { p.tap_dy[i] = q->tap_dy[i]; p.tap_dx[i] = q->tap_dx[i]; p.oy[i] = q->oy[i]; p.ox[i] = q->ox[i]; }
+    p.out = reinterpret_cast<float *>(d_out + OG); p.Ho = q->Ho; p.Wo = q->Wo; p.omul = q->omul;
+    p.planar = q->planar; p.ld_planar = q->ld_planar; p.out_mode = q->out_mode;
+    p.scale = d_scale; p.shift = d_shift; p.cmod = q->cmod; p.act = q->act; p.residual = d_res; p.zero = ctx->zero_page;
+    if (q->tail_w) {
+        p.tail_w = d_tail; p.tail_out = reinterpret_cast<float *>(d_out + OG); p.tail_ld = opos;
+        p.tail_scale = std::ldexp(1.0f / kTuneActScale, -q->tail_wexp);       // `out` is ignored by the fused-tail forms; it stays inside the guarded block
+    }
+    gl_tune_conv_form = 0;
+    TUNE_RC(h3 ? gl_launch_gather_conv_h3(ctx, p, q->phases) : gl_tune_gather_conv(ctx, p, q->phases));
+    TUNE_HIP(hipStreamSynchronize(ctx->stream));
+    q->form = gl_tune_conv_form;
+    TUNE_HIP(hipMemcpy(&sat1, ctx->h3_sat, 4, hipMemcpyDeviceToHost));
+    q->sat_delta = (int64_t)sat1 - sat0;
+    char *d_src = h3 ? d_split : d_in;
+    TUNE_HIP(hipMemcpy(q->in_guards, d_src, (size_t)q->in_guard, hipMemcpyDeviceToHost));
+    TUNE_HIP(hipMemcpy(reinterpret_cast<char *>(q->in_guards) + q->in_guard, d_src + q->in_guard + in_bytes, (size_t)q->in_guard, hipMemcpyDeviceToHost));
+    TUNE_HIP(hipMemcpy(q->out_guards, d_out, (size_t)OG, hipMemcpyDeviceToHost));
+    TUNE_HIP(hipMemcpy(reinterpret_cast<char *>(q->out_guards) + OG, d_out + OG + out_bytes, (size_t)OG, hipMemcpyDeviceToHost));
+    TUNE_HIP(hipMemcpy(q->out, d_out + OG, (size_t)out_bytes, hipMemcpyDeviceToHost));
+#undef TUNE_HIP
+#undef TUNE_RC
+    cleanup();
+    return GL_OK;
 }

@@ -133,6 +133,8 @@ SIGNATURES = {
     "gl_pggan_set_chunk": (_i, [_p, _i64]),
     "gl_pggan_set_precision": (_i, [_p, _i]),
     "gl_pggan_forward": (_i, [_p, _p, _i64, _i, ctypes.c_float, _p, _p]),
+    "gl_pggan_vjp_z": (_i, [_p, _p, _i64, _i, ctypes.c_float, _p, _p, _p]),
+    "gl_pggan_l2_grad_z": (_i, [_p, _p, _p, _i64, _i, ctypes.c_float, _p, _p]),
     "gl_medgan_create": (_i, [_p, _i, _i, _i, _i, _pp]),
     "gl_medgan_destroy": (_i, [_p]),
     "gl_medgan_set_gen_block": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, ctypes.c_float]),

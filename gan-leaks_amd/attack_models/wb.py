@@ -8,10 +8,13 @@ so that eval_roc.py scores the result unchanged.  The search is ganleaks_amd.wb.
 
     python -m ganleaks_amd.attack_models.wb --local_config config_attack_fbb.yaml --gan {dcgan,wgangp} --generator_path generator.pth
            [--nz --ngf] [--noise_path npz | --num_init N --init_seed s] [--steps --lr --beta1 --beta2] [--BATCH_SIZE]
+    python -m ganleaks_amd.attack_models.wb ... --gan pggan --pg_steps N [--alpha a] [--in_channels C] --nz Z --resolution R ...
 
---gan, --generator_path  the generator class and its state dict (what the training scripts save as generator.pth); PGGAN and VAEGAN have
-                         no backward pass and are refused
+--gan, --generator_path  the generator class and its state dict (what the training scripts save as generator.pth); VAEGAN has no backward
+                         pass and is refused
 --nz, --ngf              latent length and width (features_g)
+--pg_steps, --alpha, --in_channels   PGGAN only: the depth (images of 4 * 2^pg_steps pixels; no default, --steps is the descent's), the
+                         fade-in weight of the last block (default 1) and the channel count of the first block (default 256)
 --noise_path             the .npz the generate branches write under npz_noise/ (array `noise`): the latents of the sample bank
 --num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
 --BATCH_SIZE             only the first (N // BATCH_SIZE) * BATCH_SIZE latents take part in the start, as in fbb.py:77
@@ -37,6 +40,9 @@ from ..wb import wb_attack
 from .fbb import update_args  # noqa: F401  (the YAML overlay of the command line)
 from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, save_files
 
+# options added after params.txt got its form: an unused one leaves the file as it was before the option existed
+LATER_OPTIONS = ("pg_steps", "alpha", "in_channels")
+
 
 def parse_arguments(argv=None):
     parser = argparse.ArgumentParser()
@@ -47,7 +53,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--resolution', '-resolution', type=int, default=64, help='images that differ are resized to this square size')
     parser.add_argument('--BATCH_SIZE', type=int, default=30)
     parser.add_argument('--local_config', type=str, default=None)
-    parser.add_argument('--gan', type=str, default='dcgan', help='the generator class: dcgan or wgangp')
+    parser.add_argument('--gan', type=str, default='dcgan', help='the generator class: dcgan, wgangp or pggan')
     parser.add_argument('--generator_path', type=str, default=None, help="the generator's state dict (generator.pth)")
     parser.add_argument('--nz', type=int, default=100, help='length of a latent vector')
     parser.add_argument('--ngf', type=int, default=64, help='width parameter of the generator (features_g)')
@@ -55,6 +61,9 @@ def parse_arguments(argv=None):
     parser.add_argument('--noise_path', type=str, default=None, help="npz with the bank's latents (array 'noise'), as the generate branches write it")
     parser.add_argument('--num_init', type=int, default=None, help='without --noise_path: draw this many starting latents')
     parser.add_argument('--init_seed', type=int, default=0, help='seed of the drawn starting latents')
+    parser.add_argument('--pg_steps', type=int, default=None, help='pggan: resolution steps (4 * 2^pg_steps pixels); no default')
+    parser.add_argument('--alpha', type=float, default=None, help='pggan: fade-in weight of the last block (default 1)')
+    parser.add_argument('--in_channels', type=int, default=None, help='pggan: channel count of the first block (default 256)')
     parser.add_argument('--steps', type=int, default=64, help='gradient steps')
     parser.add_argument('--lr', type=float, default=0.05, help="Adam's step size")
     parser.add_argument('--beta1', type=float, default=0.9)
@@ -64,9 +73,21 @@ def parse_arguments(argv=None):
 
 def _request(args):
     """what can be refused before any file is read"""
-    if args.gan not in ("dcgan", "wgangp"):
-        raise SystemExit("--gan must be dcgan or wgangp, got %r: the backward pass is built for the DCGAN / WGAN-GP generator only (PGGAN and "
-                         "VAEGAN are not)" % (args.gan,))
+    if args.gan not in ("dcgan", "wgangp", "pggan"):
+        raise SystemExit("--gan must be dcgan, wgangp or pggan, got %r: the backward pass is built for the DCGAN / WGAN-GP generator and for "
+                         "PGGAN (VAEGAN is not)" % (args.gan,))
+    pg = [getattr(args, name, None) for name in LATER_OPTIONS]
+    if args.gan == "pggan":
+        if pg[0] is None:
+            raise SystemExit("--gan pggan needs --pg_steps: PGGAN's depth (images of 4 * 2^pg_steps pixels) has no default here, and --steps "
+                             "is the number of gradient steps")
+        if not 0 <= int(pg[0]) <= 8 or (pg[1] is not None and not 0.0 <= float(pg[1]) <= 1.0) or (pg[2] is not None and int(pg[2]) < 32):
+            raise SystemExit("PGGAN: --pg_steps must lie in [0, 8], --alpha in [0, 1] and --in_channels be at least 32, got %s, %s, %s" % tuple(pg))
+        if int(args.resolution) != 4 * 2 ** int(pg[0]):
+            raise SystemExit("PGGAN at --pg_steps %d makes %d x %d images; --resolution is %s" % (pg[0], 4 * 2 ** int(pg[0]), 4 * 2 ** int(pg[0]),
+                                                                                                   args.resolution))
+    elif any(v is not None for v in pg):
+        raise SystemExit("--pg_steps, --alpha and --in_channels belong to --gan pggan (PGGAN), got --gan %s" % (args.gan,))
     if getattr(args, "generator_path", None) is None:
         raise SystemExit("--generator_path is needed: the white-box attacker holds the generator")
     if (getattr(args, "noise_path", None) is None) == (getattr(args, "num_init", None) is None):
@@ -79,11 +100,16 @@ def _request(args):
 
 
 def load_generator(args):
-    """-> (generator, nz)"""
+    """-> (generator, nz); PGGAN: the generator at the requested depth"""
     import torch
-    from ..gan_models.dcgan.model_torch import Generator     # wgangp shares it (gan_models/wgangp/model.py)
     sd = torch.load(args.generator_path, map_location="cpu", weights_only=True)
     nz = int(args.nz)
+    if args.gan == "pggan":
+        from ..gan_models.pggan.model_torch import Generator as PgganGenerator
+        pg = PgganGenerator(nz, 256 if args.in_channels is None else int(args.in_channels), int(args.nc))
+        pg.load_state_dict(sd)
+        return pg.at(int(args.pg_steps), 1.0 if args.alpha is None else float(args.alpha)), nz
+    from ..gan_models.dcgan.model_torch import Generator     # wgangp shares it (gan_models/wgangp/model.py)
     gen = Generator(nz, int(args.nc), int(args.ngf))
     gen.load_state_dict(sd)
     return gen, nz
@@ -93,7 +119,7 @@ def main(args):
     _request(args)
     assert os.path.exists(args.generator_path)
     save_dir = check_folder(os.path.join(os.getcwd(), 'wb_attack', args.exp_name))
-    lines = ["%s:%s" % (key, value) for key, value in vars(args).items()]
+    lines = ["%s:%s" % (key, value) for key, value in vars(args).items() if not (key in LATER_OPTIONS and value is None)]
     with open(os.path.join(save_dir, 'params.txt'), 'w') as handle:
         handle.write("".join(line + "\n" for line in lines))
     print("\n".join(lines))

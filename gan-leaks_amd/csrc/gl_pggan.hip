@@ -6,7 +6,9 @@
 // WSConv2d (:8-22) scales its INPUT by sqrt(2/(C_in k^2)); the factor is folded into the packed weights.
 // Every convolution runs in gather_conv_kernel (fp32 MFMA): 3x3 = 9 taps, the nearest-neighbour upsampling
 // is fused into the gather (GlGatherConv::up), toRGB = 1 tap with 3 (padded to 64) columns.
-#include "gl_conv.h"
+// The gradient with respect to z (gl_pggan_grad.hip) runs this forward at precision 0 in keep mode (gl_pggan.h): the same launches, every
+// layer into a buffer of its own, the PixelNorm factors stored as well.
+#include "gl_pggan.h"
 #include <cstdlib>
 #include <cmath>
 #include <vector>
@@ -14,7 +16,7 @@
 namespace {
 
 const double kFactors[9] = {1, 1, 1, 1, 1.0 / 2, 1.0 / 4, 1.0 / 8, 1.0 / 16, 1.0 / 32};   // model_torch.py:6
-constexpr int kBlocks = 8;
+constexpr int kBlocks = kPgBlocks;
 
 // rows: x / sqrt(mean(x^2) + 1e-8), written zero-padded to dpad.  One wave per row.
 __global__ void __launch_bounds__(256) pixelnorm_rows_kernel(const float *__restrict__ in, int64_t n, int d, int dpad, float *__restrict__ out)
@@ -99,7 +101,8 @@ __global__ void __launch_bounds__(256) pixelnorm_split_kernel(char *__restrict__
 }
 
 // NHWC, in place: one wave per position
-__global__ void __launch_bounds__(256) pixelnorm_nhwc_kernel(float *__restrict__ x, int64_t positions, int C)
+// inv_out (keep mode of the gradient, else NULL): the factor of every position
+__global__ void __launch_bounds__(256) pixelnorm_nhwc_kernel(float *__restrict__ x, int64_t positions, int C, float *__restrict__ inv_out)
 {
     const int lane = threadIdx.x & 63;
     const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
@@ -112,6 +115,7 @@ __global__ void __launch_bounds__(256) pixelnorm_nhwc_kernel(float *__restrict__
         for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o, 64);
         const float inv = 1.0f / sqrtf(ss / (float)C + 1e-8f);
         for (int c = lane; c < C; c += 64) p[c] *= inv;
+        if (inv_out && lane == 0) inv_out[pos] = inv;
     }
 }
 
@@ -181,22 +185,6 @@ namespace {
 int pg_make_h3(gl_pggan *g, void *h3_slot, const std::vector<float> &pk, size_t rows, size_t K, const float *bias, int nbias, bool rgb);
 }
 
-struct gl_pggan {
-    gl_ctx *ctx;
-    int z_dim, z_pad, C, nc;
-    int cin[kBlocks], cout[kBlocks];
-    float *w_init, *b_init, *w_i3, *b_i3;
-    float *w_blk[kBlocks][2], *b_blk[kBlocks][2];
-    float *w_rgb[kBlocks + 1], *b_rgb[kBlocks + 1];
-    bool have_init, have_blk[kBlocks], have_rgb[kBlocks + 1];
-    float *ones;
-    // split-fp16 path (precision 1): per convolution the weights in the split layout (* 2^wexp) and the folded epilogue constants
-    int precision;
-    struct H3 { float *w, *scale, *shift; } h_init, h_i3, h_blk[kBlocks][2], h_rgb[kBlocks + 1];
-    int64_t chunk, ws_imgs;
-    size_t ws_act_elems, ws_rgb_elems;      // floats allocated per activation / rgb buffer
-    float *ws_z, *ws_buf[3], *ws_rgb[2];
-};
 
 namespace {
 
@@ -266,14 +254,14 @@ int pg_conv(gl_pggan *g, const float *in, int64_t m, int H, int W, int up, int C
     return gl_launch_gather_conv(g->ctx, p, 1);
 }
 
-int pg_pixelnorm(gl_pggan *g, float *x, int64_t positions, int C)
+int pg_pixelnorm(gl_pggan *g, float *x, int64_t positions, int C, float *inv_out = nullptr)
 {
     int64_t blocks = gl_ceil_div(positions, 4);
     if (blocks > 8192) blocks = 8192;
     if (g->precision == 1)
         hipLaunchKernelGGL(pixelnorm_split_kernel, dim3((unsigned)blocks), dim3(256), 0, g->ctx->stream, reinterpret_cast<char *>(x), positions, C);
     else
-        hipLaunchKernelGGL(pixelnorm_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, g->ctx->stream, x, positions, C);
+        hipLaunchKernelGGL(pixelnorm_nhwc_kernel, dim3((unsigned)blocks), dim3(256), 0, g->ctx->stream, x, positions, C, inv_out);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }
@@ -306,6 +294,9 @@ int gl_pggan_create(gl_ctx *ctx, int z_dim, int in_channels, int img_channels, g
     for (int j = 0; j <= kBlocks; ++j) g->h_rgb[j] = gl_pggan::H3{nullptr, nullptr, nullptr};
     g->chunk = 0; g->ws_imgs = 0; g->ws_act_elems = 0; g->ws_rgb_elems = 0;
     g->ws_z = nullptr; g->ws_buf[0] = g->ws_buf[1] = g->ws_buf[2] = nullptr; g->ws_rgb[0] = g->ws_rgb[1] = nullptr;
+    g->grad_dirty = true; g->keep = false; g->gws_imgs = 0; g->gws_steps = -1;
+    for (int l = 0; l < kPgLayers; ++l) g->gw[l] = g->keep_act[l] = g->keep_inv[l] = nullptr;
+    g->gws_y = g->gws_g = g->gws_roll[0] = g->gws_roll[1] = g->gws_roll[2] = nullptr;
     std::vector<float> one(16 * (size_t)in_channels, 1.0f);
     int rc = pg_upload(ctx, &g->ones, one);
     if (rc != GL_OK) { delete g; return rc; }
@@ -329,6 +320,7 @@ int gl_pggan_destroy(gl_pggan *g)
     free_h3(g->h_init); free_h3(g->h_i3);
     for (int i = 0; i < kBlocks; ++i) { free_h3(g->h_blk[i][0]); free_h3(g->h_blk[i][1]); }
     for (int j = 0; j <= kBlocks; ++j) free_h3(g->h_rgb[j]);
+    gl_pggan_grad_free(g);
     delete g;
     return GL_OK;
 }
@@ -367,6 +359,9 @@ int gl_pggan_set_initial(gl_pggan *g, const float *convt_w, const float *convt_b
     if (rc == GL_OK) rc = pg_make_h3(g, &g->h_init, pk, (size_t)16 * C, (size_t)K, convt_b, C, false);
     if (rc == GL_OK) rc = pg_make_h3(g, &g->h_i3, pk3, (size_t)cols_pad_of(C), (size_t)9 * C, ws_b, C, false);
     if (rc != GL_OK) return rc;
+    g->h_init_w.assign(convt_w, convt_w + (size_t)g->z_dim * C * 16);
+    g->h_conv_w[1].assign(ws_w, ws_w + (size_t)C * C * 9);
+    g->grad_dirty = true;
     g->have_init = true;
     return GL_OK;
 }
@@ -387,6 +382,9 @@ int gl_pggan_set_block(gl_pggan *g, int block, const float *conv1_w, const float
     if (rc == GL_OK) rc = pg_make_h3(g, &g->h_blk[block][0], p1, (size_t)cols_pad_of(co), (size_t)9 * ci, conv1_b, co, false);
     if (rc == GL_OK) rc = pg_make_h3(g, &g->h_blk[block][1], p2, (size_t)cols_pad_of(co), (size_t)9 * co, conv2_b, co, false);
     if (rc != GL_OK) return rc;
+    g->h_conv_w[2 + 2 * block].assign(conv1_w, conv1_w + (size_t)co * ci * 9);
+    g->h_conv_w[3 + 2 * block].assign(conv2_w, conv2_w + (size_t)co * co * 9);
+    g->grad_dirty = true;
     g->have_blk[block] = true;
     return GL_OK;
 }
@@ -446,7 +444,8 @@ int gl_pggan_forward(gl_pggan *g, const float *z_dev, int64_t n, int steps, floa
     if (want > n) want = n;
     const size_t rgb_elems = (size_t)R * R * 4;      // up to 4 floats per pixel (split path pads 3 -> 4)
     // `want` images per pass for THIS depth; the buffers only ever grow (ws_imgs latent rows, ws_act_elems / ws_rgb_elems floats per buffer)
-    const size_t need_act = (size_t)want * act, need_rgb = (size_t)want * rgb_elems;
+    GL_REQUIRE(!g->keep || (want == n && g->precision == 0), "gl_pggan_forward: keep mode needs precision 0 and a call of one pass");
+    const size_t need_act = g->keep ? 0 : (size_t)want * act, need_rgb = (size_t)want * rgb_elems;
     if (want > g->ws_imgs || need_act > g->ws_act_elems || need_rgb > g->ws_rgb_elems) {
         GL_HIP(hipStreamSynchronize(ctx->stream));
         const int64_t z_rows = want > g->ws_imgs ? want : g->ws_imgs;
@@ -458,7 +457,7 @@ int gl_pggan_forward(gl_pggan *g, const float *z_dev, int64_t n, int steps, floa
         g->ws_z = nullptr;
         g->ws_imgs = 0; g->ws_act_elems = 0; g->ws_rgb_elems = 0;
         GL_HIP(gl_device_alloc(g->ctx, (void **)&g->ws_z, (size_t)z_rows * g->z_pad * 4));
-        for (int k = 0; k < 3; ++k) GL_HIP(gl_device_alloc(g->ctx, (void **)&g->ws_buf[k], act_alloc * 4));
+        for (int k = 0; k < 3 && act_alloc > 0; ++k) GL_HIP(gl_device_alloc(g->ctx, (void **)&g->ws_buf[k], act_alloc * 4));
         for (int k = 0; k < 2; ++k) GL_HIP(gl_device_alloc(g->ctx, (void **)&g->ws_rgb[k], rgb_alloc * 4 + 64));
         g->ws_imgs = z_rows;
         g->ws_act_elems = act_alloc;
@@ -466,6 +465,9 @@ int gl_pggan_forward(gl_pggan *g, const float *z_dev, int64_t n, int steps, floa
     }
     const int64_t img_elems = (int64_t)nc * R * R;
     int rc;
+    // keep mode: layer l writes a buffer of its own (gl_pggan.h) instead of rolling buffer k
+    auto lbuf = [&](int l, int k) { return g->keep ? g->keep_act[l] : g->ws_buf[k]; };
+    auto linv = [&](int l) { return g->keep ? g->keep_inv[l] : nullptr; };
 
     for (int64_t i0 = 0; i0 < n; i0 += want) {
         const int64_t m = (n - i0 < want) ? n - i0 : want;
@@ -482,7 +484,7 @@ int gl_pggan_forward(gl_pggan *g, const float *z_dev, int64_t n, int steps, floa
             GlGatherConv p = {};
             p.in = g->ws_z; p.positions = m; p.H = 1; p.W = 1; p.Cin = g->z_pad;
             p.wpack = g->w_init; p.cols = 16 * C; p.cols_pad = cols_pad_of(16 * C); p.ntaps = 1; p.tap_dy[0] = 1; p.tap_dx[0] = 1;
-            p.out = g->ws_buf[0]; p.Ho = 1; p.Wo = 1; p.omul = 1;
+            p.out = lbuf(0, 0); p.Ho = 1; p.Wo = 1; p.omul = 1;
             p.scale = g->ones; p.shift = g->b_init; p.cmod = C; p.act = 2; p.zero = ctx->zero_page;
             if (h3) {
                 p.wpack = g->h_init.w; p.scale = g->h_init.scale; p.shift = g->h_init.shift; p.out_mode = 2;
@@ -494,34 +496,37 @@ int gl_pggan_forward(gl_pggan *g, const float *z_dev, int64_t n, int steps, floa
             if (rc != GL_OK) return rc;
         }
         bool normed = false;
-        rc = pg_conv(g, g->ws_buf[0], m, 4, 4, 0, C, g->w_i3, g->b_i3, C, 9, 2, g->ws_buf[1], &g->h_i3, false, &normed);
+        rc = pg_conv(g, lbuf(0, 0), m, 4, 4, 0, C, g->w_i3, g->b_i3, C, 9, 2, lbuf(1, 1), &g->h_i3, false, &normed);
         if (rc != GL_OK) return rc;
-        if (!normed) rc = pg_pixelnorm(g, g->ws_buf[1], m * 16, C);
+        if (!normed) rc = pg_pixelnorm(g, lbuf(1, 1), m * 16, C, linv(1));
         if (rc != GL_OK) return rc;
-        int cur = 1, prev = 1, hw = 4;
+        int cur = 1, hw = 4;
+        float *pcur = lbuf(1, 1), *pprev = pcur;
         bool rgb_done = false;
         for (int s = 0; s < steps; ++s) {
             hw *= 2;
             const int b1 = (cur + 1) % 3, b2 = (cur + 2) % 3;
-            rc = pg_conv(g, g->ws_buf[cur], m, hw, hw, 1, g->cin[s], g->w_blk[s][0], g->b_blk[s][0], g->cout[s], 9, 2, g->ws_buf[b1], &g->h_blk[s][0], false, &normed);
-            if (rc == GL_OK && !normed) rc = pg_pixelnorm(g, g->ws_buf[b1], m * hw * hw, g->cout[s]);
-            if (rc == GL_OK) rc = pg_conv(g, g->ws_buf[b1], m, hw, hw, 0, g->cout[s], g->w_blk[s][1], g->b_blk[s][1], g->cout[s], 9, 2, g->ws_buf[b2], &g->h_blk[s][1], false, &normed,
+            float *o1 = lbuf(2 + 2 * s, b1), *o2 = lbuf(3 + 2 * s, b2);
+            rc = pg_conv(g, pcur, m, hw, hw, 1, g->cin[s], g->w_blk[s][0], g->b_blk[s][0], g->cout[s], 9, 2, o1, &g->h_blk[s][0], false, &normed);
+            if (rc == GL_OK && !normed) rc = pg_pixelnorm(g, o1, m * hw * hw, g->cout[s], linv(2 + 2 * s));
+            if (rc == GL_OK) rc = pg_conv(g, o1, m, hw, hw, 0, g->cout[s], g->w_blk[s][1], g->b_blk[s][1], g->cout[s], 9, 2, o2, &g->h_blk[s][1], false, &normed,
                                           s + 1 == steps ? steps : -1, g->ws_rgb[0], &rgb_done);
-            if (rc == GL_OK && !normed) rc = pg_pixelnorm(g, g->ws_buf[b2], m * hw * hw, g->cout[s]);
+            if (rc == GL_OK && !normed) rc = pg_pixelnorm(g, o2, m * hw * hw, g->cout[s], linv(3 + 2 * s));
             if (rc != GL_OK) return rc;
-            prev = cur;      // input of this block (low resolution): `upscaled` of the reference is its x2 view
+            pprev = pcur;    // input of this block (low resolution): `upscaled` of the reference is its x2 view
+            pcur = o2;
             cur = b2;
         }
         // toRGB (unless the last convolution's epilogue has already written it)
         if (!rgb_done) {
-            rc = pg_conv(g, g->ws_buf[cur], m, hw, hw, 0, rgb_cin(g, steps), g->w_rgb[steps], g->b_rgb[steps], nc, 1, 0, g->ws_rgb[0], &g->h_rgb[steps], true);
+            rc = pg_conv(g, pcur, m, hw, hw, 0, rgb_cin(g, steps), g->w_rgb[steps], g->b_rgb[steps], nc, 1, 0, g->ws_rgb[0], &g->h_rgb[steps], true);
             if (rc != GL_OK) return rc;
         }
         const float *brgb = nullptr;
         if (steps > 0 && alpha != 1.0f) {
             // rgb[steps-1](upscaled): the 1x1 convolution commutes with nearest upsampling, so it runs at half resolution.
             // With alpha == 1 the term is multiplied by exactly 0 (finite values), so it is skipped.
-            rc = pg_conv(g, g->ws_buf[prev], m, hw / 2, hw / 2, 0, rgb_cin(g, steps - 1), g->w_rgb[steps - 1], g->b_rgb[steps - 1], nc, 1, 0, g->ws_rgb[1], &g->h_rgb[steps - 1], true);
+            rc = pg_conv(g, pprev, m, hw / 2, hw / 2, 0, rgb_cin(g, steps - 1), g->w_rgb[steps - 1], g->b_rgb[steps - 1], nc, 1, 0, g->ws_rgb[1], &g->h_rgb[steps - 1], true);
             if (rc != GL_OK) return rc;
             brgb = g->ws_rgb[1];
         }

@@ -152,6 +152,79 @@ class Generator:
         _, u8 = self.forward_device(x, steps, alpha, False, True)
         return u8
 
+    def at(self, steps, alpha=1.0):
+        """the generator at one fixed depth: a light view with generate_u8(z), forward(z), vjp_z(z, cot) and l2_grad_z(z, targets_u8), for
+        callers that hand a generator nothing but latents (wb_attack; pbb_attack, pbb_init_from_bank and GeneratedBank without keywords)"""
+        return GeneratorAt(self, steps, alpha)
+
+
+class GeneratorAt:
+    """`Generator.at(steps, alpha)`: Generator.forward(., steps, alpha) as a generator of its own, with the gradients with respect to z of
+    csrc/gl_pggan_grad.hip.  It holds no weights: the Generator it came from does, and its precision and chunk settings apply."""
+
+    def __init__(self, generator, steps, alpha=1.0):
+        if isinstance(steps, bool) or int(steps) != steps or not 0 <= int(steps) <= len(FACTORS) - 1:
+            raise ValueError("steps must be an integer in [0, %d], got %r" % (len(FACTORS) - 1, steps))
+        steps = int(steps)
+        for s in range(steps):
+            ci, co = int(generator.in_channels * FACTORS[s]), int(generator.in_channels * FACTORS[s + 1])
+            if ci % 32 or co % 32 or co < 32:
+                raise ValueError("steps=%d: block %d has %d -> %d channels at in_channels=%d; the convolutions need multiples of 32"
+                                 % (steps, s, ci, co, generator.in_channels))
+        alpha = float(alpha)
+        if not (np.isfinite(alpha) and 0.0 <= alpha <= 1.0):
+            raise ValueError("alpha must lie in [0, 1], got %r" % (alpha,))
+        self.generator, self.steps, self.alpha = generator, steps, alpha
+        self.z_dim = generator.z_dim
+        R = 4 * 2 ** steps
+        self.image_shape = (generator.img_channels, R, R)
+
+    @property
+    def ctx(self):
+        return self.generator.ctx
+
+    def generate_u8(self, z):
+        return self.generator.generate_u8(z, self.steps, self.alpha)
+
+    def forward(self, z):
+        return self.generator.forward(z, self.steps, self.alpha)
+
+    __call__ = forward
+
+    def _z_device(self, z):
+        gen = self.generator
+        if not gen._loaded:
+            raise RuntimeError("Generator: load_state_dict() has not been called")
+        zd = as_device(gen.ctx, z, np.float32)
+        if int(np.prod(zd.shape[1:], dtype=np.int64)) != gen.z_dim:
+            raise ValueError("expected z of shape [N,%d] or [N,%d,1,1], got %s" % (gen.z_dim, gen.z_dim, zd.shape))
+        return zd, zd.shape[0]
+
+    def vjp_z(self, z, cot):
+        """(grad, y): grad = (dG/dz)^T cot for cot [N,C,R,R] float32, a DeviceArray [N, z_dim], and y = G(z) of the fp32-product forward the
+        gradient belongs to, a DeviceArray [N,C,R,R].  The generator's precision and chunk stay as they are."""
+        zd, n = self._z_device(z)
+        ctx = self.ctx
+        cd = as_device(ctx, cot, np.float32)
+        if cd.nbytes != n * int(np.prod(self.image_shape)) * 4:
+            raise ValueError("expected a cotangent of shape %s, got %s" % ((n,) + self.image_shape, cd.shape))
+        grad, out = ctx.empty((n, self.z_dim), np.float32), ctx.empty((n,) + self.image_shape, np.float32)
+        check(ctx.lib.gl_pggan_vjp_z(self.generator._handle, _p(zd.ptr), n, self.steps, ctypes.c_float(self.alpha), _p(cd.ptr), _p(grad.ptr), _p(out.ptr)))
+        return grad, out
+
+    def l2_grad_z(self, z, targets_u8):
+        """loss[i] = sum (G(z_i) - x_i)^2 over the image, x = 2 u / 255 - 1 of targets_u8 [N,C,R,R] uint8, and grad = d loss / d z:
+        -> (grad DeviceArray [N, z_dim], loss DeviceArray [N]), float32"""
+        zd, n = self._z_device(z)
+        ctx = self.ctx
+        td = as_device(ctx, targets_u8, np.uint8)
+        if td.nbytes != n * int(np.prod(self.image_shape)):
+            raise ValueError("expected targets of shape %s uint8, got %s" % ((n,) + self.image_shape, td.shape))
+        grad, loss = ctx.empty((n, self.z_dim), np.float32), ctx.empty((n,), np.float32)
+        check(ctx.lib.gl_pggan_l2_grad_z(self.generator._handle, _p(zd.ptr), _p(td.ptr), n, self.steps, ctypes.c_float(self.alpha), _p(grad.ptr),
+                                         _p(loss.ptr)))
+        return grad, loss
+
 
 class stackGenerators:
     """model_torch.py:207-216; keys `gen.{i}.{...}`; forward(x, steps, alpha, i)"""

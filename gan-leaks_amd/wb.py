@@ -2,7 +2,7 @@
 z* = argmin_z L(x, G(z)) by gradient descent and scores the query x by L(x, G(z*)).  For all queries at once, one step is
 
     l2_grad_z           d/dz sum (G(z) - x)^2 at the iterate: the generator's own fp32-product forward and its backward pass
-                        (csrc/gl_dcgan_grad.hip), as device arrays
+                        (csrc/gl_dcgan_grad.hip, csrc/gl_pggan_grad.hip), as device arrays
     gl_wb_adam_step     one Adam update of the iterate, clamped to [-z_max, z_max] (csrc/gl_wb.hip)
     generate_u8         the 8-bit images of the new iterate, with the generator's own precision setting: exactly the images the
                         full-black-box and the partial-black-box attack score
@@ -38,8 +38,8 @@ def _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, blo
     if getattr(generator, "power_iterations", None) is not None:
         raise NotImplementedError("VAEGAN's generator (spectral normalisation advanced by every forward, self-attention) has no backward pass")
     if not hasattr(generator, "l2_grad_z") or not hasattr(generator, "generate_u8"):
-        raise NotImplementedError("%s.%s has no l2_grad_z: the backward pass is built for the DCGAN / WGAN-GP generator only"
-                                  % (type(generator).__module__, type(generator).__name__))
+        raise NotImplementedError("%s.%s has no l2_grad_z: the backward pass is built for the DCGAN / WGAN-GP generator and for PGGAN at a "
+                                  "fixed depth -- hand over pggan's Generator.at(steps, alpha)" % (type(generator).__module__, type(generator).__name__))
     if int(steps) != steps or steps < 0:
         raise ValueError("steps must be an integer >= 0, got %r" % (steps,))
     for name, v in (("lr", lr), ("eps", eps), ("z_max", z_max)):
@@ -64,8 +64,9 @@ def wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.
               distance="l2"):
     """gradient descent on the latent for every query.
 
-    queries   : [Q,3,64,64] 8-bit images (u8, or floats on the lattice 2*(u/255.)-1); numpy / torch / DeviceArray
-    generator : the DCGAN / WGAN-GP Generator (l2_grad_z and generate_u8)
+    queries   : [Q,C,H,W] 8-bit images (u8, or floats on the lattice 2*(u/255.)-1); numpy / torch / DeviceArray; [Q,3,64,64] for DCGAN
+    generator : the DCGAN / WGAN-GP Generator, or PGGAN's Generator.at(steps, alpha) (l2_grad_z and generate_u8); where it has an
+                `image_shape`, queries of another shape are refused
     z_init    : [Q, nz] or [Q, nz, 1, 1] starting latents (pbb_init_from_bank gives the nearest bank latents)
     steps, lr, beta1, beta2, eps: Adam on sum (G(z) - x)^2, float32; z_max: the iterate is clamped to [-z_max, z_max]
     block_images: queries go in blocks of that many; each block runs all its steps on the device
@@ -76,6 +77,10 @@ def wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.
     Q, nz = z_host.shape
     if len(queries) != Q:
         raise ValueError("%d queries but %d starting latents" % (len(queries), Q))
+    image_shape = tuple(int(v) for v in (queries.shape if hasattr(queries, "shape") else np.shape(queries))[1:])
+    want_shape = getattr(generator, "image_shape", None)
+    if want_shape is not None and image_shape != tuple(want_shape):
+        raise ValueError("the queries are images of shape %r, the generator makes %r" % (image_shape, tuple(want_shape)))
     ctx = generator.ctx
     lib = ctx.lib
     qu8 = prepare_images(ctx, queries)                   # raises ValueError off the 8-bit lattice
@@ -106,7 +111,7 @@ def wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.
         if history:
             trace[0, lo:lo + nb] = S_best.numpy().astype(np.int64)
         for t in range(1, steps + 1):
-            grad, _ = generator.l2_grad_z(z, q_dev.view((nb, 3, 64, 64)))
+            grad, _ = generator.l2_grad_z(z, q_dev.view((nb,) + image_shape))
             c1, c2 = 1.0 / (1.0 - float(beta1) ** t), 1.0 / (1.0 - float(beta2) ** t)
             check(lib.gl_wb_adam_step(ctx.handle, _p(z.ptr), _p(m.ptr), _p(v.ptr), _p(grad.ptr), nb, nz, _f(lr), _f(beta1), _f(beta2), _f(eps), _f(c1),
                                       _f(c2), _f(z_max)))

@@ -494,6 +494,19 @@ int gl_pggan_set_precision(gl_pggan *g, int mode);
 /* z_dev [n][z_dim] -> [n][nc][R][R], R = 4 * 2^steps.  out_f32_dev: what forward() returns; out_u8_dev: the bytes the
  * generate branch writes (gan_models/pggan/train.py:238-246: x*0.5+0.5, ToPILImage).  Either may be NULL. */
 int gl_pggan_forward(gl_pggan *g, const float *z_dev, int64_t n, int steps, float alpha, float *out_f32_dev, uint8_t *out_u8_dev);
+/* The white-box attack on PGGAN (csrc/gl_pggan_grad.hip): the derivative of Generator.forward(z, steps, alpha) with respect to z [n][z_dim],
+ * through the PixelNorm of the latent.  Each call runs the forward with fp32 products itself, whatever gl_pggan_set_precision says, and leaves
+ * that setting and gl_pggan_set_chunk's as it found them; the kept activations of one pass (gl_pggan_set_chunk images, by default what fits
+ * 1.5 GiB) and the transposed weight packs are allocated by the first gradient call and freed by gl_pggan_destroy.  Every output is one
+ * fixed-order fp32 sum: a row does not depend on the images that share the call or the pass.  Depths gl_pggan_forward refuses are refused the
+ * same way, unloaded weights with GL_ERR_STATE.  n = 0 returns GL_OK; on the context's stream, no synchronisation. */
+/* vector-Jacobian product: grad_z[n][z_dim] = (dG/dz)^T cot, cot [n][nc][R][R] fp32 (NCHW), R = 4 * 2^steps.  out_f32_dev (may be NULL)
+ * receives G(z) of the fp32-product forward: the values gl_pggan_forward gives under precision 0 */
+int gl_pggan_vjp_z(gl_pggan *g, const float *z_dev, int64_t n, int steps, float alpha, const float *cot_dev, float *grad_z_dev, float *out_f32_dev);
+/* loss[i] = sum over the image of (G(z_i) - x_i)^2, x = 2 u/255 - 1 of target_u8 [n][nc][R][R]; grad_z = d loss / d z.  The squares are
+ * added in double */
+int gl_pggan_l2_grad_z(gl_pggan *g, const float *z_dev, const uint8_t *target_u8_dev, int64_t n, int steps, float alpha, float *grad_z_dev,
+                       float *loss_dev);
 
 /* ---------------------------------------------------------------- medGAN (tabular) */
 /* gan_models/medgan/model.py:44-73 Generator(z_dim, hidden_size) and :13-41 Autoencoder(input_size, hidden_size, binary).decode,

@@ -2,9 +2,10 @@
 """Timing of the white-box attack's gradient and step (ganleaks_amd.wb), and its result next to the partial-black-box search from the same
 start.  ONE process on the shipped library, run it under the caller's `timeout`:
     python tools/bench_wb.py [--rounds 7] [--queries 4096] [--ngf 64] [--compare_queries 1024] [--steps 64]
-DCGAN-64 with synthetic weights.  Timed with device events on the context's stream, every variant warmed up once, then the variants
+    python tools/bench_wb.py --gan pggan [--in_channels 256] [--pg_steps 4] [--alpha 1.0] [--nz 256] --queries 1024 --compare_queries 256
+DCGAN-64, or with --gan pggan PGGAN at a fixed depth (gl_pggan_forward / gl_pggan_l2_grad_z, Generator.at), with synthetic weights.  Timed with device events on the context's stream, every variant warmed up once, then the variants
 ALTERNATE inside every round (median, smallest, largest):
-  forward fp32    gl_dcgan_forward at precision 0, fp32 output: the forward half of the gradient call
+  forward fp32    gl_dcgan_forward (gl_pggan_forward) at precision 0, fp32 output: the forward half of the gradient call
   l2_grad_z       gl_dcgan_l2_grad_z: that forward, the cotangent and the backward pass; x_forward is its ratio to `forward fp32`
   scoring         generate_u8 at the generator's own precision (split-fp16), the extra forward of a step
   step            l2_grad_z + gl_wb_adam_step + generate_u8 + gl_pbb_group_min + gl_pbb_accept: one step of wb_attack; scoring_share is
@@ -32,6 +33,11 @@ def main():
     ap.add_argument("--ngf", type=int, default=64)
     ap.add_argument("--compare_queries", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=64)
+    ap.add_argument("--gan", choices=["dcgan", "pggan"], default="dcgan")
+    ap.add_argument("--in_channels", type=int, default=256, help="pggan: channel count of the first block")
+    ap.add_argument("--pg_steps", type=int, default=4, help="pggan: resolution steps (4 * 2^pg_steps pixels)")
+    ap.add_argument("--alpha", type=float, default=1.0, help="pggan: fade-in weight of the last block")
+    ap.add_argument("--nz", type=int, default=None, help="latent length (default 100; 256 for pggan)")
     args = ap.parse_args()
     import ganleaks_amd as gl
     from ganleaks_amd._lib import check
@@ -53,30 +59,54 @@ def main():
         check(lib.gl_event_elapsed_ms(ev[0], ev[1], ctypes.byref(ms)))
         return ms.value
 
-    Q, nz, d = args.queries, 100, 3 * 64 * 64
-    sd = gl.synth.dcgan_state_dict(1234, features_g=args.ngf)
-    gen, gen0 = Generator(nz, 3, args.ngf), Generator(nz, 3, args.ngf)
-    gen.load_state_dict(sd)
-    gen0.load_state_dict(sd)
-    gen0.set_precision(0)
-    queries = gen.generate_u8(gl.synth.latent(2, Q))
-    z = ctx.to_device(gl.synth.latent(1, Q).reshape(Q, nz))
-    z_best = ctx.to_device(gl.synth.latent(1, Q).reshape(Q, nz))
+    pg = args.gan == "pggan"
+    Q, nz = args.queries, args.nz if args.nz is not None else (256 if pg else 100)
+    if pg:
+        from ganleaks_amd.gan_models.pggan.model_torch import Generator as PgganGenerator
+        R, pgs, alpha = 4 * 2 ** args.pg_steps, int(args.pg_steps), f(args.alpha)
+        sd = gl.synth.pggan_state_dict(1234, nz, args.in_channels)
+        full, full0 = PgganGenerator(nz, args.in_channels, 3), PgganGenerator(nz, args.in_channels, 3)
+        full.load_state_dict(sd)
+        full0.load_state_dict(sd)
+        full0.set_precision(0)
+        gen = full.at(pgs, args.alpha)               # what the attacks are handed
+        tag = {"gan": "pggan", "in_channels": args.in_channels, "pg_steps": pgs, "alpha": args.alpha}
+    else:
+        R = 64
+        sd = gl.synth.dcgan_state_dict(1234, features_g=args.ngf)
+        gen, gen0 = Generator(nz, 3, args.ngf), Generator(nz, 3, args.ngf)
+        gen.load_state_dict(sd)
+        gen0.load_state_dict(sd)
+        gen0.set_precision(0)
+        tag = {"ngf": args.ngf}
+    d = 3 * R * R
+    queries = gen.generate_u8(gl.synth.latent(2, Q, nz))
+    z = ctx.to_device(gl.synth.latent(1, Q, nz).reshape(Q, nz))
+    z_best = ctx.to_device(gl.synth.latent(1, Q, nz).reshape(Q, nz))
     m, v = ctx.zeros((Q, nz), np.float32), ctx.zeros((Q, nz), np.float32)
-    grad, loss, out = ctx.empty((Q, nz), np.float32), ctx.empty((Q,), np.float32), ctx.empty((Q, 3, 64, 64), np.float32)
+    grad, loss, out = ctx.empty((Q, nz), np.float32), ctx.empty((Q,), np.float32), ctx.empty((Q, 3, R, R), np.float32)
     one = ctx.to_device(np.ones((Q,), np.float32))
     S_best, S_new = ctx.to_device(np.full((Q,), np.iinfo(np.int64).max, np.uint64)), ctx.empty((Q,), np.uint64)
     j_new, accepted, work = ctx.empty((Q,), np.int32), ctx.empty((Q,), np.uint8), ctx.empty((16 * Q,), np.uint8)
     state = {"t": 0, "images": None}
 
     def forward32():
-        check(lib.gl_dcgan_forward(gen0._handle, p(z.ptr), Q, p(out.ptr), p(0)))
+        if pg:
+            check(lib.gl_pggan_forward(full0._handle, p(z.ptr), Q, pgs, alpha, p(out.ptr), p(0)))
+        else:
+            check(lib.gl_dcgan_forward(gen0._handle, p(z.ptr), Q, p(out.ptr), p(0)))
 
     def l2_grad():
-        check(lib.gl_dcgan_l2_grad_z(gen._handle, p(z.ptr), p(queries.ptr), Q, p(grad.ptr), p(loss.ptr)))
+        if pg:
+            check(lib.gl_pggan_l2_grad_z(full._handle, p(z.ptr), p(queries.ptr), Q, pgs, alpha, p(grad.ptr), p(loss.ptr)))
+        else:
+            check(lib.gl_dcgan_l2_grad_z(gen._handle, p(z.ptr), p(queries.ptr), Q, p(grad.ptr), p(loss.ptr)))
 
     def scoring():
-        state["images"] = gen.forward_device(z, False, True, check_range=False)[1]
+        if pg:
+            state["images"] = full.forward_device(z, pgs, args.alpha, False, True, check_range=False)[1]
+        else:
+            state["images"] = gen.forward_device(z, False, True, check_range=False)[1]
 
     def step():
         state["t"] += 1
@@ -100,7 +130,7 @@ def main():
     med = {label: float(np.median(t)) for label, t in ms.items()}
     for label, _ in variants:
         t = ms[label]
-        row = {"variant": label, "queries": Q, "ngf": args.ngf, "median_ms": round(med[label], 4), "min_ms": round(min(t), 4),
+        row = {"variant": label, "queries": Q, **tag, "median_ms": round(med[label], 4), "min_ms": round(min(t), 4),
                "max_ms": round(max(t), 4), "x_forward": round(med[label] / med["forward fp32"], 4), "rounds": args.rounds}
         if label == "step":
             row["scoring_share"] = round(med["scoring"] / med[label], 4)
@@ -110,9 +140,9 @@ def main():
     # ---- the result: gradient descent against the gradient-free search, same start
     n = args.compare_queries
     if n > 0:
-        z_bank = gl.synth.latent(11, n).reshape(n, nz)
-        z_img = gl.synth.latent(12, n).reshape(n, nz)
-        z_img[: n // 2] = z_bank[: n // 2] + np.float32(0.5) * gl.synth.latent(13, n // 2).reshape(n // 2, nz)
+        z_bank = gl.synth.latent(11, n, nz).reshape(n, nz)
+        z_img = gl.synth.latent(12, n, nz).reshape(n, nz)
+        z_img[: n // 2] = z_bank[: n // 2] + np.float32(0.5) * gl.synth.latent(13, n // 2, nz).reshape(n // 2, nz)
         q = gen.generate_u8(z_img).numpy()
         z_init, _ = gl.pbb_init_from_bank(q, gen, z_bank, batch_size=64)
         t0 = time.perf_counter()
@@ -122,7 +152,7 @@ def main():
         _, _, S_pbb = gl.pbb_attack(q, gen, z_init, rounds=32, population=64)
         t_pbb = time.perf_counter() - t0
         half = n // 2
-        print(json.dumps({"comparison": "final S from the same start", "queries": n, "ngf": args.ngf, "wb_steps": args.steps, "pbb_rounds": 32,
+        print(json.dumps({"comparison": "final S from the same start", "queries": n, **tag, "wb_steps": args.steps, "pbb_rounds": 32,
                           "pbb_population": 64, "median_S_start_near": float(np.median(tr[0][:half])), "median_S_wb_near": float(np.median(S_wb[:half])),
                           "median_S_pbb_near": float(np.median(S_pbb[:half])), "median_S_start_far": float(np.median(tr[0][half:])),
                           "median_S_wb_far": float(np.median(S_wb[half:])), "median_S_pbb_far": float(np.median(S_pbb[half:])),

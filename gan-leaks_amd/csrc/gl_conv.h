@@ -90,6 +90,12 @@ __device__ __forceinline__ char *gl_vrow_elem(char *V, int64_t ldv, int64_t row,
     return V + ((row >> 8) * (-ldv) + (k >> 6)) * 32768 + (row & 255) * 128 + (k & 63) * 2;
 }
 
+// Correctly rounded float32 square root.  __fsqrt_rn does not give one: hipcc lowers it to a bare v_sqrt_f32, which is accurate to 1 ulp
+// (measured: 10 - 20 % of the sums of squares of a layer come out one float32 step from the rounded root).  The fused epilogues and their
+// stand-alone siblings promise steps that are each correctly rounded, so that a host can repeat them (tests/test_gpu_conv_epilogues.py compares
+// with numpy's float32, bit for bit); __builtin_sqrtf is the IEEE operation (v_sqrt_f32 plus the fma test of its two neighbours).
+__device__ __forceinline__ float gl_sqrt_rn(float x) { return __builtin_sqrtf(x); }
+
 // (v * inv) * coef with both products rounded to fp32 and MATERIALISED: without the empty asm hipcc is free to fold a product into the
 // conversion or subtraction that follows it (v_fma_mix*, fma contraction), differently in different kernels, and the fused and the
 // stand-alone tap would stop agreeing bit for bit.

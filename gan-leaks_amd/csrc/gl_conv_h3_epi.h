@@ -106,7 +106,7 @@ __device__ __forceinline__ bool epilogue(const GlGatherConv &p, v4f (&acc)[TC][T
         if (tap) {
             // ---- LPIPS tap (+ 2 x 2 max-pool) from the rounded activations in acc; nothing else is stored
 #pragma unroll
-            for (int j = 0; j < TP; ++j) pinv[j] = __fdiv_rn(p.tap_scale, __fadd_rn(__fsqrt_rn(ss[j]), p.tap_eps));
+            for (int j = 0; j < TP; ++j) pinv[j] = __fdiv_rn(p.tap_scale, __fadd_rn(gl_sqrt_rn(ss[j]), p.tap_eps));
             const int HW = p.Ho * p.Wo, Wp = p.Wo >> 1;
             int img[TP], pin[TP];
 #pragma unroll
@@ -174,7 +174,7 @@ __device__ __forceinline__ bool epilogue(const GlGatherConv &p, v4f (&acc)[TC][T
         }
         const float A = p.pixnorm_act;
 #pragma unroll
-        for (int j = 0; j < TP; ++j) pinv[j] = __fdiv_rn(A, __fsqrt_rn(__fadd_rn(__fdiv_rn(ss[j], (float)p.cols), __fmul_rn(__fmul_rn(1e-8f, A), A))));
+        for (int j = 0; j < TP; ++j) pinv[j] = __fdiv_rn(A, gl_sqrt_rn(__fadd_rn(__fdiv_rn(ss[j], (float)p.cols), __fmul_rn(__fmul_rn(1e-8f, A), A))));
         if (p.rgb_out) {
             // ---- toRGB on the normalised values (what the split store would hold: hi + lo), nothing else is stored
             float res[TP][4];

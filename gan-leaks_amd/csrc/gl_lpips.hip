@@ -510,7 +510,7 @@ __global__ void __launch_bounds__(256) lpips_tap_split_kernel(const char *__rest
         }
         ss = tap_sumsq_across<G>(ss);
         if (!live) continue;
-        const float inv = __fdiv_rn(kVScale, __fadd_rn(__fsqrt_rn(ss), tap_eps));        // (A f) / (|A f| + A eps) = f / (|f| + eps)
+        const float inv = __fdiv_rn(kVScale, __fadd_rn(gl_sqrt_rn(ss), tap_eps));        // (A f) / (|A f| + A eps) = f / (|f| + eps)
         const int64_t im = pos / HW;
         const int64_t k = off + (pos - im * HW) * C + cb * 8;
         h8 oh, ol;
@@ -574,7 +574,7 @@ __global__ void __launch_bounds__(256) lpips_tap_pool_split_kernel(const char *_
             }
             ss = tap_sumsq_across<G>(ss);
             if (!live) continue;
-            const float inv = __fdiv_rn(kVScale, __fadd_rn(__fsqrt_rn(ss), tap_eps));        // (A f) / (|A f| + A eps) = f / (|f| + eps)
+            const float inv = __fdiv_rn(kVScale, __fadd_rn(gl_sqrt_rn(ss), tap_eps));        // (A f) / (|A f| + A eps) = f / (|f| + eps)
             const int64_t k = off + pin * C + cb * 8;
             h8 oh, ol;
 #pragma unroll
@@ -1936,3 +1936,21 @@ done:
 }
 
 }  // extern "C"
+
+#ifdef GL_TUNING
+// tuning build only, below the file's last __LINE__-bearing check of the production code (the production object stays what it was):
+// launch_tap_split / launch_tap_pool_split alone (gl_tune_split_post, csrc/gl_tune.hip); pooled == nullptr: the tap without the pool
+int gl_tune_tap_split(gl_ctx *ctx, const char *f, int64_t n, int H, int W, int C, const float *coef, char *V, int64_t ldv, int64_t off, char *pooled, int fmt,
+                      float eps, int64_t row0)
+{
+    if (pooled) {
+        if (fmt) launch_tap_pool_split<true>(ctx->stream, f, n, H, W, C, coef, V, ldv, off, pooled, eps, row0);
+        else launch_tap_pool_split<false>(ctx->stream, f, n, H, W, C, coef, V, ldv, off, pooled, eps, row0);
+    } else {
+        if (fmt) launch_tap_split<true>(ctx->stream, f, n, H * W, C, coef, V, ldv, off, eps, row0);
+        else launch_tap_split<false>(ctx->stream, f, n, H * W, C, coef, V, ldv, off, eps, row0);
+    }
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+#endif

@@ -83,7 +83,7 @@ __global__ void __launch_bounds__(256) pixelnorm_split_kernel(char *__restrict__
             for (int o = 1; o < 64; o <<= 1) s1 = __fadd_rn(s1, __shfl_xor(s1, o, 64));
             ss = c == 4 * lane ? s1 : __fadd_rn(ss, s1);
         }
-        const float inv = __fdiv_rn(kPgAct, __fsqrt_rn(__fadd_rn(__fdiv_rn(ss, (float)C), __fmul_rn(__fmul_rn(1e-8f, kPgAct), kPgAct))));
+        const float inv = __fdiv_rn(kPgAct, gl_sqrt_rn(__fadd_rn(__fdiv_rn(ss, (float)C), __fmul_rn(__fmul_rn(1e-8f, kPgAct), kPgAct))));
         for (int c = 4 * lane; c < C; c += 256) {
             char *q = p + (c >> 5) * 128 + (c & 31) * 2;
             const h4 hi = *reinterpret_cast<const h4 *>(q), lo = *reinterpret_cast<const h4 *>(q + 64);
@@ -543,3 +543,16 @@ int gl_pggan_forward(gl_pggan *g, const float *z_dev, int64_t n, int steps, floa
 }
 
 }  // extern "C"
+
+#ifdef GL_TUNING
+// tuning build only, below the file's last __LINE__-bearing check of the production code (the production object stays what it was):
+// pixelnorm_split_kernel alone, launched as pg_pixelnorm launches it (gl_tune_split_post, csrc/gl_tune.hip)
+int gl_tune_pixelnorm_split(gl_ctx *ctx, char *x, int64_t positions, int C)
+{
+    int64_t blocks = gl_ceil_div(positions, 4);
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(pixelnorm_split_kernel, dim3((unsigned)blocks), dim3(256), 0, ctx->stream, x, positions, C);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+#endif

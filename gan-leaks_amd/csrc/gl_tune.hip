@@ -1,6 +1,6 @@
 // TUNING BUILD ONLY (linked into libganleaks_hip_tuning.so, never into libganleaks_hip.so; not part of include/ganleaks.h).
-// Two entries: gl_tune_winograd_bound (a timing experiment, below) and gl_tune_conv_layer (one convolution launch on host arrays, for the
-// per-layer tests; at the end of the file).
+// Three entries: gl_tune_winograd_bound (a timing experiment, below), gl_tune_conv_layer (one convolution launch on host arrays, for the
+// per-layer tests) and gl_tune_split_post (one launch of a stand-alone PixelNorm / LPIPS tap kernel on a split activation; at the end of the file).
 //
 // gl_tune_winograd_bound: the measured UPPER bound of what Winograd F(2x2,3x3) could buy on the split-fp16 convolution path (VERDICT r2
 // "Next 1").  F(2x2,3x3) replaces a 3x3 convolution over P positions by 16 independent GEMMs  M_j = U_j (C_out x C_in) . V_j (C_in x P/4)
@@ -13,6 +13,7 @@
 // of 256 x 256, i.e. 4 x the staging bytes per MFMA) -- comes on top of ms[1].
 #include "gl_conv.h"
 #include <cmath>
+#include <cstring>
 #include <vector>
 
 namespace {
@@ -160,9 +161,35 @@ struct GlTuneConvLayer {                 // mirrored field by field in tests/con
     void *out_guards;                    // <- 2 * 4096 bytes: below | above the output
     int64_t sat_delta;                   // <- change of the context's split-store saturation counter
     int32_t form;                        // <- gl_tune_conv_form of the launch
-    int32_t reserved_i[7];               // room for the fused PixelNorm / toRGB / LPIPS tap fields
-    void *reserved_p[8];
+    // fused epilogues (split kernel, out_mode 2).  fuse: 0 none, 1 PixelNorm (pixnorm_act = kTuneActScale), 2 PixelNorm + toRGB (rgb_inv_act =
+    // 1 / kTuneActScale), 3 LPIPS tap (tap_scale 16384, tap_eps 1e-10 * kTuneActScale; + the 2 x 2 max-pool when tap_pool != 0), 4 tap AND
+    // PixelNorm (which the launcher must refuse).  rgb_out, the V rows and the pooled tensor each get an allocation of their own, pre-filled
+    // with `sentinel` between 4 KiB sentinel guards; for fuse 2 and 3 `out` must come back all sentinel.
+    int32_t fuse, rgb_n, tap_fmt, tap_pool;
+    int32_t reserved_i[3];
+    const float *rgb_w, *rgb_b;          // [rgb_n][cols], [rgb_n], true values
+    const float *tap_coef;               // [cols]
+    void *rgb_out;                       // <- n_img * Ho * Wo * 16 bytes ([pos][4] fp32)
+    void *tap_V;                         // <- v_bytes: the whole row buffer
+    void *pool_out;                      // <- n_img * (Ho / 2) * (Wo / 2) * cols * 4 bytes (split layout)
+    void *aux_guards;                    // <- 3 * 2 * 4096 bytes: below | above of rgb_out, V, pool (sentinel where the buffer was not used)
+    void *reserved_p[1];
+    int64_t tap_ldv, tap_off, tap_row0;  // as in GlGatherConv; tap_ldv < 0: K-blocked rows of -tap_ldv cells (tap_fmt 1 only)
+    int64_t v_bytes;                     // size of the V buffer; every row the launch may touch must lie inside (checked)
 };
+
+// the stand-alone kernels sit in anonymous namespaces: tuning-build wrappers at the end of gl_pggan.hip / gl_lpips.hip
+int gl_tune_pixelnorm_split(gl_ctx *ctx, char *x, int64_t positions, int C);
+int gl_tune_tap_split(gl_ctx *ctx, const char *f, int64_t n, int H, int W, int C, const float *coef, char *V, int64_t ldv, int64_t off, char *pooled, int fmt,
+                      float eps, int64_t row0);
+
+// bytes a V buffer needs for rows [0, rows) of k_end halves each in this layout, or -1 when layout and format do not go together
+static int64_t tune_v_need(int fmt, int64_t ldv, int64_t rows, int64_t k_end)
+{
+    if (fmt == 0) return (ldv > 0 && ldv % 128 == 0 && ldv >= k_end * 4) ? rows * ldv : -1;
+    if (ldv >= 0) return (ldv % 8 == 0 && ldv >= k_end * 2) ? rows * ldv : -1;
+    return (-ldv) * 64 >= k_end ? (rows + 255) / 256 * (-ldv) * 32768 : -1;
+}
 
 static const float kTuneActScale = 16.0f;        // gl_dcgan.hip kActScale
 
@@ -192,13 +219,32 @@ extern "C" int gl_tune_conv_layer(gl_ctx *ctx, GlTuneConvLayer *q)
     constexpr int64_t OG = 4096;
     const int64_t in_total = in_bytes + 2 * q->in_guard;
     const size_t w_elems = (size_t)q->phases * q->cols_pad * K;
+    const int fuse = q->fuse;
+    const bool f_rgb = fuse == 2, f_tap = fuse == 3 || fuse == 4, f_pool = f_tap && q->tap_pool != 0;
+    GL_REQUIRE(fuse >= 0 && fuse <= 4, "gl_tune_conv_layer: fuse=%d", fuse);
+    GL_REQUIRE(fuse == 0 || (h3 && q->out_mode == 2 && !q->tail_w && !q->planar && q->cols % 32 == 0), "gl_tune_conv_layer: the fused epilogues need the split kernel and split output");
+    GL_REQUIRE(fuse == 0 || q->aux_guards, "gl_tune_conv_layer: NULL aux_guards");
+    GL_REQUIRE(!f_rgb || (q->rgb_w && q->rgb_b && q->rgb_out && q->rgb_n >= 1 && q->rgb_n <= 4), "gl_tune_conv_layer: toRGB needs rgb_w, rgb_b, rgb_out and rgb_n in 1..4");
+    const int64_t rgb_bytes = f_rgb ? opos * 16 : 0;
+    const int64_t pool_bytes = f_pool ? q->n_img * (q->Ho / 2) * (q->Wo / 2) * q->cols * 4 : 0;
+    const int64_t v_bytes = f_tap ? q->v_bytes : 0;
+    if (f_tap) {
+        GL_REQUIRE(q->tap_coef && q->tap_V && (q->tap_fmt == 0 || q->tap_fmt == 1) && q->tap_row0 >= 0 && q->tap_off >= 0 && q->tap_off % 64 == 0 &&
+                       (!f_pool || q->pool_out),
+                   "gl_tune_conv_layer: bad tap arguments");
+        // the kernel takes the row from the output position: every row [tap_row0, tap_row0 + n_img) up to half tap_off + Ho * Wo * cols must lie
+        // inside the buffer the caller sized
+        const int64_t need = tune_v_need(q->tap_fmt, q->tap_ldv, q->tap_row0 + q->n_img, q->tap_off + (int64_t)q->Ho * q->Wo * q->cols);
+        GL_REQUIRE(need > 0 && need <= v_bytes, "gl_tune_conv_layer: the V rows need %lld bytes, v_bytes=%lld (tap_ldv=%lld)", (long long)need,
+                   (long long)v_bytes, (long long)q->tap_ldv);
+    }
 
-    char *d_in = nullptr, *d_split = nullptr, *d_out = nullptr, *d_tail = nullptr;
-    float *d_w = nullptr, *d_scale = nullptr, *d_shift = nullptr, *d_res = nullptr;
+    char *d_in = nullptr, *d_split = nullptr, *d_out = nullptr, *d_tail = nullptr, *d_rgb = nullptr, *d_V = nullptr, *d_pool = nullptr;
+    float *d_w = nullptr, *d_scale = nullptr, *d_shift = nullptr, *d_res = nullptr, *d_rgbw = nullptr, *d_rgbb = nullptr, *d_coef = nullptr;
     auto cleanup = [&]() {
         (void)hipStreamSynchronize(ctx->stream);
-        (void)hipFree(d_in); (void)hipFree(d_split); (void)hipFree(d_out); (void)hipFree(d_tail);
-        (void)hipFree(d_w); (void)hipFree(d_scale); (void)hipFree(d_shift); (void)hipFree(d_res);
+        (void)hipFree(d_in); (void)hipFree(d_split); (void)hipFree(d_out); (void)hipFree(d_tail); (void)hipFree(d_rgb); (void)hipFree(d_V); (void)hipFree(d_pool);
+        (void)hipFree(d_w); (void)hipFree(d_scale); (void)hipFree(d_shift); (void)hipFree(d_res); (void)hipFree(d_rgbw); (void)hipFree(d_rgbb); (void)hipFree(d_coef);
     };
 #define TUNE_HIP(e) do { if ((e) != hipSuccess) { gl_set_error("gl_tune_conv_layer: %s failed", #e); cleanup(); return GL_ERR_HIP; } } while (0)
 #define TUNE_RC(e) do { const int rc_ = (e); if (rc_ != GL_OK) { cleanup(); return rc_; } } while (0)
@@ -210,6 +256,25 @@ extern "C" int gl_tune_conv_layer(gl_ctx *ctx, GlTuneConvLayer *q)
     TUNE_HIP(hipMalloc((void **)&d_shift, (size_t)q->cmod * 4));
     if (q->residual) TUNE_HIP(hipMalloc((void **)&d_res, (size_t)(opos * q->cols * 4)));
     if (q->tail_w) TUNE_HIP(hipMalloc((void **)&d_tail, 24 * 1024));
+    if (f_rgb) {
+        TUNE_HIP(hipMalloc((void **)&d_rgb, (size_t)(rgb_bytes + 2 * OG)));
+        TUNE_HIP(hipMalloc((void **)&d_rgbw, (size_t)q->rgb_n * q->cols * 4));
+        TUNE_HIP(hipMalloc((void **)&d_rgbb, 16));
+        TUNE_HIP(hipMemcpy(d_rgbw, q->rgb_w, (size_t)q->rgb_n * q->cols * 4, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemset(d_rgbb, 0, 16));
+        TUNE_HIP(hipMemcpy(d_rgbb, q->rgb_b, (size_t)q->rgb_n * 4, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemsetAsync(d_rgb, q->sentinel & 0xFF, (size_t)(rgb_bytes + 2 * OG), ctx->stream));
+    }
+    if (f_tap) {
+        TUNE_HIP(hipMalloc((void **)&d_V, (size_t)(v_bytes + 2 * OG)));
+        TUNE_HIP(hipMalloc((void **)&d_coef, (size_t)q->cols * 4));
+        TUNE_HIP(hipMemcpy(d_coef, q->tap_coef, (size_t)q->cols * 4, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemsetAsync(d_V, q->sentinel & 0xFF, (size_t)(v_bytes + 2 * OG), ctx->stream));
+    }
+    if (f_pool) {
+        TUNE_HIP(hipMalloc((void **)&d_pool, (size_t)(pool_bytes + 2 * OG)));
+        TUNE_HIP(hipMemsetAsync(d_pool, q->sentinel & 0xFF, (size_t)(pool_bytes + 2 * OG), ctx->stream));
+    }
     {
         // input: [guard | tensor | guard] as fp32 rows of Cin values; the split path converts all of it, guards included
         std::vector<float> guard((size_t)(q->in_guard / 4), q->poison);
@@ -265,6 +330,12 @@ extern "C" int gl_tune_conv_layer(gl_ctx *ctx, GlTuneConvLayer *q)
         p.tail_w = d_tail; p.tail_out = reinterpret_cast<float *>(d_out + OG); p.tail_ld = opos;
         p.tail_scale = std::ldexp(1.0f / kTuneActScale, -q->tail_wexp);       // `out` is ignored by the fused-tail forms; it stays inside the guarded block
     }
+    if (fuse == 1 || fuse == 2 || fuse == 4) p.pixnorm_act = kTuneActScale;
+    if (f_rgb) { p.rgb_w = d_rgbw; p.rgb_b = d_rgbb; p.rgb_out = reinterpret_cast<float *>(d_rgb + OG); p.rgb_n = q->rgb_n; p.rgb_inv_act = 1.0f / kTuneActScale; }
+    if (f_tap) {
+        p.tap_V = d_V + OG; p.tap_coef = d_coef; p.tap_ldv = q->tap_ldv; p.tap_off = q->tap_off; p.tap_row0 = q->tap_row0; p.tap_fmt = q->tap_fmt;
+        p.tap_pool = f_pool ? d_pool + OG : nullptr; p.tap_scale = 16384.0f; p.tap_eps = 1e-10f * kTuneActScale;
+    }
     gl_tune_conv_form = 0;
     TUNE_RC(h3 ? gl_launch_gather_conv_h3(ctx, p, q->phases) : gl_tune_gather_conv(ctx, p, q->phases));
     TUNE_HIP(hipStreamSynchronize(ctx->stream));
@@ -277,6 +348,101 @@ extern "C" int gl_tune_conv_layer(gl_ctx *ctx, GlTuneConvLayer *q)
     TUNE_HIP(hipMemcpy(q->out_guards, d_out, (size_t)OG, hipMemcpyDeviceToHost));
     TUNE_HIP(hipMemcpy(reinterpret_cast<char *>(q->out_guards) + OG, d_out + OG + out_bytes, (size_t)OG, hipMemcpyDeviceToHost));
     TUNE_HIP(hipMemcpy(q->out, d_out + OG, (size_t)out_bytes, hipMemcpyDeviceToHost));
+    if (fuse) {
+        char *ag = reinterpret_cast<char *>(q->aux_guards);
+        std::memset(ag, q->sentinel & 0xFF, (size_t)(6 * OG));
+        char *bufs[3] = {d_rgb, d_V, d_pool};
+        void *host[3] = {q->rgb_out, q->tap_V, q->pool_out};
+        const int64_t bytes[3] = {rgb_bytes, v_bytes, pool_bytes};
+        for (int b = 0; b < 3; ++b) {
+            if (!bufs[b]) continue;
+            TUNE_HIP(hipMemcpy(ag + (2 * b) * OG, bufs[b], (size_t)OG, hipMemcpyDeviceToHost));
+            TUNE_HIP(hipMemcpy(ag + (2 * b + 1) * OG, bufs[b] + OG + bytes[b], (size_t)OG, hipMemcpyDeviceToHost));
+            TUNE_HIP(hipMemcpy(host[b], bufs[b] + OG, (size_t)bytes[b], hipMemcpyDeviceToHost));
+        }
+    }
+#undef TUNE_HIP
+#undef TUNE_RC
+    cleanup();
+    return GL_OK;
+}
+
+// gl_tune_split_post: ONE launch of a stand-alone kernel that follows a convolution on the split layout -- pixelnorm_split_kernel (op 0, in place),
+// lpips_tap_split_kernel (op 1) or lpips_tap_pool_split_kernel (op 2) -- on host bytes of a split activation [n_img * H * W][C], for
+// tests/test_gpu_conv_epilogues.py.  Same treatment as above: every buffer between 4 KiB sentinel guards, V and pool pre-filled with the sentinel,
+// raw bytes back.  The tap parameters mean what they mean in GlGatherConv; the scale is the kernels' own (16384).
+struct GlTuneSplitPost {                 // mirrored field by field in tests/conv_layer_common.py
+    int32_t op, C, H, W;
+    int64_t n_img;
+    int32_t tap_fmt, sentinel;
+    int64_t tap_ldv, tap_off, tap_row0, v_bytes;
+    float tap_eps;
+    int32_t reserved_i;
+    const void *act;                     // n_img * H * W * C * 4 bytes
+    const float *tap_coef;               // [C] (ops 1, 2)
+    void *act_out;                       // <- the activation buffer after the launch (op 0: normalised; ops 1, 2: must be unchanged)
+    void *tap_V;                         // <- v_bytes
+    void *pool_out;                      // <- n_img * (H / 2) * (W / 2) * C * 4 bytes (op 2)
+    void *guards;                        // <- 3 * 2 * 4096 bytes: below | above of the activation, V, pool
+};
+
+extern "C" int gl_tune_split_post(gl_ctx *ctx, GlTuneSplitPost *q)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && q && q->act && q->act_out && q->guards, "gl_tune_split_post: NULL argument");
+    GL_REQUIRE(q->op >= 0 && q->op <= 2 && q->n_img > 0 && q->H > 0 && q->W > 0 && q->C > 0 && q->C % 32 == 0, "gl_tune_split_post: bad problem");
+    const bool tap = q->op != 0, pool = q->op == 2;
+    constexpr int64_t OG = 4096;
+    const int64_t positions = q->n_img * q->H * q->W, act_bytes = positions * q->C * 4;
+    const int64_t v_bytes = tap ? q->v_bytes : 0, pool_bytes = pool ? q->n_img * (q->H / 2) * (q->W / 2) * q->C * 4 : 0;
+    if (tap) {
+        GL_REQUIRE((q->C == 64 || q->C == 128 || q->C == 256 || q->C == 512) && q->tap_coef && q->tap_V && (q->tap_fmt == 0 || q->tap_fmt == 1) &&
+                       q->tap_row0 >= 0 && q->tap_off >= 0 && q->tap_off % 64 == 0,
+                   "gl_tune_split_post: bad tap arguments");
+        GL_REQUIRE(!pool || (q->pool_out && q->H % 2 == 0 && q->W % 2 == 0), "gl_tune_split_post: the pool needs even H and W");
+        const int64_t need = tune_v_need(q->tap_fmt, q->tap_ldv, q->tap_row0 + q->n_img, q->tap_off + (int64_t)q->H * q->W * q->C);
+        GL_REQUIRE(need > 0 && need <= v_bytes, "gl_tune_split_post: the V rows need %lld bytes, v_bytes=%lld (tap_ldv=%lld)", (long long)need,
+                   (long long)v_bytes, (long long)q->tap_ldv);
+    }
+    char *d_act = nullptr, *d_V = nullptr, *d_pool = nullptr;
+    float *d_coef = nullptr;
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d_act); (void)hipFree(d_V); (void)hipFree(d_pool); (void)hipFree(d_coef);
+    };
+#define TUNE_HIP(e) do { if ((e) != hipSuccess) { gl_set_error("gl_tune_split_post: %s failed", #e); cleanup(); return GL_ERR_HIP; } } while (0)
+#define TUNE_RC(e) do { const int rc_ = (e); if (rc_ != GL_OK) { cleanup(); return rc_; } } while (0)
+    TUNE_HIP(hipMalloc((void **)&d_act, (size_t)(act_bytes + 2 * OG)));
+    TUNE_HIP(hipMemset(d_act, q->sentinel & 0xFF, (size_t)(act_bytes + 2 * OG)));
+    TUNE_HIP(hipMemcpy(d_act + OG, q->act, (size_t)act_bytes, hipMemcpyHostToDevice));
+    if (tap) {
+        TUNE_HIP(hipMalloc((void **)&d_V, (size_t)(v_bytes + 2 * OG)));
+        TUNE_HIP(hipMemset(d_V, q->sentinel & 0xFF, (size_t)(v_bytes + 2 * OG)));
+        TUNE_HIP(hipMalloc((void **)&d_coef, (size_t)q->C * 4));
+        TUNE_HIP(hipMemcpy(d_coef, q->tap_coef, (size_t)q->C * 4, hipMemcpyHostToDevice));
+    }
+    if (pool) {
+        TUNE_HIP(hipMalloc((void **)&d_pool, (size_t)(pool_bytes + 2 * OG)));
+        TUNE_HIP(hipMemset(d_pool, q->sentinel & 0xFF, (size_t)(pool_bytes + 2 * OG)));
+    }
+    TUNE_HIP(hipDeviceSynchronize());
+    if (!tap) TUNE_RC(gl_tune_pixelnorm_split(ctx, d_act + OG, positions, q->C));
+    else TUNE_RC(gl_tune_tap_split(ctx, d_act + OG, q->n_img, q->H, q->W, q->C, d_coef, d_V + OG, q->tap_ldv, q->tap_off, pool ? d_pool + OG : nullptr, q->tap_fmt,
+                                   q->tap_eps, q->tap_row0));
+    TUNE_HIP(hipStreamSynchronize(ctx->stream));
+    {
+        char *g = reinterpret_cast<char *>(q->guards);
+        std::memset(g, q->sentinel & 0xFF, (size_t)(6 * OG));
+        char *bufs[3] = {d_act, d_V, d_pool};
+        void *host[3] = {q->act_out, q->tap_V, q->pool_out};
+        const int64_t bytes[3] = {act_bytes, v_bytes, pool_bytes};
+        for (int b = 0; b < 3; ++b) {
+            if (!bufs[b]) continue;
+            TUNE_HIP(hipMemcpy(g + (2 * b) * OG, bufs[b], (size_t)OG, hipMemcpyDeviceToHost));
+            TUNE_HIP(hipMemcpy(g + (2 * b + 1) * OG, bufs[b] + OG + bytes[b], (size_t)OG, hipMemcpyDeviceToHost));
+            TUNE_HIP(hipMemcpy(host[b], bufs[b] + OG, (size_t)bytes[b], hipMemcpyDeviceToHost));
+        }
+    }
 #undef TUNE_HIP
 #undef TUNE_RC
     cleanup();

@@ -51,7 +51,8 @@ def tap_sets(kind):
 
 class Case(object):
     def __init__(self, name, kernel, taps, n, H, W, Cin, cols, form, out="f32", cmod=None, act=0, up=0, residual=False, tail=False,
-                 cols_pad=None, inputs="struct", env=None, big=False, sat=None, atol=None, data=None):
+                 cols_pad=None, inputs="struct", env=None, big=False, sat=None, atol=None, data=None, fuse=0, rgb_n=0, tap_fmt=0, tap_pool=False,
+                 tap_layout="row", tap_row0=0, tap_off=0, refused=None):
         self.name, self.kernel, self.kind, self.n, self.H, self.W, self.Cin, self.cols, self.form = name, kernel, taps, n, H, W, Cin, cols, form
         self.taps, self.oy, self.ox, self.omul = tap_sets(taps)
         self.phases, self.ntaps = len(self.taps), len(self.taps[0])
@@ -71,6 +72,10 @@ class Case(object):
         self.ld_planar = self.positions
         self.wexp = 11 if inputs in ("struct", "arith_x", "act34") else 12
         self.tail_wexp = 11
+        # fused epilogues (the second half of this file): 0 none, 1 PixelNorm, 2 PixelNorm + toRGB, 3 LPIPS tap, 4 tap + PixelNorm (refused)
+        self.fuse, self.rgb_n, self.tap_fmt, self.tap_pool, self.tap_layout = fuse, rgb_n, tap_fmt, tap_pool, tap_layout
+        self.tap_row0, self.tap_off = tap_row0, tap_off
+        self.refused = refused                # None, or a piece of the error message the launcher must refuse the case with
 
     @property
     def in_guard(self):
@@ -393,11 +398,19 @@ class TuneConvLayer(ctypes.Structure):          # csrc/gl_tune.hip GlTuneConvLay
                 ("poison", ctypes.c_float), ("sentinel", ctypes.c_int32),
                 ("in_guard", ctypes.c_int64), ("out_bytes", ctypes.c_int64),
                 ("out", ctypes.c_void_p), ("in_guards", ctypes.c_void_p), ("out_guards", ctypes.c_void_p),
-                ("sat_delta", ctypes.c_int64), ("form", ctypes.c_int32), ("reserved_i", ctypes.c_int32 * 7), ("reserved_p", ctypes.c_void_p * 8)]
+                ("sat_delta", ctypes.c_int64), ("form", ctypes.c_int32),
+                ("fuse", ctypes.c_int32), ("rgb_n", ctypes.c_int32), ("tap_fmt", ctypes.c_int32), ("tap_pool", ctypes.c_int32),
+                ("reserved_i", ctypes.c_int32 * 3),
+                ("rgb_w", ctypes.c_void_p), ("rgb_b", ctypes.c_void_p), ("tap_coef", ctypes.c_void_p),
+                ("rgb_out", ctypes.c_void_p), ("tap_V", ctypes.c_void_p), ("pool_out", ctypes.c_void_p), ("aux_guards", ctypes.c_void_p),
+                ("reserved_p", ctypes.c_void_p * 1),
+                ("tap_ldv", ctypes.c_int64), ("tap_off", ctypes.c_int64), ("tap_row0", ctypes.c_int64), ("v_bytes", ctypes.c_int64)]
 
 
-def run_layer(lib, ctx_handle, c, d):
-    """one launch through gl_tune_conv_layer -> dict(out=bytes, in_guards=(lo, hi), out_guards=(lo, hi), sat_delta, form)"""
+def run_layer(lib, ctx_handle, c, d, fuse=None):
+    """one launch through gl_tune_conv_layer -> dict(out=bytes, in_guards=(lo, hi), out_guards=(lo, hi), sat_delta, form) and, for a fused
+    epilogue, rgb / V / pool = raw bytes, aux_guards = [(lo, hi)] * 3 in that order.  fuse=0: the same case without its fused epilogue"""
+    fuse = c.fuse if fuse is None else fuse
     q = TuneConvLayer()
     q.kernel, q.phases, q.ntaps, q.up, q.n_img = (1 if c.kernel == "h3" else 0), c.phases, c.ntaps, c.up, c.n
     q.H, q.W, q.Cin, q.cols, q.cols_pad, q.Ho, q.Wo, q.omul = c.H, c.W, c.Cin, c.cols, c.cols_pad, c.Ho, c.Wo, c.omul
@@ -419,6 +432,24 @@ def run_layer(lib, ctx_handle, c, d):
     ig = np.empty(2 * c.in_guard, np.uint8)
     og = np.empty(2 * OUT_GUARD, np.uint8)
     q.out, q.in_guards, q.out_guards = out.ctypes.data, ig.ctypes.data, og.ctypes.data
+    q.fuse = fuse
+    aux = {}
+    if fuse:
+        ag = aux["aux_guards"] = np.empty(6 * OUT_GUARD, np.uint8)
+        q.aux_guards = ag.ctypes.data
+    if fuse == 2:
+        rw = keep["rgb_w"] = np.ascontiguousarray(d["rgb_w"][:c.rgb_n], np.float32)
+        rb = keep["rgb_b"] = np.ascontiguousarray(d["rgb_b"][:c.rgb_n], np.float32)
+        aux["rgb"] = np.empty(c.opos * 16, np.uint8)
+        q.rgb_w, q.rgb_b, q.rgb_n, q.rgb_out = rw.ctypes.data, rb.ctypes.data, c.rgb_n, aux["rgb"].ctypes.data
+    if fuse in (3, 4):
+        tc = keep["tap_coef"] = np.ascontiguousarray(d["tap_coef"], np.float32)
+        ldv, vb = v_geometry(c)
+        aux["V"] = np.empty(vb, np.uint8)
+        q.tap_coef, q.tap_V, q.tap_fmt, q.tap_ldv, q.tap_off, q.tap_row0, q.v_bytes = tc.ctypes.data, aux["V"].ctypes.data, c.tap_fmt, ldv, c.tap_off, c.tap_row0, vb
+        if c.tap_pool:
+            aux["pool"] = np.empty(c.n * (c.Ho // 2) * (c.Wo // 2) * c.cols * 4, np.uint8)
+            q.tap_pool, q.pool_out = 1, aux["pool"].ctypes.data
     for k in c.env:
         os.environ[k] = c.env[k]
     try:
@@ -431,5 +462,359 @@ def run_layer(lib, ctx_handle, c, d):
     if rc != 0:
         lib.gl_last_error.restype = ctypes.c_char_p
         raise RuntimeError("gl_tune_conv_layer(%s): %s" % (c.name, lib.gl_last_error().decode()))
-    return {"out": out.tobytes(), "in_guards": (ig[:c.in_guard].tobytes(), ig[c.in_guard:].tobytes()),
-            "out_guards": (og[:OUT_GUARD].tobytes(), og[OUT_GUARD:].tobytes()), "sat_delta": int(q.sat_delta), "form": int(q.form)}
+    r = {"out": out.tobytes(), "in_guards": (ig[:c.in_guard].tobytes(), ig[c.in_guard:].tobytes()),
+         "out_guards": (og[:OUT_GUARD].tobytes(), og[OUT_GUARD:].tobytes()), "sat_delta": int(q.sat_delta), "form": int(q.form)}
+    if fuse:
+        ag = aux.pop("aux_guards")
+        r["aux_guards"] = [(ag[2 * b * OUT_GUARD:(2 * b + 1) * OUT_GUARD].tobytes(), ag[(2 * b + 1) * OUT_GUARD:(2 * b + 2) * OUT_GUARD].tobytes()) for b in range(3)]
+        r.update(aux)                           # rgb / V / pool stay numpy uint8 arrays (the V buffers are large)
+    return r
+
+
+# ====================================================================================================================================
+# The fused epilogues of csrc/gl_conv_h3_epi.h (PixelNorm, PixelNorm + toRGB, LPIPS tap + 2 x 2 max-pool) and their stand-alone siblings
+# (pixelnorm_split_kernel, lpips_tap_split_kernel, lpips_tap_pool_split_kernel): what tests/test_conv_epilogues_cpu.py and
+# tests/test_gpu_conv_epilogues.py share.
+#
+# References: float64, from the float64 activations of reference() -- PixelNorm v / sqrt(mean_c v^2 + 1e-8), toRGB b + W . v_norm,
+# tap v / (sqrt(sum_c v^2) + 1e-10) * coef * 16384, pool the plain 2 x 2 max.
+#
+# Exact cases: structural inputs with Cin = 32 and act 0 or 1.  The stored activations (value * ACT_SCALE) are then integer multiples of one
+# power of two (`stored_unit`), the sum of squares of a position is below 2^24 unit^2 and therefore exact in float32 IN ANY ORDER, and everything
+# after it is a fixed sequence of correctly rounded float32 operations (/, sqrt, +, *), which numpy's float32 reproduces; the fma residual of
+# PixelNorm's low half is computed in float64, where product and difference are exact, then rounded float32 -> float16 like the device's.
+# So the device bytes must equal the oracle's bit for bit.
+# Bounded cases (toRGB, act 2, the clamped pair, real-valued inputs): elementwise against float64,
+#     split values  |ref| 2^-21 + 2^-24 (stored units)       fp16 rows  |ref| (2^-11 + 2^-21) + 2^-25
+#     toRGB         S 2^-20 + 2^-24 |ref|,  S = sum_ch |w_ch v_ch|   (2^-21 relative per normalised value, <= 9 float32 roundings on any path)
+V_SCALE = 16384.0                                        # csrc/gl_feat_pair.h kVScale
+TAP_EPS = np.float32(1e-10) * np.float32(ACT_SCALE)      # normalize_tensor's eps in stored units
+PIX_EPS = np.float32(1e-8) * np.float32(ACT_SCALE) * np.float32(ACT_SCALE)
+TAP_OFF = 128                                            # non-zero multiple of 64
+HALO_SHAPE = (171, 32, 48)
+
+
+def v_geometry(c):
+    """-> (tap_ldv, v_bytes) of the V buffer a tap case writes into: room for rows [0, tap_row0 + n] and one unwritten chunk behind every row;
+    K-blocked: cells = ceil(K / 64) passed as a negative tap_ldv, whole 256-row blocks"""
+    k_end = c.tap_off + c.Ho * c.Wo * c.cols
+    if c.tap_layout == "blocked":
+        assert c.tap_fmt == 1
+        cells = (k_end + 63) // 64
+        return -cells, (c.tap_row0 + c.n + 255) // 256 * cells * 32768
+    ldv = k_end * 4 + 128 if c.tap_fmt == 0 else k_end * 2 + 64
+    return ldv, (c.tap_row0 + c.n + 1) * ldv
+
+
+TAP_VARIANTS = [(pool, fmt, layout) for pool in (False, True) for fmt, layout in ((0, "row"), (1, "row"), (1, "blocked"))]
+
+
+def _epi_cases():
+    pn, rgb, tap, refuse = [], [], [], []
+    shapes = {"t0": ((3, 6, 12), H3 | 0), "t1": ((3, 10, 10), H3 | 1)}
+
+    def conv(name, shape, cols, form, key, **kw):
+        n, H, W = shape
+        return Case(name, "h3", "c3", n, H, W, 32, cols, form, out="split", data=key, big=shape == HALO_SHAPE, **kw)
+    # ---- PixelNorm (mode 1): every fusable form, ragged tiles, cols below the tile's channels, UP, halo
+    for tile, colss in (("t0", (128, 96)), ("t1", (64, 32))):
+        shape, form = shapes[tile]
+        for cols in colss:
+            pn.append(conv("pn_%s_cols%d" % (tile, cols), shape, cols, form, "epi_%s_cols%d" % (tile, cols), fuse=1))
+            pn.append(conv("pn_up_%s_cols%d" % (tile, cols), shape, cols, form | UP, "epi_up_%s_cols%d" % (tile, cols), fuse=1, up=1, act=1))
+        pn.append(conv("pn_%s_cols%d_act2" % (tile, colss[0]), shape, colss[0], form, "epi_%s_cols%d_act2" % (tile, colss[0]), fuse=1, act=2))
+    for cols, wc in ((64, 1), (96, 2), (128, 2)):
+        pn.append(conv("pn_halo%d_cols%d" % (wc, cols), HALO_SHAPE, cols, HALO | wc, "epi_halo_cols%d" % cols, fuse=1))
+    pn.append(conv("pn_up_halo1_cols64", HALO_SHAPE, 64, HALO | 1, "epi_up_halo_cols64", fuse=1, up=1, act=1))
+    for sat in ("below", "above"):
+        pn.append(conv("pn_sat_%s" % sat, shapes["t0"][0], 128, H3 | 0, "epi_sat_%s" % sat, fuse=1, sat=sat))
+    # ---- PixelNorm + toRGB (mode 2)
+    for name, tile, cols, rn, act in (("rgb_t0_cols128", "t0", 128, 3, 0), ("rgb_t0_cols96", "t0", 96, 1, 0), ("rgb_t1_cols64", "t1", 64, 1, 0),
+                                      ("rgb_t1_cols32", "t1", 32, 3, 0), ("rgb_t0_cols128_act2", "t0", 128, 3, 2), ("rgb_t1_cols64_act2", "t1", 64, 3, 2)):
+        shape, form = shapes[tile]
+        rgb.append(conv(name, shape, cols, form, "epi_%s_cols%d%s" % (tile, cols, "_act2" if act else ""), fuse=2, rgb_n=rn, act=act))
+    rgb.append(conv("rgb_halo1_cols64", HALO_SHAPE, 64, HALO | 1, "epi_halo_cols64", fuse=2, rgb_n=3))
+    rgb.append(conv("rgb_halo2_cols96", HALO_SHAPE, 96, HALO | 2, "epi_halo_cols96", fuse=2, rgb_n=3))
+    rgb.append(conv("rgb_halo2_cols128", HALO_SHAPE, 128, HALO | 2, "epi_halo_cols128", fuse=2, rgb_n=1))
+    # ---- LPIPS tap (mode 3), act 1 like VGG16's ReLU.  W = 16, n = 2, H = 6: 192 positions, the image boundary at 96 lies inside the second wave's
+    # 64 positions and the tile is ragged; W = 32: the pool partner is two position tiles away
+    tshapes = [("tap_t1_w16_cols64", (2, 6, 16), 64, H3 | 1), ("tap_t1_w32_cols64", (3, 2, 32), 64, H3 | 1),
+               ("tap_t0_w16_cols128", (2, 6, 16), 128, H3 | 0), ("tap_t0_w16_cols96", (2, 6, 16), 96, H3 | 0),
+               ("tap_t0_w32_cols128", (1, 6, 32), 128, H3 | 0),
+               ("tap_halo1_cols64", HALO_SHAPE, 64, HALO | 1), ("tap_halo2_cols128", HALO_SHAPE, 128, HALO | 2)]
+    for name, shape, cols, form in tshapes:
+        for pool, fmt, layout in TAP_VARIANTS:
+            # K-blocked: the images cross the 256-row block boundary (rows 250 ... 420 of the halo shape, 255 ... of the small ones; a single
+            # image sits in the second block); row-major rows of the halo shape start at 2, to keep the buffer small
+            row0 = (250 if layout == "blocked" else 2) if shape == HALO_SHAPE else 255 if shape[0] > 1 else 257
+            tap.append(conv("%s_%s%s%s" % (name, "f16" if fmt else "split", "_blocked" if layout == "blocked" else "", "_pool" if pool else ""), shape, cols,
+                            form, "epi_" + name, fuse=3, act=1, tap_fmt=fmt, tap_layout=layout, tap_pool=pool, tap_row0=row0, tap_off=TAP_OFF))
+    # ---- what the launcher must refuse (an error, no convolution launch)
+    refuse.append(conv("refuse_pn_cols160_tile0", (3, 6, 12), 160, H3 | 0, "epi_refuse_cols160", fuse=1, refused="all 160 channels in one tile"))
+    refuse.append(conv("refuse_pn_tile5", (455, 24, 24), 96, H3 | 5, "epi_refuse_tile5", fuse=1, refused="all 96 channels in one tile"))
+    refuse.append(conv("refuse_tap_w12", (3, 6, 12), 128, H3 | 0, "epi_refuse_w12", fuse=3, act=1, tap_off=TAP_OFF, refused="tap cannot be fused"))
+    refuse.append(conv("refuse_tap_with_pixelnorm", (2, 6, 16), 128, H3 | 0, "epi_refuse_both", fuse=4, act=1, tap_off=TAP_OFF, refused="tap cannot be fused"))
+    refuse.append(conv("refuse_tap_switched_off", (2, 6, 16), 128, H3 | 0, "epi_refuse_switch", fuse=3, act=1, tap_off=TAP_OFF, env={"GL_TAP_FUSE": "0"},
+                       refused="tap cannot be fused"))
+    return pn, rgb, tap, refuse
+
+
+PN_CASES, RGB_CASES, TAP_CASES, REFUSE_CASES = _epi_cases()
+EPI_CASES = PN_CASES + RGB_CASES + TAP_CASES
+EPI_BY_NAME = dict((c.name, c) for c in EPI_CASES + REFUSE_CASES)
+assert len(EPI_BY_NAME) == len(EPI_CASES) + len(REFUSE_CASES) and not set(EPI_BY_NAME) & set(BY_NAME)
+
+
+def epi_exact(c):
+    """whether the case is compared bit for bit with the host oracle (else: with float64 under the derived bounds)"""
+    return c.fuse in (1, 3) and c.act in (0, 1) and c.sat is None and c.inputs == "struct"
+
+
+def chain_applies(c):
+    """fused == unfused, bit for bit: the stand-alone kernels exist for 64 and 128 channels (the tap's; PixelNorm's takes any C % 16 == 0)"""
+    return c.fuse in (1, 3) and c.cols in (64, 128)
+
+
+def make_epi_inputs(c):
+    """make_inputs + what the epilogue needs; the additions come from a generator of their own, so that the convolution's operands are those
+    of every other case of the key"""
+    d = make_inputs(c)
+    rng = np.random.default_rng(sum(c.key.encode()) * 104729 + 17)
+    d["tap_coef"] = rng.uniform(0.01, 1.0, size=c.cols).astype(np.float32)
+    d["rgb_w"] = (np.asarray([-2, -1, 1, 2], np.float32)[rng.integers(0, 4, size=(4, c.cols))] / np.float32(8)).astype(np.float32)
+    d["rgb_b"] = rng.integers(-3, 4, size=4).astype(np.float32)
+    return d
+
+
+# --------------------------------------------------------------------------------------------------------- float64 references
+def ref_clamped(c, ref):
+    """the activations as pass 1 of the fused PixelNorm / tap keeps them: clamped to the fp16 range of the stored value"""
+    return np.clip(ref, -F16_MAX / ACT_SCALE, F16_MAX / ACT_SCALE)
+
+
+def ref_pixelnorm(v):
+    """[..., C] float64 true values -> v / sqrt(mean_c v^2 + 1e-8)"""
+    return v / np.sqrt(np.mean(v * v, axis=-1, keepdims=True) + 1e-8)
+
+
+def ref_rgb(vn, w, b):
+    """-> (b + W . v_norm [positions][rgb_n], S = sum_ch |w_ch v_ch| [positions][rgb_n])"""
+    vn = vn.reshape(-1, vn.shape[-1])
+    w = np.asarray(w, np.float64)
+    return np.asarray(b, np.float64)[None, :] + vn @ w.T, np.abs(vn) @ np.abs(w).T
+
+
+def ref_tap(v, coef):
+    """[..., C] float64 true values -> the V values (stored units: * 16384)"""
+    return v / (np.sqrt(np.sum(v * v, axis=-1, keepdims=True)) + 1e-10) * np.asarray(coef, np.float64) * V_SCALE
+
+
+def pool2(v):
+    """[n][H][W][C] -> [n][H / 2][W / 2][C], the plain 2 x 2 max"""
+    n, H, W, C = v.shape
+    return v.reshape(n, H // 2, 2, W // 2, 2, C).max(axis=(2, 4))
+
+
+def bound_split(ref_stored):
+    return np.abs(ref_stored) * 2.0 ** -21 + 2.0 ** -24
+
+
+def bound_f16(ref_stored):
+    return np.abs(ref_stored) * (2.0 ** -11 + 2.0 ** -21) + 2.0 ** -25
+
+
+def bound_rgb(ref, S):
+    return S * 2.0 ** -20 + 2.0 ** -24 * np.abs(ref)
+
+
+# ------------------------------------------------------------------------------------------------------------ the exact oracle
+def stored_unit(c, d):
+    """the power of two every stored activation of a structural case is an integer multiple of (shift and sums are integers)"""
+    return ACT_SCALE * min(1.0, float(np.min(d["scale"])))
+
+
+def sumsq_problems(stored, unit):
+    """stored [positions][C] float64: the preconditions of the oracle -> list of violations"""
+    bad = []
+    if not np.array_equal(np.round(stored / unit) * unit, stored):
+        bad.append("stored values are no multiples of %g" % unit)
+    ss = float(np.max(np.sum(stored * stored, axis=-1))) / (unit * unit)
+    if not ss < 2.0 ** 24:
+        bad.append("sum of squares %g unit^2 is not below 2^24" % ss)
+    if not np.array_equal(decode_split(encode_split(stored), len(stored), stored.shape[1]), stored):
+        bad.append("stored values not representable as hi + lo")
+    return bad
+
+
+def _sumsq32(stored):
+    ss = np.sum(stored.astype(np.float64) ** 2, axis=-1)
+    assert np.array_equal(ss.astype(np.float32).astype(np.float64), ss)      # exact by the precondition
+    return ss.astype(np.float32)
+
+
+def _halves(t32):
+    """float32 -> (hi, lo) float16 as a split store of t makes them"""
+    hi = t32.astype(np.float16)
+    return hi, (t32 - hi.astype(np.float32)).astype(np.float16)
+
+
+def oracle_pixelnorm(stored):
+    """stored [positions][C] float32 (exact sums) -> (hi, lo) float16 of the normalised stored values, as both the fused epilogue and
+    pixelnorm_split_kernel compute them: inv = A / sqrt(ss / C + 1e-8 A A), hi = half(v * inv), lo = half(fma(v, inv, -hi))"""
+    stored = np.asarray(stored, np.float32)
+    A = np.float32(ACT_SCALE)
+    inv = A / np.sqrt(_sumsq32(stored) / np.float32(stored.shape[1]) + PIX_EPS)
+    assert inv.dtype == np.float32
+    prod = stored.astype(np.float64) * inv.astype(np.float64)[:, None]        # 24 x 24 bits: exact
+    hi = np.clip(prod.astype(np.float32), -F16_MAX, F16_MAX).astype(np.float16)
+    lo = (prod - hi.astype(np.float64)).astype(np.float32).astype(np.float16)  # the difference is exact in float64; fma rounds it once to float32
+    return hi, lo
+
+
+def oracle_tap(stored, coef):
+    """-> (hi, lo) float16 of the V values: inv = 16384 / (sqrt(ss) + eps), t = (v * inv) * coef with both products rounded to float32"""
+    stored = np.asarray(stored, np.float32)
+    inv = np.float32(V_SCALE) / (np.sqrt(_sumsq32(stored)) + TAP_EPS)
+    t = (stored * inv[:, None]) * np.asarray(coef, np.float32)[None, :]
+    assert t.dtype == np.float32
+    return _halves(t)
+
+
+def oracle_pool(stored_nhwc):
+    """[n][H][W][C] float32 stored values -> (hi, lo) float16 [n * H/2 * W/2][C]"""
+    m = pool2(np.asarray(stored_nhwc, np.float32))
+    return _halves(m.reshape(-1, m.shape[-1]))
+
+
+# ------------------------------------------------------------------------------------------------------------------- decoders
+def split_halves(buf, rows, d):
+    """split layout bytes [rows][d / 32][32 hi | 32 lo] -> (hi, lo) float16 [rows][d]"""
+    a = np.frombuffer(buf, np.float16).reshape(rows, d // 32, 2, 32)
+    return a[:, :, 0, :].reshape(rows, d), a[:, :, 1, :].reshape(rows, d)
+
+
+def halves_value(hi, lo):
+    return hi.astype(np.float64) + lo.astype(np.float64)
+
+
+def decode_rgb(buf, opos):
+    return np.frombuffer(buf, np.float32).reshape(opos, 4)
+
+
+def vrow_half_index(fmt, ldv, rows, ks):
+    """position, counted in halves from the start of the V buffer, of half k of buffer row r -> int64 [len(rows)][len(ks)]
+    fmt 0: split rows of ldv bytes, chunks of [32 hi | 32 lo] (the index is the hi half's; lo: + 32)
+    fmt 1, ldv >= 0: fp16 rows of ldv bytes;  ldv < 0: K-blocked [row / 256][-ldv cells][row % 256][64 halves]"""
+    r = np.asarray(rows, np.int64)[:, None]
+    k = np.asarray(ks, np.int64)[None, :]
+    if fmt == 0:
+        return r * (ldv // 2) + (k // 32) * 64 + k % 32
+    if ldv >= 0:
+        return r * (ldv // 2) + k
+    return ((r // 256) * (-ldv) + k // 64) * 16384 + (r % 256) * 64 + k % 64
+
+
+def decode_vrows(buf, fmt, ldv, row0, n, off, K):
+    """V buffer (uint8 array) -> (hi [n][K] float16, lo or None, whether every half outside the written range still holds the sentinel)"""
+    h = np.asarray(buf).view(np.uint16)
+    idx = vrow_half_index(fmt, ldv, np.arange(row0, row0 + n), np.arange(off, off + K))
+    written = np.zeros(len(h), bool)
+    written[idx] = True
+    hi = h[idx].view(np.float16)
+    lo = None
+    if fmt == 0:
+        written[idx + 32] = True
+        lo = h[idx + 32].view(np.float16)
+    rest_ok = bool(np.all(h[~written] == SENTINEL * 0x101))
+    return hi, lo, rest_ok
+
+
+# ------------------------------------------------------------------------------------------------- the stand-alone kernels
+class PostCase(object):
+    """one launch of gl_tune_split_post: op 0 pixelnorm_split_kernel, 1 lpips_tap_split_kernel, 2 lpips_tap_pool_split_kernel"""
+    def __init__(self, name, op, shape, C, inputs, tap_fmt=0, tap_layout="row", tap_row0=0, tap_off=0):
+        self.name, self.op, self.C, self.inputs = name, op, C, inputs
+        self.n, self.H, self.W = shape
+        self.Ho, self.Wo, self.cols = self.H, self.W, C                       # what v_geometry reads
+        self.tap_fmt, self.tap_layout, self.tap_row0, self.tap_off, self.tap_pool = tap_fmt, tap_layout, tap_row0, tap_off, op == 2
+        self.positions = self.n * self.H * self.W
+        self.key = "post_%s_%dx%dx%d_C%d" % ((inputs,) + tuple(shape) + (C,))
+
+    def __repr__(self):
+        return self.name
+
+
+def _post_cases():
+    c = []
+    for inputs in ("exact", "real"):
+        # 216 positions: a ragged last workgroup of 4 waves; C = 512: two sweeps of 256 channels
+        for C in (32, 64, 96, 128, 256, 512):
+            c.append(PostCase("post_pn_%s_C%d" % (inputs, C), 0, (3, 6, 12), C, inputs))
+        # 3 x 5 x 5 = 75 positions: ragged for 8, 4, 2 and 1 positions per wave;  3 x 6 x 10: 45 windows
+        for C in (64, 128, 256, 512):
+            for fmt, layout in ((0, "row"), (1, "row"), (1, "blocked")):
+                tag = "%s%s" % ("f16" if fmt else "split", "_blocked" if layout == "blocked" else "")
+                c.append(PostCase("post_tap_%s_C%d_%s" % (inputs, C, tag), 1, (3, 5, 5), C, inputs, fmt, layout, 255, TAP_OFF))
+                c.append(PostCase("post_tappool_%s_C%d_%s" % (inputs, C, tag), 2, (3, 6, 10), C, inputs, fmt, layout, 255, TAP_OFF))
+    return c
+
+
+POST_CASES = _post_cases()
+POST_BY_NAME = dict((c.name, c) for c in POST_CASES)
+assert len(POST_BY_NAME) == len(POST_CASES)
+
+
+def make_post_inputs(c):
+    """-> dict(stored [positions][C] float32: what the split activation holds, tap_coef)
+    exact: small non-zero integers and ONE odd integer in [2049, 3001] per position, which needs its low half; the sum of squares stays below
+    512 * 64 + 3001^2 < 2^24 for every C.  real: ReLU'd Gaussians * 16, rounded to hi + lo"""
+    rng = np.random.default_rng(sum(c.key.encode()) * 7919 + len(c.key))
+    if c.inputs == "exact":
+        v = rng.integers(1, 9, size=(c.positions, c.C)) * rng.choice([-1, 1], size=(c.positions, c.C))
+        v[np.arange(c.positions), rng.integers(0, c.C, size=c.positions)] = 2049 + 2 * rng.integers(0, 477, size=c.positions)
+        stored = v.astype(np.float32)
+    else:
+        raw = (np.maximum(rng.standard_normal((c.positions, c.C)), -0.25) * ACT_SCALE).astype(np.float32)
+        stored = decode_split(encode_split(raw), c.positions, c.C).astype(np.float32)
+    return {"stored": stored, "tap_coef": rng.uniform(0.01, 1.0, size=c.C).astype(np.float32)}
+
+
+class TuneSplitPost(ctypes.Structure):          # csrc/gl_tune.hip GlTuneSplitPost
+    _fields_ = [("op", ctypes.c_int32), ("C", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("n_img", ctypes.c_int64),
+                ("tap_fmt", ctypes.c_int32), ("sentinel", ctypes.c_int32),
+                ("tap_ldv", ctypes.c_int64), ("tap_off", ctypes.c_int64), ("tap_row0", ctypes.c_int64), ("v_bytes", ctypes.c_int64),
+                ("tap_eps", ctypes.c_float), ("reserved_i", ctypes.c_int32),
+                ("act", ctypes.c_void_p), ("tap_coef", ctypes.c_void_p),
+                ("act_out", ctypes.c_void_p), ("tap_V", ctypes.c_void_p), ("pool_out", ctypes.c_void_p), ("guards", ctypes.c_void_p)]
+
+
+def run_split_post(lib, ctx_handle, c, act_bytes, coef):
+    """one launch through gl_tune_split_post on the split activation `act_bytes` [n * H * W][C]; `c`: a PostCase, or a fused Case whose
+    stand-alone counterpart (same tap parameters) is meant -> dict(act=bytes, V, pool = uint8 arrays or None, guards=[(lo, hi)] * 3)"""
+    q = TuneSplitPost()
+    op = c.op if isinstance(c, PostCase) else (0 if c.fuse == 1 else 2 if c.tap_pool else 1)
+    q.op, q.C, q.H, q.W, q.n_img, q.sentinel = op, c.cols, c.Ho, c.Wo, c.n, SENTINEL
+    src = np.frombuffer(act_bytes, np.uint8)
+    assert len(src) == c.n * c.Ho * c.Wo * c.cols * 4
+    act_out = np.empty(len(src), np.uint8)
+    guards = np.empty(6 * OUT_GUARD, np.uint8)
+    q.act, q.act_out, q.guards = src.ctypes.data, act_out.ctypes.data, guards.ctypes.data
+    V = pool = None
+    if op:
+        tc = np.ascontiguousarray(coef, np.float32)
+        ldv, vb = v_geometry(c)
+        V = np.empty(vb, np.uint8)
+        q.tap_coef, q.tap_V, q.tap_fmt, q.tap_ldv, q.tap_off, q.tap_row0, q.v_bytes = tc.ctypes.data, V.ctypes.data, c.tap_fmt, ldv, c.tap_off, c.tap_row0, vb
+        q.tap_eps = float(TAP_EPS)
+    if op == 2:
+        pool = np.empty(c.n * (c.Ho // 2) * (c.Wo // 2) * c.cols * 4, np.uint8)
+        q.pool_out = pool.ctypes.data
+    lib.gl_tune_split_post.restype = ctypes.c_int
+    lib.gl_tune_split_post.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+    if lib.gl_tune_split_post(ctx_handle, ctypes.byref(q)) != 0:
+        lib.gl_last_error.restype = ctypes.c_char_p
+        raise RuntimeError("gl_tune_split_post(%s): %s" % (c.name, lib.gl_last_error().decode()))
+    return {"act": act_out.tobytes(), "V": V, "pool": pool,
+            "guards": [(guards[2 * b * OUT_GUARD:(2 * b + 1) * OUT_GUARD].tobytes(), guards[(2 * b + 1) * OUT_GUARD:(2 * b + 2) * OUT_GUARD].tobytes())
+                       for b in range(3)]}

@@ -109,6 +109,7 @@ SIGNATURES = {
     "gl_pbb_group_min": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "gl_pbb_accept": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p]),
     "gl_wb_adam_step": (_i, [_p, _p, _p, _p, _p, _i64, _i64] + [ctypes.c_float] * 7),
+    "gl_wb_diag_keys": (_i, [_p, _p, _i64, _i64, _p]),
     "gl_dcgan_create": (_i, [_p, _i, _i, _i, _pp]),
     "gl_dcgan_destroy": (_i, [_p]),
     "gl_dcgan_set_conv_weight": (_i, [_p, _i, _p]),
@@ -151,6 +152,9 @@ SIGNATURES = {
     "gl_lpips_feature_dim": (_i64, [_i, _i]),
     "gl_lpips_features_u8": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
     "gl_lpips_features_f32": (_i, [_p, _p, _i64, _i, _i, _p, _p]),
+    "gl_lpips_ref_dim": (_i64, [_i, _i]),
+    "gl_lpips_ref_rows_u8": (_i, [_p, _p, _i64, _i, _i, _p]),
+    "gl_lpips_grad_image": (_i, [_p, _p, _p, _p, _i64, _i, _i, _p, _p]),
     "gl_feat_knn": (_i, [_p, _p, _p, _i64, _i64, _p, _p, _i64, _i64, _p]),
     "gl_fbb_knn_lpips_host": (_i, [_p, _p, _p, _i64, _p, _i64, _i, _i, _i64, _i64, _p, _p]),
     "gl_rows_split_dim": (_i64, [_i64]),

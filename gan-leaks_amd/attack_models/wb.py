@@ -9,6 +9,7 @@ so that eval_roc.py scores the result unchanged.  The search is ganleaks_amd.wb.
     python -m ganleaks_amd.attack_models.wb --local_config config_attack_fbb.yaml --gan {dcgan,wgangp} --generator_path generator.pth
            [--nz --ngf] [--noise_path npz | --num_init N --init_seed s] [--steps --lr --beta1 --beta2] [--BATCH_SIZE]
     python -m ganleaks_amd.attack_models.wb ... --gan pggan --pg_steps N [--alpha a] [--in_channels C] --nz Z --resolution R ...
+    python -m ganleaks_amd.attack_models.wb ... --pair_distance l2-lpips
 
 --gan, --generator_path  the generator class and its state dict (what the training scripts save as generator.pth); VAEGAN has no backward
                          pass and is refused
@@ -19,6 +20,11 @@ so that eval_roc.py scores the result unchanged.  The search is ganleaks_amd.wb.
 --num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
 --BATCH_SIZE             only the first (N // BATCH_SIZE) * BATCH_SIZE latents take part in the start, as in fbb.py:77
 --steps, --lr, --beta1, --beta2   the descent (ganleaks_amd.wb.wb_attack)
+--pair_distance l2-lpips (default absent) the same attack under 0.2 * LPIPS + L2, the distance fbb.py hard-wires and the paper's white-box loss
+                         (ganleaks_amd.wb.pair_wb_attack); VGG16 and lin weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH; the
+                         start is the bank latent nearest under that distance; the resolution must be a multiple of 16.  {pos,neg}_key.npy
+                         (int64 [n, 1]: the uint32 pattern of the float32 distance, the exact and ordered score) takes the place of the S
+                         files, and the trace holds keys
 Files under ./wb_attack/<exp_name>/:
     {pos,neg}_loss.npy float64 [n, 1]: L(x, G(z*)); {pos,neg}_z.npy float32 [n, nz]: z*; {pos,neg}_S.npy int64 [n, 1]: the exact sum of
     squared differences behind the loss; {pos,neg}_init_loss.npy float64 [n, 1]: the full-black-box score the descent started from;
@@ -36,12 +42,13 @@ import numpy as np
 
 from ..attack import _dist32
 from ..pbb import pbb_init_from_bank
-from ..wb import wb_attack
+from ..wb import pair_wb_attack, wb_attack
 from .fbb import update_args  # noqa: F401  (the YAML overlay of the command line)
 from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, save_files
 
 # options added after params.txt got its form: an unused one leaves the file as it was before the option existed
-LATER_OPTIONS = ("pg_steps", "alpha", "in_channels")
+LATER_OPTIONS = ("pg_steps", "alpha", "in_channels", "pair_distance")
+PGGAN_OPTIONS = LATER_OPTIONS[:3]
 
 
 def parse_arguments(argv=None):
@@ -68,6 +75,8 @@ def parse_arguments(argv=None):
     parser.add_argument('--lr', type=float, default=0.05, help="Adam's step size")
     parser.add_argument('--beta1', type=float, default=0.9)
     parser.add_argument('--beta2', type=float, default=0.999)
+    parser.add_argument('--pair_distance', type=str, default=None, choices=['l2-lpips'],
+                        help='run the descent under 0.2 * LPIPS + L2 (weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH)')
     return parser.parse_args(argv)
 
 
@@ -76,7 +85,12 @@ def _request(args):
     if args.gan not in ("dcgan", "wgangp", "pggan"):
         raise SystemExit("--gan must be dcgan, wgangp or pggan, got %r: the backward pass is built for the DCGAN / WGAN-GP generator and for "
                          "PGGAN (VAEGAN is not)" % (args.gan,))
-    pg = [getattr(args, name, None) for name in LATER_OPTIONS]
+    pg = [getattr(args, name, None) for name in PGGAN_OPTIONS]
+    pair = getattr(args, "pair_distance", None)
+    if pair not in (None, "l2-lpips"):
+        raise SystemExit("--pair_distance must be l2-lpips, got %r (without it the descent runs on exact l2)" % (pair,))
+    if pair is not None and int(args.resolution) % 16:
+        raise SystemExit("--pair_distance l2-lpips needs a --resolution that is a multiple of 16 (VGG16 pools four times), got %s" % (args.resolution,))
     if args.gan == "pggan":
         if pg[0] is None:
             raise SystemExit("--gan pggan needs --pg_steps: PGGAN's depth (images of 4 * 2^pg_steps pixels) has no default here, and --steps "
@@ -142,6 +156,8 @@ def main(args):
     if len(z_bank) < int(args.BATCH_SIZE):
         raise SystemExit("the %d starting latents hold no full batch of %d" % (len(z_bank), args.BATCH_SIZE))
 
+    if getattr(args, "pair_distance", None) is not None:
+        return _main_pair(args, save_dir, both, n_pos, gen, z_bank)
     z_init, _ = pbb_init_from_bank(both, gen, z_bank, batch_size=int(args.BATCH_SIZE))
     dist, z_star, S, trace = wb_attack(both, gen, z_init, steps=int(args.steps), lr=float(args.lr), beta1=float(args.beta1), beta2=float(args.beta2),
                                        history=True)
@@ -154,6 +170,27 @@ def main(args):
     save_files(save_dir, ['pos_init_loss', 'neg_init_loss'], [np.ascontiguousarray(init_loss[:n_pos]), np.ascontiguousarray(init_loss[n_pos:])])
     save_files(save_dir, ['pos_trace', 'neg_trace'], [np.ascontiguousarray(trace[:, :n_pos]), np.ascontiguousarray(trace[:, n_pos:])])
     return save_dir, loss[:n_pos], loss[n_pos:], z_star, S
+
+
+def _main_pair(args, save_dir, both, n_pos, gen, z_bank):
+    """main() under --pair_distance l2-lpips: started from the bank latent nearest under that distance"""
+    from .. import lpips as _lp
+    from ..attack import GeneratedBank, attack
+    model = _lp.default_model()                          # FileNotFoundError names the two weight files
+    n_eff = (len(z_bank) // int(args.BATCH_SIZE)) * int(args.BATCH_SIZE)
+    _, idx = attack(both, GeneratedBank(gen, z_bank), distance="l2-lpips", batch_size=int(args.BATCH_SIZE), lpips=model)
+    assert (np.asarray(idx) < n_eff).all()
+    z_init = z_bank[np.asarray(idx)]
+    dist, z_star, key, trace = pair_wb_attack(both, gen, z_init, steps=int(args.steps), lr=float(args.lr), beta1=float(args.beta1),
+                                              beta2=float(args.beta2), history=True, lpips=model)
+    init = trace[0].astype(np.uint32).view(np.float32)                                # attack()'s float32 for the start
+    loss, init_loss, key = dist.astype(np.float64).reshape(-1, 1), init.astype(np.float64).reshape(-1, 1), key.reshape(-1, 1)
+    save_files(save_dir, ['pos_loss', 'neg_loss'], [np.ascontiguousarray(loss[:n_pos]), np.ascontiguousarray(loss[n_pos:])])
+    save_files(save_dir, ['pos_z', 'neg_z'], [np.ascontiguousarray(z_star[:n_pos]), np.ascontiguousarray(z_star[n_pos:])])
+    save_files(save_dir, ['pos_key', 'neg_key'], [np.ascontiguousarray(key[:n_pos]), np.ascontiguousarray(key[n_pos:])])
+    save_files(save_dir, ['pos_init_loss', 'neg_init_loss'], [np.ascontiguousarray(init_loss[:n_pos]), np.ascontiguousarray(init_loss[n_pos:])])
+    save_files(save_dir, ['pos_trace', 'neg_trace'], [np.ascontiguousarray(trace[:, :n_pos]), np.ascontiguousarray(trace[:, n_pos:])])
+    return save_dir, loss[:n_pos], loss[n_pos:], z_star, key
 
 
 if __name__ == '__main__':

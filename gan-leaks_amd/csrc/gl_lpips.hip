@@ -15,7 +15,7 @@
 //
 // Convolutions reuse gather_conv_kernel (gl_conv.hip): 3x3 p1 = 9 taps; the first layer (3 input channels)
 // is im2col'ed by the input kernel into one 32-wide K slice (27 values + 5 zeros).
-#include "gl_conv.h"
+#include "gl_lpips.h"
 #include "gl_pair256.h"
 #include "gl_feat_pair.h"
 #include <cmath>
@@ -27,7 +27,7 @@ using namespace gl_feat_pair;     // tile shapes, K segments and the row scale s
 
 namespace {
 
-constexpr int kNumConv = 13;
+constexpr int kNumConv = kLpNumConv;
 const int kCout[kNumConv] = {64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512, 512};
 const int kCin[kNumConv] = {3, 64, 64, 128, 128, 256, 256, 256, 512, 512, 512, 512, 512};
 // after conv index i: 1 = LPIPS tap, 2 = tap then 2x2 max-pool
@@ -1159,31 +1159,6 @@ feat_knn_h1s_kernel(const char *__restrict__ bank, const float *__restrict__ ban
 
 }  // namespace
 
-struct gl_lpips {
-    gl_ctx *ctx;
-    float *w[kNumConv];       // packed conv weights
-    float *bias[kNumConv];
-    float *ones;              // 512 ones (epilogue scale)
-    float *lin[5];            // raw lin weights (host-checked >= 0)
-    std::vector<float> lin_host[5];
-    bool have_w[kNumConv], have_lin[5];
-    // split-fp16 path: weights in the split layout scaled by 2^wexp, epilogue constants 2^-wexp and bias * kVggAct
-    int precision;
-    float *wsplit[kNumConv], *scale_h3[kNumConv], *bias_h3[kNumConv];
-    int wexp[kNumConv];
-    // the output of convolution i is stored as (value * act[i]) in the split layout; act[i] = 2^aexp[i], chosen per layer by a calibration
-    // pass on fixed synthetic images the first time the split path runs (lp_calibrate), kVggAct before that.  Powers of two: a value's halves
-    // only move in exponent, so wherever nothing clamps or falls into the fp16 subnormals the results do not depend on the choice.
-    float act[kNumConv];
-    std::vector<float> bias_host[kNumConv];
-    bool calibrated, calibrate;
-    unsigned *calib_max;      // device, kNumConv words: max |activation| per layer as float bits (set only during the calibration pass)
-    // workspace for `chunk` images of H x W
-    int64_t chunk, ws_imgs;
-    int ws_H, ws_W;
-    float *ws_a, *ws_b, *ws_coef;
-};
-
 namespace {
 
 int lp_upload(gl_ctx *ctx, float **dev, const std::vector<float> &host)
@@ -1569,6 +1544,7 @@ int gl_lpips_destroy(gl_lpips *l)
     gl_make_current(l ? l->ctx : nullptr);
     if (!l) return GL_OK;
     (void)hipStreamSynchronize(l->ctx->stream);
+    gl_lpips_grad_free(l);
     for (int i = 0; i < kNumConv; ++i) { (void)hipFree(l->w[i]); (void)hipFree(l->bias[i]); (void)hipFree(l->wsplit[i]); (void)hipFree(l->scale_h3[i]); (void)hipFree(l->bias_h3[i]); }
     for (int i = 0; i < 5; ++i) (void)hipFree(l->lin[i]);
     (void)hipFree(l->ones); (void)hipFree(l->ws_a); (void)hipFree(l->ws_b); (void)hipFree(l->ws_coef);
@@ -1644,6 +1620,8 @@ int gl_lpips_set_conv(gl_lpips *l, int conv_index, const float *w, const float *
         if (rc != GL_OK) return rc;
         l->bias_host[conv_index].assign(bias, bias + co_n);
     }
+    l->w_host[conv_index].assign(w, w + (size_t)co_n * ci_n * 9);      // the image gradient packs its transposes from these
+    l->grad_dirty = true;
     l->have_w[conv_index] = true;
     // new weights: back to the default activation scales until the next split-path call calibrates again
     for (int i = 0; i < kNumConv; ++i) l->act[i] = kVggAct;

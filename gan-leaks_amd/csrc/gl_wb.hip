@@ -30,6 +30,13 @@ __global__ void __launch_bounds__(kThreads) wb_adam_kernel(float *__restrict__ z
     }
 }
 
+// keys[i] = the uint32 pattern of M[i][i], zero-extended: the score of query i against its own image out of a block's pair distances
+__global__ void __launch_bounds__(kThreads) wb_diag_keys_kernel(const float *__restrict__ M, int64_t n, int64_t ld, uint64_t *__restrict__ keys)
+{
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) keys[i] = (uint64_t)__float_as_uint(M[i * ld + i]);
+}
+
 static inline bool finite_f(float x) { return x == x && x <= 3.402823466e38f && x >= -3.402823466e38f; }
 
 }  // namespace
@@ -53,6 +60,18 @@ int gl_wb_adam_step(gl_ctx *ctx, float *z_dev, float *m_dev, float *v_dev, const
     if (blocks > 65536) blocks = 65536;
     hipLaunchKernelGGL(wb_adam_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, z_dev, m_dev, v_dev, grad_dev, total, lr, beta1, beta2, eps,
                        c1, c2, z_max);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_wb_diag_keys(gl_ctx *ctx, const float *M_dev, int64_t n, int64_t ld, uint64_t *keys_dev)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx, "gl_wb_diag_keys: NULL ctx");
+    GL_REQUIRE(n >= 0 && ld >= n && (n == 0 || ld <= INT64_MAX / n), "gl_wb_diag_keys: bad sizes n=%lld ld=%lld", (long long)n, (long long)ld);
+    if (n == 0) return GL_OK;
+    GL_REQUIRE(M_dev && keys_dev, "gl_wb_diag_keys: NULL device pointer");
+    hipLaunchKernelGGL(wb_diag_keys_kernel, dim3((unsigned)gl_ceil_div(n, kThreads)), dim3(kThreads), 0, ctx->stream, M_dev, n, ld, keys_dev);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }

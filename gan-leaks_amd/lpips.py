@@ -17,7 +17,7 @@ import os
 
 import numpy as np
 
-from ._lib import Context, DeviceArray, check
+from ._lib import Context, DeviceArray, as_device, check
 from .attack import _to_device_rows, encode_if_lattice
 
 _p = ctypes.c_void_p
@@ -206,6 +206,43 @@ class LpipsModel:
         if role is not None:
             return FeatureBank(ctx, V, norms, n, K1, K - 3 * H * W, index_base, role, fmt, scale)
         return FeatureBank(ctx, V, norms, n, K, K - 3 * H * W, index_base)
+
+
+    # ---- the image gradient of the distance (csrc/gl_lpips_grad.hip): the white-box attack under 0.2 * LPIPS + L2
+    def _targets(self, targets_u8):
+        if not self._loaded:
+            raise RuntimeError("LpipsModel: weights not loaded")
+        shape = tuple(targets_u8.shape)
+        if len(shape) != 4 or shape[1] != 3:
+            raise ValueError("LPIPS needs images of shape [n,3,H,W], got %s" % (shape,))
+        n, _, H, W = shape
+        R = int(self.ctx.lib.gl_lpips_ref_dim(H, W))
+        if R < 0:
+            raise ValueError("LPIPS path needs H and W to be multiples of 16, got %dx%d" % (H, W))
+        return as_device(self.ctx, targets_u8, np.uint8), n, H, W, R
+
+    def reference_rows(self, targets_u8):
+        """the targets' side of grad_image: their normalised tap values, a float32 DeviceArray [n, gl_lpips_ref_dim(H, W)] (2 MB per 64 x 64
+        image).  The targets of a descent stay what they are, so their VGG16 forward runs once.  targets_u8 [n,3,H,W] uint8."""
+        td, n, H, W, R = self._targets(targets_u8)
+        ref = self.ctx.empty((max(n, 1), R), np.float32)
+        check(self.ctx.lib.gl_lpips_ref_rows_u8(self._handle, _p(td.ptr), n, H, W, _p(ref.ptr)))
+        return ref
+
+    def grad_image(self, y, targets_u8, ref=None):
+        """loss[i] = 0.2 * LPIPS(y_i, x_i) + mean (y_i - x_i)^2 for y [n,3,H,W] float32 and x = 2 u / 255 - 1 of targets_u8 [n,3,H,W] uint8, and
+        cot = d loss / d y -> (cot DeviceArray [n,3,H,W], loss DeviceArray [n]), float32.  VGG16 runs with fp32 products whatever
+        set_precision says.  ref: reference_rows(targets_u8); None computes them in the call, with the same result bit for bit."""
+        td, n, H, W, R = self._targets(targets_u8)
+        yd = as_device(self.ctx, y, np.float32)
+        if yd.nbytes != n * 3 * H * W * 4:
+            raise ValueError("expected images of shape %s float32, got %s" % ((n, 3, H, W), tuple(yd.shape)))
+        if ref is not None and (not isinstance(ref, DeviceArray) or ref.dtype != np.float32 or ref.nbytes != max(n, 1) * R * 4):
+            raise ValueError("ref must be reference_rows() of these %d targets: a float32 DeviceArray [%d, %d]" % (n, n, R))
+        cot, loss = self.ctx.empty((max(n, 1), 3, H, W), np.float32), self.ctx.empty((max(n, 1),), np.float32)
+        check(self.ctx.lib.gl_lpips_grad_image(self._handle, _p(yd.ptr), _p(td.ptr), _p(ref.ptr if ref is not None else 0), n, H, W, _p(cot.ptr),
+                                               _p(loss.ptr)))
+        return (cot, loss) if n else (cot.view((0, 3, H, W)), loss.view((0,)))
 
 
 def features_sharded(model, images_u8, comm):

@@ -28,18 +28,25 @@ _f = ctypes.c_float
 GL_PBB_PARTIAL_BYTES = 16    # include/ganleaks.h
 
 
-def _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, block_images, distance):
-    """everything that can be refused without a GPU; -> z_init float32 [Q, nz]"""
-    if distance == "l2-lpips":
-        raise NotImplementedError("wb_attack is built for distance='l2'; 0.2 * LPIPS + L2 needs the backward pass of the VGG16 features and is "
-                                  "not built")
-    if distance != "l2":
-        raise ValueError("distance must be 'l2', got %r" % (distance,))
+def _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, block_images, distance, gradient="l2_grad_z"):
+    """everything that can be refused without a GPU; -> z_init float32 [Q, nz].  gradient: the method the caller needs of the generator"""
+    if gradient == "l2_grad_z":
+        if distance == "l2-lpips":
+            raise NotImplementedError("wb_attack is built for distance='l2'; 0.2 * LPIPS + L2 needs the backward pass of the VGG16 features and is "
+                                      "not built into wb_attack: pair_wb_attack runs the descent under that distance")
+        if distance != "l2":
+            raise ValueError("distance must be 'l2', got %r" % (distance,))
+    else:
+        if distance == "l2":
+            raise ValueError("pair_wb_attack is built for distance='l2-lpips'; wb_attack runs the descent on exact 'l2'")
+        if distance != "l2-lpips":
+            raise ValueError("distance must be 'l2-lpips', got %r" % (distance,))
     if getattr(generator, "power_iterations", None) is not None:
         raise NotImplementedError("VAEGAN's generator (spectral normalisation advanced by every forward, self-attention) has no backward pass")
-    if not hasattr(generator, "l2_grad_z") or not hasattr(generator, "generate_u8"):
-        raise NotImplementedError("%s.%s has no l2_grad_z: the backward pass is built for the DCGAN / WGAN-GP generator and for PGGAN at a "
-                                  "fixed depth -- hand over pggan's Generator.at(steps, alpha)" % (type(generator).__module__, type(generator).__name__))
+    if not hasattr(generator, gradient) or not hasattr(generator, "generate_u8"):
+        raise NotImplementedError("%s.%s has no %s: the backward pass is built for the DCGAN / WGAN-GP generator and for PGGAN at a "
+                                  "fixed depth -- hand over pggan's Generator.at(steps, alpha)"
+                                  % (type(generator).__module__, type(generator).__name__, gradient))
     if int(steps) != steps or steps < 0:
         raise ValueError("steps must be an integer >= 0, got %r" % (steps,))
     for name, v in (("lr", lr), ("eps", eps), ("z_max", z_max)):
@@ -126,3 +133,142 @@ def wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.
         del u8
     dist = _dist32(S_out, d, "u8")
     return (dist, z_star, S_out, trace) if history else (dist, z_star, S_out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the same descent under 0.2 * LPIPS + L2, the distance fbb.py hard-wires and the paper's white-box loss (section 5.4)
+PAIR_BLOCK = 256        # queries scored per gl_feat_pair_dist* call: one tile of the pair kernels, and one block of K-blocked search rows
+
+
+def _forward_f32(generator, z_dev):
+    """G(z) of the generator's fp32-product forward -- the values vjp_z differentiates -- as a DeviceArray, with the precision setting the
+    caller sees put back"""
+    owner = getattr(generator, "generator", generator)             # pggan's Generator.at(steps, alpha) is a view of its Generator
+    before = owner._precision
+    owner.set_precision(0)
+    try:
+        if owner is generator:
+            y, _ = generator.forward_device(z_dev, True, False, check_range=False)
+        else:
+            y, _ = owner.forward_device(z_dev, generator.steps, generator.alpha, True, False, check_range=False)
+    finally:
+        owner.set_precision(before)
+    return y
+
+
+def pair_grad_z(generator, z, targets_u8, lpips=None, ref=None):
+    """loss[i] = 0.2 * LPIPS(G(z_i), x_i) + mean (G(z_i) - x_i)^2, x = 2 u / 255 - 1 of targets_u8 [n,3,H,W] uint8, and grad = d loss / d z:
+    -> (grad DeviceArray [n, nz], loss DeviceArray [n]), float32.  G(z) is the generator's fp32-product forward, the image gradient is
+    LpipsModel.grad_image's (csrc/gl_lpips_grad.hip) and the last step the generator's own vjp_z (DCGAN / WGAN-GP, pggan's
+    Generator.at(steps, alpha)).  lpips: the LpipsModel (default: lpips.default_model()); ref: its reference_rows(targets_u8)."""
+    from . import lpips as _lp
+    from ._lib import as_device
+    if not hasattr(generator, "vjp_z"):
+        raise NotImplementedError("%s.%s has no vjp_z" % (type(generator).__module__, type(generator).__name__))
+    model = lpips if lpips is not None else _lp.default_model()
+    z_dev = as_device(generator.ctx, z, np.float32)
+    y = _forward_f32(generator, z_dev)
+    n = z_dev.shape[0]
+    shape = tuple(int(v) for v in targets_u8.shape)
+    cot, loss = model.grad_image(y.view((n,) + shape[1:]), targets_u8, ref)
+    out = generator.vjp_z(z_dev, cot)                              # DCGAN: grad; the PGGAN view: (grad, y)
+    return (out[0] if isinstance(out, tuple) else out), loss
+
+
+def _pair_keys(ctx, model, fq, lo, u8_images, keys):
+    """keys[i] = bits(D32(query lo + i, image i)) for the nb images of a block: the images' bank rows, pair distances of blocks of PAIR_BLOCK
+    queries against the same block of images, and their diagonals"""
+    lib = ctx.lib
+    nb = u8_images.shape[0]
+    fb = model.features(u8_images, role=model.search_role("bank"), fmt=fq.fmt)
+    if fb.K != fq.K or fb.fmt != fq.fmt:
+        raise ValueError("the images' rows and the queries' rows differ in layout")
+    M = ctx.empty((PAIR_BLOCK, PAIR_BLOCK), np.float32)
+    esz = 2 if fq.role else 4
+    for b0 in range(0, nb, PAIR_BLOCK):
+        m = min(PAIR_BLOCK, nb - b0)
+        # where the rows are stored K-blocked, lo and b0 are multiples of PAIR_BLOCK = 256: whole blocks, each contiguous
+        qV = fq.V.ptr + (lo + b0) * fq.K * esz
+        bV = fb.V.ptr + b0 * fb.K * esz
+        qn, bn = fq.norms.ptr + (lo + b0) * 4, fb.norms.ptr + b0 * 4
+        if fq.role:
+            check(lib.gl_feat_pair_dist_h1_scaled(ctx.handle, _p(bV), _p(bn), m, _p(qV), _p(qn), m, fb.K, _f(fb.scale), _p(M.ptr), PAIR_BLOCK))
+        else:
+            check(lib.gl_feat_pair_dist(ctx.handle, _p(bV), _p(bn), m, _p(qV), _p(qn), m, fb.K, _p(M.ptr), PAIR_BLOCK))
+        check(lib.gl_wb_diag_keys(ctx.handle, _p(M.ptr), m, PAIR_BLOCK, _p(keys.ptr + b0 * 8)))
+    ctx.sync()                                                      # fb and M are released on return
+    return keys
+
+
+def pair_wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.999, eps=1e-8, z_max=4.0, block_images=1024, history=False,
+                   distance="l2-lpips", lpips=None):
+    """wb_attack under 0.2 * LPIPS + L2: gradient descent on the latent for every query, scored by the distance attack(distance='l2-lpips')
+    searches.
+
+    queries, generator, z_init, steps .. z_max, history: as wb_attack; the generator needs vjp_z and generate_u8, H and W multiples of 16
+    lpips: the LpipsModel (default: lpips.default_model(), weights from local files)
+    One step is pair_grad_z -> gl_wb_adam_step -> generate_u8 -> the pair distance D32(query, its image) of the search's own kernels, on the
+    search's own row formats -> gl_pbb_accept into a separate best-so-far, the key being the uint32 pattern of D32 (D32 >= +0: the unsigned
+    order of the patterns is the order of the floats).  Step 0 scores the start, so a score never rises, and started from the nearest bank
+    latent under l2-lpips the attack can only lower attack(distance='l2-lpips')'s answer.  block_images: queries per block (rounded up to a
+    multiple of 256 for images from 96 x 96, whose search rows are stored in blocks of 256); results do not depend on it.
+    returns (dist float32 [Q] -- the float whose pattern is key --, z_star float32 [Q, nz], key int64 [Q]), and with history=True also
+    trace int64 [steps + 1, Q]: the best key after every step, trace[0] the starting point's."""
+    z_host = _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, block_images, distance, gradient="vjp_z")
+    steps = int(steps)
+    Q, nz = z_host.shape
+    if len(queries) != Q:
+        raise ValueError("%d queries but %d starting latents" % (len(queries), Q))
+    image_shape = tuple(int(v) for v in (queries.shape if hasattr(queries, "shape") else np.shape(queries))[1:])
+    want_shape = getattr(generator, "image_shape", None)
+    if want_shape is not None and image_shape != tuple(want_shape):
+        raise ValueError("the queries are images of shape %r, the generator makes %r" % (image_shape, tuple(want_shape)))
+    if len(image_shape) != 3 or image_shape[0] != 3 or image_shape[1] % 16 or image_shape[2] % 16 or min(image_shape[1:]) < 16:
+        raise ValueError("the l2-lpips path needs [Q,3,H,W] images with H and W multiples of 16, got %r" % (image_shape,))
+    from . import lpips as _lp
+    ctx = generator.ctx
+    lib = ctx.lib
+    model = lpips if lpips is not None else _lp.default_model()
+    qu8 = prepare_images(ctx, queries)                   # raises ValueError off the 8-bit lattice
+    d = qu8.shape[1]
+    z_star = np.empty((Q, nz), np.float32)
+    key_out = np.empty((Q,), np.int64)
+    trace = np.empty((steps + 1, Q), np.int64) if history else None
+    per_block = int(block_images)
+    fq = model.features(qu8.view((Q,) + image_shape), role="query" if model.search_role("bank") else None) if Q else None
+    if Q and fq.blocked and per_block < Q:
+        per_block = -(-per_block // PAIR_BLOCK) * PAIR_BLOCK            # K-blocked rows (images from 96 x 96) come in blocks of 256
+
+    def images(z_dev, n):
+        u8 = generator.generate_u8(z_dev)
+        if not isinstance(u8, DeviceArray) or u8.dtype != np.uint8 or u8.nbytes != n * d:
+            raise ValueError("generate_u8 gave %s for %d latents; the queries hold %d values each" % (getattr(u8, "shape", None), n, d))
+        return u8.view((n,) + image_shape)
+
+    for lo in range(0, Q, per_block):
+        nb = min(per_block, Q - lo)
+        q_dev = qu8.view((nb,) + image_shape, offset_bytes=lo * d)
+        ref = model.reference_rows(q_dev) if steps else None
+        z, z_best = ctx.to_device(z_host[lo:lo + nb]), ctx.to_device(z_host[lo:lo + nb])
+        m, v = ctx.zeros((nb, nz), np.float32), ctx.zeros((nb, nz), np.float32)
+        one = ctx.to_device(np.ones((nb,), np.float32))                    # gl_pbb_accept's step width: not used here, stays 1
+        S_best, S_new = ctx.empty((nb,), np.uint64), ctx.empty((nb,), np.uint64)
+        j_new, accepted = ctx.zeros((nb,), np.int32), ctx.empty((nb,), np.uint8)
+        # step 0: the starting point itself, straight into S_best
+        _pair_keys(ctx, model, fq, lo, images(z, nb), S_best)
+        if history:
+            trace[0, lo:lo + nb] = S_best.numpy().astype(np.int64)
+        for t in range(1, steps + 1):
+            grad, _ = pair_grad_z(generator, z, q_dev, model, ref)
+            c1, c2 = 1.0 / (1.0 - float(beta1) ** t), 1.0 / (1.0 - float(beta2) ** t)
+            check(lib.gl_wb_adam_step(ctx.handle, _p(z.ptr), _p(m.ptr), _p(v.ptr), _p(grad.ptr), nb, nz, _f(lr), _f(beta1), _f(beta2), _f(eps), _f(c1),
+                                      _f(c2), _f(z_max)))
+            _pair_keys(ctx, model, fq, lo, images(z, nb), S_new)
+            check(lib.gl_pbb_accept(ctx.handle, _p(z_best.ptr), _p(one.ptr), _p(S_best.ptr), _p(z.ptr), _p(S_new.ptr), _p(j_new.ptr), nb, nz, 1,
+                                    _f(1.0), _f(1.0), _f(1.0), _f(1.0), _p(accepted.ptr)))
+            if history:
+                trace[t, lo:lo + nb] = S_best.numpy().astype(np.int64)
+        z_star[lo:lo + nb] = z_best.numpy()
+        key_out[lo:lo + nb] = S_best.numpy().astype(np.int64)
+    dist = key_out.astype(np.uint32).view(np.float32)
+    return (dist, z_star, key_out, trace) if history else (dist, z_star, key_out)

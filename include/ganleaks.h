@@ -386,6 +386,10 @@ int gl_pbb_accept(gl_ctx *ctx, float *z_dev, float *sigma_dev, uint64_t *S_cur_d
  * with c1 = 1 / (1 - beta1^t), c2 = 1 / (1 - beta2^t) computed by the caller in double and passed as floats.  z, m, v, grad [nq][nz]. */
 int gl_wb_adam_step(gl_ctx *ctx, float *z_dev, float *m_dev, float *v_dev, const float *grad_dev, int64_t nq, int64_t nz, float lr, float beta1,
                     float beta2, float eps, float c1, float c2, float z_max);
+/* keys[i] = the uint32 pattern of M[i * ld + i], zero-extended, i < n: the scores of n queries against their own images, taken from the diagonal
+ * of a block of pair distances (gl_feat_pair_dist*), in the form gl_pbb_accept compares.  The distances are >= +0, so the unsigned order of the
+ * patterns is the order of the floats.  Asynchronous. */
+int gl_wb_diag_keys(gl_ctx *ctx, const float *M_dev, int64_t n, int64_t ld, uint64_t *keys_dev);
 
 /* ---------------------------------------------------------------- sharded bank: the cross-GPU minimum (RCCL over xGMI) */
 /* The reference runs on one device (attack_models/fbb.py:40) and takes the minimum over the whole bank with torch.min (fbb.py:86).  With the bank
@@ -549,6 +553,21 @@ int64_t gl_lpips_feature_dim(int H, int W);
  * stored as 32 hi + 32 lo halves of V * 2^14, see csrc/gl_lpips.hip) and norms_dev [n] = |V|^2 */
 int gl_lpips_features_u8(gl_lpips *l, const uint8_t *img_u8_dev, int64_t n, int H, int W, float *V_dev, float *norms_dev);
 int gl_lpips_features_f32(gl_lpips *l, const float *img_f32_dev, int64_t n, int H, int W, float *V_dev, float *norms_dev);
+/* The image gradient of the distance (csrc/gl_lpips_grad.hip): for y [n][3][H][W] fp32 and targets x = 2 u / 255 - 1 of 8-bit codes,
+ *   loss[i] = 0.2 * LPIPS(y_i, x_i) + mean_k (y_i - x_i)^2   (Loss('l2-lpips'), attack_models/utils.py:166-176)   and   cot = d loss / d y,
+ * [n][3][H][W] fp32.  The call runs VGG16 with fp32 products whatever gl_lpips_set_precision says (precision, calibration and chunk stay as
+ * they are), keeps every activation of a pass and goes backwards through the taps, the max-pools, the ReLUs and the convolutions; every output
+ * is one fixed-order fp32 sum, so a row depends on its image alone.  A pass is gl_lpips_set_chunk's images, by default what fits 4 GiB of kept
+ * activations (4.9 MB per 64 x 64 image).  Where all channels of a tap position are zero the projection term of the normalisation's gradient
+ * is taken as 0.  ref_dev: the targets' normalised tap values from gl_lpips_ref_rows_u8, [n][gl_lpips_ref_dim(H, W)] fp32 -- the targets of a
+ * descent do not change, so their forward runs once; NULL: the call computes them itself, with the same result bit for bit.
+ * gl_lpips_ref_dim: sum_l C_l H_l W_l floats per image (499 712 at 64 x 64), -1 where gl_lpips_feature_dim is -1.
+ * n == 0 returns GL_OK; NULL pointers (ref_dev apart) and H, W that are no multiples of 16: GL_ERR_INVALID; weights not loaded: GL_ERR_STATE.
+ * Asynchronous on the context's stream. */
+int64_t gl_lpips_ref_dim(int H, int W);
+int gl_lpips_ref_rows_u8(gl_lpips *l, const uint8_t *target_u8_dev, int64_t n, int H, int W, float *ref_dev);
+int gl_lpips_grad_image(gl_lpips *l, const float *y_f32_dev, const uint8_t *target_u8_dev, const float *ref_dev, int64_t n, int H, int W,
+                        float *cot_dev, float *loss_dev);
 /* keys[q] = min(keys[q], (float_bits(max(|V_q|^2 + |V_n|^2 - 2 V_q.V_n, 0)) << 32) | (index_base + n)), n < n_rows.
  * custom_knn (attack_models/fbb.py:73-88) with Loss('l2-lpips'); unpack with gl_keys_unpack_f32.  The contraction runs as three
  * fp16 MFMAs per product on the hi/lo halves (fp32 accumulation). */

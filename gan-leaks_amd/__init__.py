@@ -19,5 +19,5 @@ from .attack import ball_counts_rows, count_balls_rows, eps_to_ssd_rows, kth_dis
 from .attack import count_balls_rows_f32, density_ratio_loss, density_ratio_loss_f32, eps_rows_to_bits, pair_ball_counts_rows, pair_kth_distances  # noqa: F401
 from .attack import kde_coef, kde_loss, kde_scores, kde_sums  # noqa: F401
 from .attack import kde_cut_bits_rows, kde_sums_f32, pair_kde_scores  # noqa: F401
-from .pbb import pbb_attack, pbb_init_from_bank  # noqa: F401
+from .pbb import pair_pbb_attack, pair_pbb_init_from_bank, pbb_attack, pbb_init_from_bank  # noqa: F401
 from .wb import pair_grad_z, pair_wb_attack, wb_attack  # noqa: F401

@@ -107,6 +107,7 @@ SIGNATURES = {
     "gl_fbb_knn_l2_host": (_i, [_p, _p, _i64, _p, _i64, _i64, _i64, _p, _p]),
     "gl_pbb_candidates": (_i, [_p, _p, _p, _i64, _i64, _i64, ctypes.c_uint64, ctypes.c_uint32, _i64, ctypes.c_float, _p]),
     "gl_pbb_group_min": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
+    "gl_pbb_group_min_keys": (_i, [_p, _p, _i64, _i64, _i64, _p, _p]),
     "gl_pbb_accept": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p]),
     "gl_wb_adam_step": (_i, [_p, _p, _p, _p, _p, _i64, _i64] + [ctypes.c_float] * 7),
     "gl_wb_diag_keys": (_i, [_p, _p, _i64, _i64, _p]),

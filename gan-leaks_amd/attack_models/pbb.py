@@ -10,6 +10,7 @@ only improve on.
     python -m ganleaks_amd.attack_models.pbb --local_config config_attack_fbb.yaml --gan {dcgan,wgangp,pggan} --generator_path generator.pth
            [--nz --ngf --in_channels --steps --alpha] [--noise_path npz | --num_init N --init_seed s]
            [--rounds --population --sigma --seed] [--BATCH_SIZE]
+    python -m ganleaks_amd.attack_models.pbb ... --pair_distance l2-lpips
 
 --gan, --generator_path  the generator class and its state dict (what the training scripts save as generator.pth)
 --nz, --ngf              DCGAN / WGAN-GP: latent length and width (features_g); --nz, --in_channels, --steps, --alpha: PGGAN
@@ -17,10 +18,15 @@ only improve on.
 --num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
 --BATCH_SIZE             only the first (N // BATCH_SIZE) * BATCH_SIZE latents take part in the start, as in fbb.py:77
 --rounds, --population, --sigma, --seed   the search (ganleaks_amd.pbb.pbb_attack)
+--pair_distance l2-lpips (default absent) the same attack under 0.2 * LPIPS + L2, the distance fbb.py hard-wires and the paper's loss
+                         (ganleaks_amd.pbb.pair_pbb_attack); VGG16 and lin weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH; the
+                         start is the bank latent nearest under that distance (pair_pbb_init_from_bank); the resolution must be a multiple
+                         of 16.  {pos,neg}_key.npy (int64 [n, 1]: the uint32 pattern of the float32 distance, the exact and ordered score)
+                         takes the place of the S files, and the trace holds keys
 Files under ./pbb_attack/<exp_name>/:
     {pos,neg}_loss.npy float64 [n, 1]: L(x, G(z*)); {pos,neg}_z.npy float32 [n, nz]: z*; {pos,neg}_S.npy int64 [n, 1]: the exact sum of
     squared differences behind the loss; {pos,neg}_init_loss.npy float64 [n, 1]: the full-black-box score the search started from;
-    {pos,neg}_trace.npy int64 [rounds + 1, n]: S after every round; params.txt.  Small = member-like:
+    {pos,neg}_trace.npy int64 [rounds + 1, n]: S after every round; params.txt (an absent --pair_distance leaves no line).  Small = member-like:
     `eval_roc --attack_type pbb -ldir pbb_attack/<exp_name>` scores the attack.
 One GPU; the queries of a larger set can be split by hand (pbb_attack's query_base keeps the noise of every query what it was).
 """
@@ -33,9 +39,12 @@ import warnings
 import numpy as np
 
 from ..attack import _dist32
-from ..pbb import pbb_attack, pbb_init_from_bank
+from ..pbb import pair_pbb_attack, pair_pbb_init_from_bank, pbb_attack, pbb_init_from_bank
 from .fbb import update_args  # noqa: F401  (the YAML overlay of the command line)
 from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, save_files
+
+# options added after params.txt got its form: an unused one leaves the file as it was before the option existed
+LATER_OPTIONS = ("pair_distance",)
 
 
 def parse_arguments(argv=None):
@@ -62,11 +71,18 @@ def parse_arguments(argv=None):
     parser.add_argument('--population', type=int, default=64, help='candidates per query and round')
     parser.add_argument('--sigma', type=float, default=0.5, help='initial step width')
     parser.add_argument('--seed', type=int, default=0, help='seed of the search noise')
+    parser.add_argument('--pair_distance', type=str, default=None, choices=['l2-lpips'],
+                        help='run the search under 0.2 * LPIPS + L2 (weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH)')
     return parser.parse_args(argv)
 
 
 def _request(args):
     """what can be refused before any file is read"""
+    pair = getattr(args, "pair_distance", None)
+    if pair not in (None, "l2-lpips"):
+        raise SystemExit("--pair_distance must be l2-lpips, got %r (without it the search runs on exact l2)" % (pair,))
+    if pair is not None and int(args.resolution) % 16:
+        raise SystemExit("--pair_distance l2-lpips needs a --resolution that is a multiple of 16 (VGG16 pools four times), got %s" % (args.resolution,))
     if getattr(args, "generator_path", None) is None:
         raise SystemExit("--generator_path is needed: the partial-black-box attacker holds the generator")
     if (getattr(args, "noise_path", None) is None) == (getattr(args, "num_init", None) is None):
@@ -99,7 +115,7 @@ def main(args):
     _request(args)
     assert os.path.exists(args.generator_path)
     save_dir = check_folder(os.path.join(os.getcwd(), 'pbb_attack', args.exp_name))
-    lines = ["%s:%s" % (key, value) for key, value in vars(args).items()]
+    lines = ["%s:%s" % (key, value) for key, value in vars(args).items() if not (key in LATER_OPTIONS and value is None)]
     with open(os.path.join(save_dir, 'params.txt'), 'w') as handle:
         handle.write("".join(line + "\n" for line in lines))
     print("\n".join(lines))
@@ -122,6 +138,8 @@ def main(args):
     if len(z_bank) < int(args.BATCH_SIZE):
         raise SystemExit("the %d starting latents hold no full batch of %d" % (len(z_bank), args.BATCH_SIZE))
 
+    if getattr(args, "pair_distance", None) is not None:
+        return _main_pair(args, save_dir, both, n_pos, gen, kw, z_bank)
     z_init, _ = pbb_init_from_bank(both, gen, z_bank, batch_size=int(args.BATCH_SIZE), **kw)
     dist, z_star, S, trace = pbb_attack(both, gen, z_init, rounds=int(args.rounds), population=int(args.population), sigma=float(args.sigma),
                                         seed=int(args.seed), history=True, **kw)
@@ -134,6 +152,23 @@ def main(args):
     save_files(save_dir, ['pos_init_loss', 'neg_init_loss'], [np.ascontiguousarray(init_loss[:n_pos]), np.ascontiguousarray(init_loss[n_pos:])])
     save_files(save_dir, ['pos_trace', 'neg_trace'], [np.ascontiguousarray(trace[:, :n_pos]), np.ascontiguousarray(trace[:, n_pos:])])
     return save_dir, loss[:n_pos], loss[n_pos:], z_star, S
+
+
+def _main_pair(args, save_dir, both, n_pos, gen, kw, z_bank):
+    """main() under --pair_distance l2-lpips: started from the bank latent nearest under that distance"""
+    from .. import lpips as _lp
+    model = _lp.default_model()                          # FileNotFoundError names the two weight files
+    z_init, _ = pair_pbb_init_from_bank(both, gen, z_bank, batch_size=int(args.BATCH_SIZE), lpips=model, **kw)
+    dist, z_star, key, trace = pair_pbb_attack(both, gen, z_init, rounds=int(args.rounds), population=int(args.population), sigma=float(args.sigma),
+                                               seed=int(args.seed), history=True, lpips=model, **kw)
+    init = trace[0].astype(np.uint32).view(np.float32)                                # attack()'s float32 for the start
+    loss, init_loss, key = dist.astype(np.float64).reshape(-1, 1), init.astype(np.float64).reshape(-1, 1), key.reshape(-1, 1)
+    save_files(save_dir, ['pos_loss', 'neg_loss'], [np.ascontiguousarray(loss[:n_pos]), np.ascontiguousarray(loss[n_pos:])])
+    save_files(save_dir, ['pos_z', 'neg_z'], [np.ascontiguousarray(z_star[:n_pos]), np.ascontiguousarray(z_star[n_pos:])])
+    save_files(save_dir, ['pos_key', 'neg_key'], [np.ascontiguousarray(key[:n_pos]), np.ascontiguousarray(key[n_pos:])])
+    save_files(save_dir, ['pos_init_loss', 'neg_init_loss'], [np.ascontiguousarray(init_loss[:n_pos]), np.ascontiguousarray(init_loss[n_pos:])])
+    save_files(save_dir, ['pos_trace', 'neg_trace'], [np.ascontiguousarray(trace[:, :n_pos]), np.ascontiguousarray(trace[:, n_pos:])])
+    return save_dir, loss[:n_pos], loss[n_pos:], z_star, key
 
 
 if __name__ == '__main__':

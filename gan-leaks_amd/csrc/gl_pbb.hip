@@ -4,6 +4,8 @@
 //     the generator     : all nq * lambda candidates in one pass (gl_dcgan_forward / gl_pggan_forward, not touched here)
 //     gl_pbb_group_min  : every query against its OWN lambda images only -- exact S = sum (a - b)^2 and the minimum of (S, j)
 //     gl_pbb_accept     : the winner replaces the incumbent where it is strictly closer; sigma grows on success and shrinks otherwise.
+// Under 0.2 LPIPS + L2 the third step is gl_feat_pair_dist* on the candidates' search rows and gl_pbb_group_min_keys over the stored block
+// of pair distances: the minimum of the uint32 patterns of every query's own lambda columns.
 // Everything is a pure function of (seed, round, global query index, j, c) and of exact integers, so the result does not depend on how
 // the queries are blocked or sharded.  No tuning variables are read.
 #include "gl_common.h"
@@ -197,6 +199,34 @@ __global__ void __launch_bounds__(kThreads) pbb_combine_kernel(const pbb_partial
     out_j[q] = best.j;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- grouped minimum of keys
+// The same reduction over a stored block of pair distances M (gl_feat_pair_dist*): one wave per query, four queries per workgroup.  The
+// lanes stride over the query's own lambda columns (coalesced), each keeps the minimum of (pattern << 32) | j, and a butterfly leaves the
+// wave's minimum in every lane: the smallest pattern, and among equal patterns the smallest j.  D32 >= +0, so the unsigned order of the
+// patterns is the order of the floats.
+__global__ void __launch_bounds__(kThreads) pbb_group_min_keys_kernel(const float *__restrict__ M, int64_t nq, int64_t lambda, int64_t ld,
+                                                                      unsigned long long *__restrict__ keys, int *__restrict__ out_j)
+{
+    const int64_t q = (int64_t)blockIdx.x * WAVES + (threadIdx.x >> 6);
+    if (q >= nq) return;                               // wave-uniform; no barrier below
+    const int lane = threadIdx.x & 63;
+    const float *row = M + q * ld + q * lambda;
+    unsigned long long best = ~0ull;
+    for (int64_t j = lane; j < lambda; j += 64) {
+        const unsigned long long v = ((unsigned long long)__float_as_uint(row[j]) << 32) | (unsigned long long)j;
+        best = v < best ? v : best;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(best, o, 64);
+        best = other < best ? other : best;
+    }
+    if (lane == 0) {
+        keys[q] = best >> 32;
+        out_j[q] = (int)(best & 0xffffffffull);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- accept
 // one wave per query.  Every lane reads the decision before lane 0 overwrites S_cur.
 __global__ void __launch_bounds__(64) pbb_accept_kernel(float *__restrict__ z, float *__restrict__ sigma, unsigned long long *__restrict__ S_cur,
@@ -275,6 +305,25 @@ int gl_pbb_group_min(gl_ctx *ctx, const uint8_t *queries_u8_dev, const uint8_t *
     GL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pbb_combine_kernel, dim3((unsigned)gl_ceil_div(nq, kThreads)), dim3(kThreads), 0, ctx->stream, part, nq, (int)groups,
                        reinterpret_cast<unsigned long long *>(out_S_dev), out_j_dev);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_pbb_group_min_keys(gl_ctx *ctx, const float *M_dev, int64_t nq, int64_t lambda, int64_t ld, uint64_t *keys_dev, int32_t *j_dev)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx, "gl_pbb_group_min_keys: NULL ctx");
+    GL_REQUIRE(nq >= 0 && nq < (1ll << 31) && lambda >= 1 && lambda < (1ll << 31), "gl_pbb_group_min_keys: bad sizes nq=%lld lambda=%lld", (long long)nq,
+               (long long)lambda);
+    // nq * lambda < 2^62 after the check above; the last element read is M[(nq - 1) * ld + nq * lambda - 1], below nq * ld
+    GL_REQUIRE(ld >= nq * lambda && (nq == 0 || ld <= INT64_MAX / 4 / nq), "gl_pbb_group_min_keys: ld=%lld must hold nq * lambda = %lld * %lld columns",
+               (long long)ld, (long long)nq, (long long)lambda);
+    if (nq == 0) return GL_OK;
+    GL_REQUIRE(M_dev && keys_dev && j_dev, "gl_pbb_group_min_keys: NULL device pointer");
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(M_dev) & 3) == 0 && (reinterpret_cast<uintptr_t>(keys_dev) & 7) == 0 &&
+               (reinterpret_cast<uintptr_t>(j_dev) & 3) == 0, "gl_pbb_group_min_keys: M_dev, j_dev must be 4-byte and keys_dev 8-byte aligned");
+    hipLaunchKernelGGL(pbb_group_min_keys_kernel, dim3((unsigned)gl_ceil_div(nq, WAVES)), dim3(kThreads), 0, ctx->stream, M_dev, nq, lambda, ld,
+                       reinterpret_cast<unsigned long long *>(keys_dev), j_dev);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }

@@ -12,6 +12,11 @@ The strategy is elitist, so the score of a query never rises from round to round
 the nearest bank latent (pbb_init_from_bank) the attack refines the full-black-box answer and can only lower it.  Distances are exact
 integers and the noise is integer arithmetic up to one rounded product, so results do not depend on block_images or on how the queries are
 sharded (query_base).
+
+pair_pbb_attack is the same strategy under 0.2 * LPIPS + L2, the distance fbb.py hard-wires: the candidates' images go through VGG16 into
+the search's own rows (LpipsModel.features), gl_feat_pair_dist* scores a tile of 256 queries against the tile's candidates, and
+gl_pbb_group_min_keys takes every query's minimum over its OWN lambda columns on the uint32 pattern of the float32 distance -- the score
+attack(distance='l2-lpips') reports for that pair, bit for bit.  pair_pbb_init_from_bank is its start.
 """
 from __future__ import annotations
 
@@ -29,13 +34,21 @@ GL_PBB_GROUP = 16            # include/ganleaks.h
 GL_PBB_PARTIAL_BYTES = 16
 
 
-def _check_arguments(generator, z_init, rounds, population, sigma, distance, up, down, sigma_min, sigma_max, z_max, block_images, query_base):
-    """everything that can be refused without a GPU; -> z_init float32 [Q, nz]"""
-    if distance == "l2-lpips":
-        raise NotImplementedError("pbb_attack is built for distance='l2' (exact integer S on 8-bit images); 0.2 * LPIPS + L2 needs the VGG16 "
-                                  "features of every candidate and is not built")
-    if distance != "l2":
-        raise ValueError("distance must be 'l2', got %r" % (distance,))
+def _check_arguments(generator, z_init, rounds, population, sigma, distance, up, down, sigma_min, sigma_max, z_max, block_images, query_base,
+                     pair=False):
+    """everything that can be refused without a GPU; -> z_init float32 [Q, nz].  pair: the caller is pair_pbb_attack"""
+    if pair:
+        if distance == "l2":
+            raise ValueError("pair_pbb_attack is built for distance='l2-lpips'; pbb_attack runs the search on exact 'l2'")
+        if distance != "l2-lpips":
+            raise ValueError("distance must be 'l2-lpips', got %r" % (distance,))
+    else:
+        if distance == "l2-lpips":
+            raise NotImplementedError("pbb_attack is built for distance='l2' (exact integer S on 8-bit images); 0.2 * LPIPS + L2 needs the VGG16 "
+                                      "features of every candidate and is not built into pbb_attack: pair_pbb_attack runs the search under "
+                                      "that distance")
+        if distance != "l2":
+            raise ValueError("distance must be 'l2', got %r" % (distance,))
     if not hasattr(generator, "generate_u8"):
         raise TypeError("generator must provide generate_u8(z, ...) -> u8 DeviceArray")
     if getattr(generator, "power_iterations", None) is not None:
@@ -129,6 +142,125 @@ def pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=0.5, 
         del u8
     dist = _dist32(S_out, d, "u8")
     return (dist, z_star, S_out, trace) if history else (dist, z_star, S_out)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the same search under 0.2 * LPIPS + L2, the distance fbb.py hard-wires and the loss of the paper (section 5.3)
+def pair_pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=0.5, seed=0, up=1.5, down=1.5 ** -0.25, sigma_min=1e-4,
+                    sigma_max=4.0, z_max=4.0, block_images=4096, query_base=0, history=False, distance="l2-lpips", lpips=None, **generate_kwargs):
+    """pbb_attack under 0.2 * LPIPS + L2: the same (1 + lambda) strategy, scored by the distance attack(distance='l2-lpips') searches.
+
+    queries, generator, z_init, rounds .. z_max, seed, query_base, history, generate_kwargs: as pbb_attack; [Q,3,H,W] images, H and W
+    multiples of 16.  lpips: the LpipsModel (default: lpips.default_model(), weights from local files)
+    A round is gl_pbb_candidates (the candidates pbb_attack would draw for the same seed, query_base and incumbents) -> generate_u8 on all
+    nb * lambda latents -> their search rows (LpipsModel.features, the bank's role) -> per tile of 256 queries one gl_feat_pair_dist* call of
+    the tile's queries against the tile's candidates and gl_pbb_group_min_keys over every query's own lambda columns -> gl_pbb_accept.  The
+    key is the uint32 pattern of D32(query, image) out of the search's own pair kernels (D32 >= +0: the unsigned order of the patterns is
+    the order of the floats), so key == bits(pair_distances(query, generate_u8(z_star))).  Round 0 scores the start, the strategy is
+    elitist: a key never rises, and started from pair_pbb_init_from_bank the attack can only lower attack(distance='l2-lpips')'s answer.
+    D32 is a function of the two rows alone and the noise one of the global query index, so results do not depend on block_images or on
+    how the queries are split with query_base.
+    block_images: candidate images generated and turned into rows at a time -- queries go in blocks of max(1, block_images // population)
+    (rounded up to a multiple of 256 for images from 96 x 96, whose search rows are stored in blocks of 256).  One block's candidate rows
+    (1 MB per 64 x 64 image) and its block of pair distances are allocated once and reused by every round; ValueError before the first
+    round when they do not fit the device.
+    returns (dist float32 [Q] -- the float whose pattern is key --, z_star float32 [Q, nz], key int64 [Q]), and with history=True also
+    trace int64 [rounds + 1, Q]: the key after every round, trace[0] the starting point's."""
+    z_host = _check_arguments(generator, z_init, rounds, population, sigma, distance, up, down, sigma_min, sigma_max, z_max, block_images,
+                              query_base, pair=True)
+    rounds, lam, seed, query_base = int(rounds), int(population), int(seed) & 0xFFFFFFFFFFFFFFFF, int(query_base)
+    Q, nz = z_host.shape
+    if len(queries) != Q:
+        raise ValueError("%d queries but %d starting latents" % (len(queries), Q))
+    image_shape = tuple(int(v) for v in (queries.shape if hasattr(queries, "shape") else np.shape(queries))[1:])
+    if len(image_shape) != 3 or image_shape[0] != 3 or image_shape[1] % 16 or image_shape[2] % 16 or min(image_shape[1:]) < 16:
+        raise ValueError("the l2-lpips path needs [Q,3,H,W] images with H and W multiples of 16, got %r" % (image_shape,))
+    from . import lpips as _lp
+    from .wb import PAIR_BLOCK, _pair_keys
+    ctx = generator.ctx
+    lib = ctx.lib
+    model = lpips if lpips is not None else _lp.default_model()
+    qu8 = prepare_images(ctx, queries)                   # raises ValueError off the 8-bit lattice
+    d = qu8.shape[1]
+    z_star = np.empty((Q, nz), np.float32)
+    key_out = np.empty((Q,), np.int64)
+    trace = np.empty((rounds + 1, Q), np.int64) if history else None
+    if Q == 0:
+        dist = key_out.astype(np.uint32).view(np.float32)
+        return (dist, z_star, key_out, trace) if history else (dist, z_star, key_out)
+    bank_role = model.search_role("bank")
+    fq = model.features(qu8.view((Q,) + image_shape), role="query" if bank_role else None)
+    per_block = max(1, int(block_images) // lam)
+    if fq.blocked and per_block < Q:
+        per_block = -(-per_block // PAIR_BLOCK) * PAIR_BLOCK            # K-blocked rows (images from 96 x 96) come in blocks of 256
+    per_block = min(per_block, Q)
+    tile = min(PAIR_BLOCK, per_block)                    # queries per gl_feat_pair_dist* call; M is [tile][tile * lambda]
+    esz = 2 if fq.role else 4
+    cand = fb = M = None
+    if rounds:
+        rows = per_block * lam
+        cap = int(lib.gl_lpips_search_rows_capacity(rows, fq.K)) if fq.role else rows
+        need, avail = cap * fq.K * esz + tile * tile * lam * 4, ctx.mem_info()[0]
+        if need > avail:
+            raise ValueError("a block of %d queries x %d candidates needs %d bytes for the candidates' rows and their pair distances; %d are "
+                             "available: lower population or block_images" % (per_block, lam, need, avail))
+        cand = ctx.empty((rows, nz), np.float32)
+        M = ctx.empty((tile, tile * lam), np.float32)
+
+    def images(z_dev, n):
+        u8 = generator.generate_u8(z_dev, **generate_kwargs)
+        if not isinstance(u8, DeviceArray) or u8.dtype != np.uint8 or u8.nbytes != n * d:
+            raise ValueError("generate_u8 gave %s for %d latents; the queries hold %d values each" % (getattr(u8, "shape", None), n, d))
+        return u8.view((n,) + image_shape)
+
+    for lo in range(0, Q, per_block):
+        nb = min(per_block, Q - lo)
+        z = ctx.to_device(z_host[lo:lo + nb])
+        sig = ctx.to_device(np.full((nb,), sigma, np.float32))
+        S_cur, S_new = ctx.empty((nb,), np.uint64), ctx.empty((nb,), np.uint64)
+        j_new, accepted = ctx.empty((nb,), np.int32), ctx.empty((nb,), np.uint8)
+        # round 0: the starting point itself (lambda = 1), straight into S_cur
+        _pair_keys(ctx, model, fq, lo, images(z, nb), S_cur)
+        if history:
+            trace[0, lo:lo + nb] = S_cur.numpy().astype(np.int64)
+        cz = cand.view((nb * lam, nz)) if rounds else None
+        for r in range(1, rounds + 1):
+            check(lib.gl_pbb_candidates(ctx.handle, _p(z.ptr), _p(sig.ptr), nb, nz, lam, ctypes.c_uint64(seed), ctypes.c_uint32(r), query_base + lo,
+                                        _f(z_max), _p(cz.ptr)))
+            # the first block is the largest: its rows are the buffer every later round and block writes into
+            fb = model.features(images(cz, nb * lam), role=bank_role, fmt=fq.fmt, out=fb)
+            if fb.K != fq.K or fb.fmt != fq.fmt:
+                raise ValueError("the candidates' rows and the queries' rows differ in layout")
+            for b0 in range(0, nb, tile):
+                m = min(tile, nb - b0)
+                # where the rows are stored K-blocked, tile = 256 and lo is a multiple of 256: lo + b0 and b0 * lambda are whole blocks
+                qV, qn = fq.V.ptr + (lo + b0) * fq.K * esz, fq.norms.ptr + (lo + b0) * 4
+                bV, bn = fb.V.ptr + b0 * lam * fb.K * esz, fb.norms.ptr + b0 * lam * 4
+                if fq.role:
+                    check(lib.gl_feat_pair_dist_h1_scaled(ctx.handle, _p(bV), _p(bn), m * lam, _p(qV), _p(qn), m, fb.K, _f(fb.scale), _p(M.ptr),
+                                                          tile * lam))
+                else:
+                    check(lib.gl_feat_pair_dist(ctx.handle, _p(bV), _p(bn), m * lam, _p(qV), _p(qn), m, fb.K, _p(M.ptr), tile * lam))
+                check(lib.gl_pbb_group_min_keys(ctx.handle, _p(M.ptr), m, lam, tile * lam, _p(S_new.ptr + b0 * 8), _p(j_new.ptr + b0 * 4)))
+            check(lib.gl_pbb_accept(ctx.handle, _p(z.ptr), _p(sig.ptr), _p(S_cur.ptr), _p(cz.ptr), _p(S_new.ptr), _p(j_new.ptr), nb, nz, lam,
+                                    _f(up), _f(down), _f(sigma_min), _f(sigma_max), _p(accepted.ptr)))
+            if history:
+                trace[r, lo:lo + nb] = S_cur.numpy().astype(np.int64)
+        z_star[lo:lo + nb] = z.numpy()
+        key_out[lo:lo + nb] = S_cur.numpy().astype(np.int64)
+    dist = key_out.astype(np.uint32).view(np.float32)
+    return (dist, z_star, key_out, trace) if history else (dist, z_star, key_out)
+
+
+def pair_pbb_init_from_bank(queries, generator, z_bank, batch_size=64, lpips=None, **generate_kwargs):
+    """the start of pair_pbb_attack: the latent of every query's nearest bank sample under 0.2 * LPIPS + L2 -- the full-black-box answer,
+    attack(queries, GeneratedBank(generator, z_bank), distance='l2-lpips', batch_size=..., lpips=...).
+    -> (z_bank[idx] float32 [Q, nz], idx int64 [Q])"""
+    if type(z_bank).__module__.startswith("torch"):
+        z_bank = z_bank.detach().cpu().numpy()
+    z_bank = np.asarray(z_bank, np.float32)
+    _, idx = attack(queries, GeneratedBank(generator, z_bank, **generate_kwargs), distance="l2-lpips", batch_size=batch_size, lpips=lpips)
+    return np.ascontiguousarray(z_bank[idx].reshape(len(idx), -1)), idx
 
 
 def pbb_init_from_bank(queries, generator, z_bank, batch_size=64, **generate_kwargs):

@@ -343,7 +343,9 @@ int gl_fbb_knn_l2_host(gl_ctx *ctx, const uint8_t *bank_u8_host, int64_t n_bank,
  * GAN-Leaks' second attack (section 5.3 of the paper; the reference fork ships only fbb.py): the attacker holds the generator, searches
  * z* = argmin_z L(x, G(z)) without gradients and scores the query by L(x, G(z*)).  Built as a (1 + lambda) evolution strategy per query:
  * a round is gl_pbb_candidates -> the generator on all nq * lambda latents -> gl_pbb_group_min -> gl_pbb_accept, with everything resident on
- * the device.  All three run on the context's stream, do not synchronise, return GL_OK for nq == 0 and read no tuning variable. */
+ * the device.  Under 0.2 LPIPS + L2, the distance fbb.main hard-wires, the third step is the candidates' search rows (gl_lpips_*_features_*),
+ * gl_feat_pair_dist* per tile of 256 queries against the tile's own candidates and gl_pbb_group_min_keys over the stored block; the other
+ * steps are the same.  All four run on the context's stream, do not synchronise, return GL_OK for nq == 0 and read no tuning variable. */
 /* the bit pattern of C = float32(1 / (65536 sqrt(8/3))) = 9.344062e-06, the scale of the noise below */
 #define GL_PBB_NOISE_SCALE_BITS 0x371CC471u
 /* out[(q * lambda + j) * nz + c] = clamp(fl32(z[q * nz + c] + fl32(sigma[q] * eps)), -z_max, z_max), each operation rounded on its own (no
@@ -367,6 +369,16 @@ int gl_pbb_candidates(gl_ctx *ctx, const float *z_dev, const float *sigma_dev, i
 #define GL_PBB_PARTIAL_BYTES 16
 int gl_pbb_group_min(gl_ctx *ctx, const uint8_t *queries_u8_dev, const uint8_t *cand_u8_dev, int64_t nq, int64_t lambda, int64_t d, uint64_t *out_S_dev,
                      int32_t *out_j_dev, void *workspace_dev);
+/* The grouped minimum under 0.2 LPIPS + L2, the distance fbb.main hard-wires (attack_models/fbb.py:148), over a stored block of pair
+ * distances: M_dev is what gl_feat_pair_dist / gl_feat_pair_dist_h1_scaled wrote for nq queries against their nq * lambda candidate rows
+ * (leading dimension ld >= nq * lambda floats), query i's own candidates in columns i * lambda .. i * lambda + lambda - 1.
+ *     keys_dev[i] = min_j bits(M[i * ld + i * lambda + j]), zero-extended;  j_dev[i] = the smallest j that attains it.
+ * The uint32 patterns are compared as unsigned integers: D32 >= +0 and never NaN, so that is the order of the floats (+inf included), and
+ * the result is the form gl_wb_diag_keys writes (lambda = 1 is the diagonal) and gl_pbb_accept reads.  Going through the search's own pair
+ * kernels is what makes the score the bits attack(distance='l2-lpips') reports for the pair.  1 <= lambda < 2^31, nq < 2^31; keys_dev [nq]
+ * uint64 (8-byte aligned), j_dev [nq] int32.  One wave per query, lanes striding over j, a 64-bit minimum of (pattern << 32) | j across
+ * the wave; no atomics, no workspace. */
+int gl_pbb_group_min_keys(gl_ctx *ctx, const float *M_dev, int64_t nq, int64_t lambda, int64_t ld, uint64_t *keys_dev, int32_t *j_dev);
 /* The elitist (1 + lambda) step.  Where S_new[q] < S_cur[q], strictly: z[q] = cand_z[q * lambda + j_new[q]], S_cur[q] = S_new[q],
  * sigma[q] = fl32(sigma[q] * up), accepted[q] = 1; otherwise sigma[q] = fl32(sigma[q] * down), accepted[q] = 0 and z, S_cur stay.  Then
  * sigma[q] is clamped to [sigma_min, sigma_max].  z_dev [nq][nz], sigma_dev [nq], cand_z_dev [nq * lambda][nz] fp32; S_cur_dev, S_new_dev

@@ -348,60 +348,312 @@ def set_topk_workspace(ctx, nbytes):
     check(ctx.lib.gl_topk_set_workspace(ctx.handle, int(nbytes)))
 
 
-def _attack_topk(queries, bank, k, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
-    """attack(..., k=k): the bank passes through HBM in chunks like _attack_streamed's (one chunk when it fits), every chunk folds its keys
-    into the same [Q, k] lists."""
-    k = _check_k(k)
-    unsupported = "top-k is built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
-    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
-        raise NotImplementedError(unsupported + "got LPIPS feature rows")
-    prepared = isinstance(bank, Bank)
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx = bank.ctx
-        base = bank.index_base
-    else:
-        ctx = ctx or Context.get()
-        base = int(index_base)
-    shard = reduce_fn is not None or base != 0
+def _new_keys(ctx, nq):
+    """empty packed keys DeviceArray [max(nq, 1)] uint64 (gl_keys_init)"""
+    keys = ctx.empty((max(nq, 1),), np.uint64)
+    check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), nq))
+    return keys
+
+
+def _new_topk(ctx, nq, k):
+    """empty key lists DeviceArray [max(nq, 1), k] uint64 (gl_topk_init)"""
+    keys = ctx.empty((max(nq, 1), k), np.uint64)
+    check(ctx.lib.gl_topk_init(ctx.handle, _p(keys.ptr), nq, k))
+    return keys
+
+
+# ---- the bank walkers: one per row family (DESIGN.md section 5).  Every reduction over the pairs of a query set and a bank is a launch
+# function handed to a walker's run_pass; the walkers know the bank forms, the chunks, the query slices and the row layout, and nothing of
+# what is reduced.
+
+def _rows_in_play(bank, batch_size, ctx, reduce_fn, index_base):
+    """(ctx, index_base, n_rows) of a bank by attack()'s rule: n_rows = (N // batch_size) * batch_size unless the bank is a shard
+    (index_base != 0 or reduce_fn given); no full batch raises ValueError.  A Bank, a FeatureBank and a GeneratedBank carry their own
+    context and index_base; for any other bank `ctx` comes back as it was given (None: the caller takes the default).  Needs no GPU."""
+    if hasattr(bank, "index_base"):
+        ctx, index_base = bank.ctx, bank.index_base
+    index_base = int(index_base)
+    shard = reduce_fn is not None or index_base != 0
     n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
     if n_rows == 0 and reduce_fn is None:
         raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-    if not shard and k > n_rows:
+    return ctx, index_base, n_rows
+
+
+def _check_k_rows(k, bank, batch_size, reduce_fn, index_base):
+    """k nearest samples need k rows that take part, unless the bank is a shard; before any row is prepared"""
+    _, index_base, n_rows = _rows_in_play(bank, batch_size, None, reduce_fn, index_base)
+    if reduce_fn is None and index_base == 0 and k > n_rows:
         raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_rows))
+
+
+def _bank_rows(bank, lo, hi):
+    """rows [lo, hi) of a bank that is a GeneratedBank, a DeviceArray or a host array"""
+    if getattr(bank, "kind", None) == "generated":
+        return bank.rows(lo, hi)
+    if isinstance(bank, DeviceArray):
+        return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
+    return bank[lo:hi]
+
+
+def _slice_rows(arr, a, b):
+    """rows [a, b) of a DeviceArray whose first axis runs over the queries"""
+    rest = tuple(arr.shape[1:])
+    row_bytes = arr.dtype.itemsize * int(np.prod(rest, dtype=np.int64))
+    return arr.view((b - a,) + rest, offset_bytes=a * row_bytes)
+
+
+def _run_pass_on(ctx, nq, n_rows, walk):
+    """the run_pass every walker returns.  run_pass(new_out, per_query, launch, reduce, out_per_query=True) -> DeviceArray is one pass over
+    the bank: new_out() makes the fresh, initialised output of the pass; per_query is a list of host arrays [Q, ...] that are uploaded once
+    for all slices and chunks; launch(bank rows, query rows, per_query DeviceArrays, n_rows or None, out) adds one chunk to `out`; reduce
+    (or None) is the cross-shard reduction, called once per pass with the whole output -- also by a shard without rows, whose output is
+    untouched.  out_per_query=False: the output has no query axis (a histogram) and is handed whole to every query slice.
+    walk(out, new_out, dev, launch, out_per_query) -> out makes the launches; it returns another output only after a layout restart."""
+    def run_pass(new_out, per_query, launch, reduce, out_per_query=True):
+        out = new_out()
+        if nq and n_rows:
+            dev = [ctx.to_device(np.ascontiguousarray(a)) for a in per_query]
+            out = walk(out, new_out, dev, launch, out_per_query)
+            ctx.sync()                                       # the uploads are released on return
+        if reduce is not None:
+            out = reduce(out)
+        return out
+    return run_pass
+
+
+def _lattice_rows_walker(what, queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base, hint=""):
+    """one pass over the exact-integer rows of a bank (int8 rows on the 8-bit or the integer lattice), whatever is reduced from the pairs.
+    The bank -- images, a prepared `Bank`, a `GeneratedBank` -- passes through HBM in chunks of at most `chunk_bytes` (u8 codes + int8
+    rows), each prepared on the queries' lattice and with their norm width; an unprepared bank is prepared again on every pass.  `what`
+    opens the refusals ("top-k is") and `hint` closes those of rows off both lattices: LPIPS feature rows raise NotImplementedError, rows off the queries' lattice _OffLattice -- the
+    prepared ones before any launch, a chunk when the stream reaches it.  Returns (ctx, the prepared query Bank, n_rows, run_pass)."""
+    unsupported = what + " built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError(unsupported + "got LPIPS feature rows")
+    prepared = isinstance(bank, Bank)
+    ctx, base, n_rows = _rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
+    ctx = ctx or Context.get()
+    if prepared and bank.kind == "f32":
+        raise _OffLattice(unsupported + "the bank is off both lattices" + hint)
     fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
     if fq.kind == "f32":
-        raise _OffLattice(unsupported + "the queries are off both lattices")
-    keys = None
-    if prepared:
-        keys, _, _ = topk_keys(bank, fq, k, n_rows)
-    else:
+        raise _OffLattice(unsupported + "the queries are off both lattices" + hint)
+    if prepared and bank.kind != fq.kind:
+        raise _OffLattice(unsupported + "got %r queries, %r bank" % (fq.kind, bank.kind))
+    if not prepared:
         chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
         step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
 
-        def rows(lo, hi):
-            if generated:
-                return bank.rows(lo, hi)
-            if isinstance(bank, DeviceArray):
-                return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
-            return bank[lo:hi]
-
+    def walk(out, new_out, dev, launch, out_per_query):
+        if prepared:
+            launch(bank, fq, dev, n_rows, out)
+            return out
         for lo in range(0, n_rows, step):
-            hi = min(lo + step, n_rows)
-            chunk = rows(lo, hi)
+            chunk = _bank_rows(bank, lo, min(lo + step, n_rows))
             if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
                 raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
             try:
                 b = Bank.from_images(chunk, ctx, index_base=base + lo, force_kind=fq.kind, norms64=fq.wide)
             except ValueError as e:
                 raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
-            keys, _, _ = topk_keys(b, fq, k, keys=keys)
+            launch(b, fq, dev, None, out)
             ctx.sync()
-    if keys is None:                         # a shard without rows still takes part in the reduction
-        keys = ctx.empty((max(fq.n, 1), k), np.uint64)
-        check(ctx.lib.gl_topk_init(ctx.handle, _p(keys.ptr), fq.n, k))
-    if reduce_fn is not None:
-        keys = reduce_fn(keys)
+        return out
+
+    return ctx, fq, n_rows, _run_pass_on(ctx, fq.n, n_rows, walk)
+
+
+def _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """one pass over the fp32 rows of a bank, whatever is reduced from the pairs: 8-bit codes and integer tables decoded, floats as they
+    are, in chunks of at most `chunk_bytes` of fp32 rows.  A bank of one chunk is uploaded once, a longer one once per pass.  Returns
+    (ctx, nq, n_rows, run_pass)."""
+    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
+        raise NotImplementedError("distance='l2' takes images or tables; got LPIPS feature rows")
+    ctx, base, n_rows = _rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
+    ctx = ctx or Context.get()
+    fq = queries.as_f32() if isinstance(queries, Bank) else Bank.from_images(queries, ctx, force_kind="f32")
+    resident = None
+    if isinstance(bank, Bank):
+        resident = bank.as_f32()
+    else:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        step = max(1, int(chunk_bytes // (4 * fq.d)))
+        if 0 < n_rows <= step:
+            resident = Bank.from_images(_bank_rows(bank, 0, n_rows), ctx, index_base=base, force_kind="f32")
+
+    def walk(out, new_out, dev, launch, out_per_query):
+        if resident is not None:
+            launch(resident, fq, dev, n_rows, out)
+            return out
+        for lo in range(0, n_rows, step):
+            b = Bank.from_images(_bank_rows(bank, lo, min(lo + step, n_rows)), ctx, index_base=base + lo, force_kind="f32")
+            launch(b, fq, dev, None, out)
+            ctx.sync()
+        return out
+
+    return ctx, fq.n, n_rows, _run_pass_on(ctx, fq.n, n_rows, walk)
+
+
+def _lpips_stream_walk(slices, bounds, query_rows, chunk_rows, restartable, fmt, sync):
+    """the walk of a streamed 'l2-lpips' pass (_run_pass_on), free of any Context: every query slice against the whole bank stream.
+    slices: [(a, b)] over the queries; bounds(fq) -> [(r0, r1)], the bank chunks for these query rows; query_rows(a, b, fmt) -> the
+    slice's rows in layout fmt (None: as the images give it); chunk_rows(r0, r1, fq, buf) -> the chunk's rows in fq's layout, written
+    into `buf` (None on the first chunk: ONE buffer serves all chunks of a slice); sync() follows every launch.
+    One row layout per call: 8-bit codes give lattice rows until a query slice or a bank chunk turns out to be off-lattice floats
+    (ValueError from either callable).  Then -- if `restartable`: the queries are images that can be featurised again -- the pass starts
+    over in the hi / lo layout with a second fresh output, and every later pass starts there.  Nothing of an abandoned layout survives
+    in an output, and every (query, bank row) pair is seen exactly once.  A single slice is featurised once per layout, not per pass."""
+    state = {"fmt": fmt, "fq": None}
+
+    def rows_of(a, b):
+        if len(slices) == 1 and state["fq"] is not None and getattr(state["fq"], "fmt", None) == state["fmt"]:
+            return state["fq"]
+        fq = query_rows(a, b, state["fmt"])
+        if len(slices) == 1:
+            state["fq"] = fq
+        return fq
+
+    def stream(out, dev, launch, out_per_query):
+        """False: an off-lattice slice or chunk met lattice rows"""
+        for a, b in slices:
+            if b == a:
+                continue
+            try:
+                fq = rows_of(a, b)
+            except ValueError:
+                if not restartable or state["fmt"] != "lattice":
+                    raise
+                return False
+            if restartable and state["fmt"] is None:
+                state["fmt"] = getattr(fq, "fmt", None)      # the first slice settles it: 'lattice' for 8-bit codes, else 'hilo'
+            dev_s = [_slice_rows(x, a, b) for x in dev]
+            out_s = _slice_rows(out, a, b) if out_per_query else out
+            buf = None
+            for r0, r1 in bounds(fq):
+                try:
+                    buf = chunk_rows(r0, r1, fq, buf)
+                except ValueError:
+                    if not restartable or getattr(fq, "fmt", None) != "lattice":
+                        raise
+                    return False
+                launch(buf, fq, dev_s, None, out_s)
+                sync()
+        return True
+
+    def walk(out, new_out, dev, launch, out_per_query):
+        if not stream(out, dev, launch, out_per_query):
+            state["fmt"], state["fq"] = "hilo", None
+            out = new_out()                                  # the output of the abandoned layout is dropped
+            if not stream(out, dev, launch, out_per_query):
+                raise AssertionError("unreachable")
+        return out
+
+    return walk
+
+
+def _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
+    """one pass over the 'l2-lpips' rows of a bank, whatever is reduced from the pairs: attack()'s resident / streamed decision and row
+    preparation; a streamed bank is featurised chunk by chunk into one buffer, and query rows beyond the query budget go in slices
+    (_lpips_stream_walk).  layout: None, or 'hilo' to put fp16 search rows of both sides in the hi / lo layout from the start
+    (DeviceGroup).  Returns (ctx, nq, n_rows, run_pass); the launch sees FeatureBanks, and of the per-query arrays and of a per-query
+    output the rows of its query slice."""
+    from . import lpips as _lp
+    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
+    q_feat = getattr(queries, "kind", None) == "feat"
+    if model is None and not (prepared and q_feat):        # prepared rows on both sides need no VGG16
+        model = _lp.default_model()
+    streamed = False
+    if not prepared:
+        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
+        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
+            streamed = True
+        else:
+            per_img = _feature_row_bytes(ctx, model, bank)
+            streamed = per_img * n_rows > chunk_bytes or (not q_feat and len(queries) * per_img > chunk_bytes)
+
+    if not streamed:
+        if not prepared:
+            bank = _bank_rows(bank, 0, n_rows)
+        if layout == "hilo" and model is not None and model.search_role("bank"):
+            fb = bank if prepared else model.features(bank, index_base=index_base, role="bank", fmt="hilo")
+            fq = queries if q_feat else model.features(queries, role="query", fmt="hilo")
+        else:
+            fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
+
+        def walk(out, new_out, dev, launch, out_per_query):
+            launch(fb, fq, dev, n_rows, out)
+            return out
+
+        return ctx, fq.n, n_rows, _run_pass_on(ctx, fq.n, n_rows, walk)
+
+    role_q = None if q_feat else model.search_role("query")
+    nq = queries.n if q_feat else len(queries)
+    if q_feat or nq == 0:
+        slices = [(0, nq)]
+    else:
+        q_step = max(1, int(_query_budget_bytes(chunk_bytes, ctx) // _feature_row_bytes(ctx, model, queries)))
+        slices = [(a, min(a + q_step, nq)) for a in range(0, nq, q_step)]
+
+    def bounds(fq):
+        step = max(1, int(chunk_bytes // (fq.K * (2 if fq.role else 4))))
+        if fq.role:
+            step = _lp.preferred_bank_rows(step, fq.n)
+        return [(r0, min(r0 + step, n_rows)) for r0 in range(0, n_rows, step)]
+
+    def query_rows(a, b, fmt):
+        return queries if q_feat else model.features(queries[a:b], role=role_q, fmt=fmt if role_q else None)
+
+    def chunk_rows(r0, r1, fq, buf):
+        return model.features(_bank_rows(bank, r0, r1), index_base=index_base + r0, role="bank" if getattr(fq, "role", None) else None, out=buf,
+                              fmt=getattr(fq, "fmt", None))
+
+    walk = _lpips_stream_walk(slices, bounds, query_rows, chunk_rows, not q_feat, "hilo" if (layout == "hilo" and role_q) else None, ctx.sync)
+    return ctx, nq, n_rows, _run_pass_on(ctx, nq, n_rows, walk)
+
+
+def _topk_lists(ctx, nq, k, topk, run_pass, reduce_fn):
+    """the [Q, k] key lists of one pass: topk(bank rows, query rows, k, n_rows or None, keys) folds a chunk in"""
+    return run_pass(lambda: _new_topk(ctx, nq, k), [], lambda b, fq, dev, n, out: topk(b, fq, k, n, out), reduce_fn)
+
+
+def _shared_radii_counts(ctx, nq, thr, count, run_pass, reduce_fn):
+    """ball_counts' pass: count(bank rows, query rows, ascending thresholds, n_rows or None, counts) adds a chunk.  The library sees the
+    thresholds sorted; the columns are put back in the caller's order at the end.  int64 [Q, T]."""
+    order = np.argsort(thr, kind="stable")
+    srt = np.ascontiguousarray(thr[order])
+    counts = run_pass(lambda: new_counts(ctx, nq, len(thr)), [], lambda b, fq, dev, n, out: count(b, fq, srt, n, out), reduce_fn)
+    out = np.empty((nq, len(thr)), np.int64)
+    out[:, order] = counts.numpy()[:nq].astype(np.int64)
+    return out
+
+
+def _counter_of(ctx, nq, reduce_fn, launch, run_pass):
+    """count_pass(thr int64 [Q, T], rows ascending) -> int64 [Q, T] on a walker's run_pass, summed over the chunks and -- through
+    reduce_fn -- the shards"""
+    def count_pass(thr):
+        thr = np.ascontiguousarray(thr, np.int64)
+        counts = run_pass(lambda: new_counts(ctx, nq, thr.shape[1]), [thr], launch, reduce_fn)
+        return counts.numpy()[:nq].astype(np.int64)
+    return count_pass
+
+
+def _hist_passes(ctx, hist, run_pass, reduce_fn):
+    """one_pass(lo, shift, n_bins) -> int64 [n_bins] on a walker's run_pass, summed over chunks, query slices and -- through reduce_fn --
+    the shards: hist(bank rows, query rows, lo, shift, n_bins, n_rows or None, bins) adds a chunk"""
+    def one_pass(lo, shift, n_bins):
+        bins = run_pass(lambda: new_hist(ctx, n_bins), [], lambda b, fq, dev, n, out: hist(b, fq, lo, shift, n_bins, n, out), reduce_fn,
+                        out_per_query=False)
+        return bins.numpy().reshape(-1)[:n_bins].astype(np.int64)
+    return one_pass
+
+
+def _attack_topk(queries, bank, k, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
+    """attack(..., k=k): every chunk folds its keys into the same [Q, k] lists"""
+    k = _check_k(k)
+    _check_k_rows(k, bank, batch_size, reduce_fn, index_base)
+    ctx, fq, _, run_pass = _lattice_rows_walker("top-k is", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    keys = _topk_lists(ctx, fq.n, k, lambda *a: topk_keys(*a), run_pass, reduce_fn)
     return unpack_topk(ctx, keys, fq.n, k, fq.d, fq.kind)
 
 
@@ -543,73 +795,18 @@ def ball_counts(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chu
     e32 = _check_eps(eps)                    # before any Context: these checks run without a GPU
     float_path = _check_rows_float_path(float_path)
     if distance == "l2-lpips":
-        return _ball_counts_lpips(queries, bank, e32, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base)
-    if float_path is None:
-        return _ball_counts_l2(queries, bank, e32, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
-    if _layout != "f32":
+        from . import lpips as _lp
+        ctx, nq, _, run_pass = _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, None)
+        return _shared_radii_counts(ctx, nq, e32, lambda *a: _lp.feat_count(*a), run_pass, reduce_fn)
+    if _layout != "f32" or float_path is None:
         try:
-            return _ball_counts_l2(queries, bank, e32, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+            ctx_l, fq, _, run_pass = _lattice_rows_walker("ball counts are", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+            return _shared_radii_counts(ctx_l, fq.n, eps_to_ssd(e32, fq.d, fq.kind), lambda *a: count_balls(*a), run_pass, reduce_fn)
         except _OffLattice:
-            pass                             # nothing of the integer pass survives: the fp32 rows start over
-    return _float_rows(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base, eps=e32)
-
-
-def _ball_counts_l2(queries, bank, e32, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
-    """ball_counts(distance='l2') on the exact-integer path"""
-    unsupported = "ball counts are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
-    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
-        raise NotImplementedError(unsupported + "got LPIPS feature rows")
-    prepared = isinstance(bank, Bank)
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx = bank.ctx
-        base = bank.index_base
-    else:
-        ctx = ctx or Context.get()
-        base = int(index_base)
-    shard = reduce_fn is not None or base != 0
-    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
-    if n_rows == 0 and reduce_fn is None:
-        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-    if prepared and bank.kind == "f32":
-        raise _OffLattice(unsupported + "the bank is off both lattices")
-    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
-    if fq.kind == "f32":
-        raise _OffLattice(unsupported + "the queries are off both lattices")
-    # the library sees the thresholds sorted; the columns are put back in the caller's order at the end
-    thr = eps_to_ssd(e32, fq.d, fq.kind)
-    order = np.argsort(thr, kind="stable")
-    counts = new_counts(ctx, fq.n, len(thr))              # fresh counters per call
-    if prepared:
-        count_balls(bank, fq, thr[order], n_rows, counts)
-    else:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
-
-        def rows(lo, hi):
-            if generated:
-                return bank.rows(lo, hi)
-            if isinstance(bank, DeviceArray):
-                return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
-            return bank[lo:hi]
-
-        for lo in range(0, n_rows, step):
-            hi = min(lo + step, n_rows)
-            chunk = rows(lo, hi)
-            if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
-                raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
-            try:
-                b = Bank.from_images(chunk, ctx, index_base=base + lo, force_kind=fq.kind, norms64=fq.wide)
-            except ValueError as e:
-                raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
-            count_balls(b, fq, thr[order], counts=counts)
-            ctx.sync()
-    if reduce_fn is not None:                # (a shard without rows takes part with zeros)
-        counts = reduce_fn(counts)
-    host = counts.numpy()[:fq.n]
-    out = np.empty((fq.n, len(thr)), np.int64)
-    out[:, order] = host.astype(np.int64)
-    return out
+            if float_path is None:
+                raise                        # nothing of the integer pass survives: the fp32 rows start over
+    ctx, nq, _, run_pass = _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    return _shared_radii_counts(ctx, nq, e32, lambda *a: count_balls_f32(*a), run_pass, reduce_fn)
 
 
 def _check_eps_rows(eps, nq=None):
@@ -779,66 +976,16 @@ def count_balls_rows(bank, queries, thr, n_rows=None, counts=None):
     return counts, queries, bank.kind
 
 
+def _count_launch_l2(b, fq, per_query, n, out):
+    count_balls_rows(b, fq, per_query[0], n, out)
+
+
 def _rows_counter(what, queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
-    """what ball_counts_rows and kth_distances share: the bank forms and refusals of _ball_counts_l2, and one pass over the bank per call of
-    the returned function.  Returns (fq: the prepared query Bank, n_rows: the local rows that take part, count_pass), with
-    count_pass(thr int64 [Q, T], rows ascending) -> int64 [Q, T], summed over the chunks and -- through reduce_fn -- the shards."""
-    unsupported = what + " are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
-    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
-        raise NotImplementedError(unsupported + "got LPIPS feature rows")
-    prepared = isinstance(bank, Bank)
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx = bank.ctx
-        base = bank.index_base
-    else:
-        ctx = ctx or Context.get()
-        base = int(index_base)
-    shard = reduce_fn is not None or base != 0
-    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
-    if n_rows == 0 and reduce_fn is None:
-        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-    if prepared and bank.kind == "f32":
-        raise _OffLattice(unsupported + "the bank is off both lattices (per-query radii on the float paths are not built)")
-    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
-    if fq.kind == "f32":
-        raise _OffLattice(unsupported + "the queries are off both lattices (per-query radii on the float paths are not built)")
-    if not prepared:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
-
-    def rows(lo, hi):
-        if generated:
-            return bank.rows(lo, hi)
-        if isinstance(bank, DeviceArray):
-            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
-        return bank[lo:hi]
-
-    def count_pass(thr):
-        thr = np.ascontiguousarray(thr, np.int64)
-        counts = new_counts(ctx, fq.n, thr.shape[1])         # fresh counters per pass
-        if fq.n and n_rows:
-            thr_dev = ctx.to_device(thr)
-            if prepared:
-                count_balls_rows(bank, fq, thr_dev, n_rows, counts)
-            else:
-                for r0 in range(0, n_rows, step):
-                    r1 = min(r0 + step, n_rows)
-                    chunk = rows(r0, r1)
-                    if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
-                        raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
-                    try:
-                        b = Bank.from_images(chunk, ctx, index_base=base + r0, force_kind=fq.kind, norms64=fq.wide)
-                    except ValueError as e:
-                        raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
-                    count_balls_rows(b, fq, thr_dev, counts=counts)
-                    ctx.sync()
-            ctx.sync()                                       # thr_dev is released on return
-        if reduce_fn is not None:            # (a shard without rows takes part with zeros)
-            counts = reduce_fn(counts)
-        return counts.numpy()[:fq.n].astype(np.int64)
-
-    return fq, n_rows, count_pass
+    """what ball_counts_rows and kth_distances share: (fq: the prepared query Bank, n_rows: the local rows that take part, count_pass) on
+    _lattice_rows_walker, one count_balls_rows pass over the bank per call of count_pass"""
+    ctx, fq, n_rows, run_pass = _lattice_rows_walker(what, queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base,
+                                                     hint=" (per-query radii on the float paths are not built)")
+    return fq, n_rows, _counter_of(ctx, fq.n, reduce_fn, _count_launch_l2, run_pass)
 
 
 def ball_counts_rows(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None, chunk_bytes=None, index_base=0, distance="l2"):
@@ -859,7 +1006,7 @@ def ball_counts_rows(queries, bank, eps, batch_size=64, ctx=None, reduce_fn=None
     if distance == "l2-lpips":
         raise NotImplementedError("per-query radii are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
                                   "distance='l2-lpips' is not (its thresholds are floats; ball_counts takes radii shared by all queries)")
-    fq, _, count_pass = _rows_counter("per-query ball counts", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    fq, _, count_pass = _rows_counter("per-query ball counts are", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
     if e32.shape[0] != fq.n:
         raise ValueError("eps has %d rows for %d queries" % (e32.shape[0], fq.n))
     # the library sees every row sorted; the columns are put back in the caller's order at the end
@@ -908,7 +1055,7 @@ def kth_distances(queries, bank, k, batch_size=64, ctx=None, reduce_fn=None, chu
     if distance == "l2-lpips":
         raise NotImplementedError("k-th neighbour distances are built for the exact-integer L2 search (8-bit images or integer tables on both "
                                   "sides); distance='l2-lpips' is not (nearest_neighbours gives its 32 nearest)")
-    fq, n_rows, count_pass = _rows_counter("k-th neighbour distances", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    fq, n_rows, count_pass = _rows_counter("k-th neighbour distances are", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
     if reduce_fn is None and max(ks) > n_rows:
         raise ValueError("k=%d exceeds the %d bank rows that take part" % (max(ks), n_rows))
     s_max = 65025 * fq.d
@@ -1043,9 +1190,7 @@ def kde_scores(queries, bank, bandwidths, batch_size=64, ctx=None, reduce_fn=Non
     if distance == "l2-lpips":
         raise NotImplementedError("kernel-density scores are built for the exact-integer L2 search (8-bit images or integer tables on both "
                                   "sides); distance='l2-lpips' is not (its distances are rounded floats, the fixed-point sum needs an exact S)")
-    unsupported = "kernel-density scores are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
-    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
-        raise NotImplementedError(unsupported + "got LPIPS feature rows")
+    what = "kernel-density scores are"
     for name, rows in (("queries", queries), ("bank", bank)):
         if isinstance(rows, Bank):
             off = rows.kind == "f32"
@@ -1054,52 +1199,17 @@ def kde_scores(queries, bank, bandwidths, batch_size=64, ctx=None, reduce_fn=Non
         else:
             off = False
         if off:
-            raise _OffLattice(unsupported + "the %s are off both lattices" % name)
+            raise _OffLattice(what + " built for the exact-integer L2 search (8-bit images or integer tables on both sides); the %s are off "
+                              "both lattices" % name)
     reduce_min, reduce_sum = reduce_fn if reduce_fn is not None else (None, None)
-    prepared = isinstance(bank, Bank)
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx = bank.ctx
-        base = bank.index_base
-    else:
-        base = int(index_base)
-    shard = reduce_fn is not None or base != 0
-    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
-    if n_rows == 0 and reduce_fn is None:
-        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
+    _, _, n_rows = _rows_in_play(bank, batch_size, None, reduce_fn, index_base)
     if n_rows >= KDE_MAX_ROWS:
         raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d given): 2^23 weights of 2^40 overflow 64 bits" % n_rows)
-    ctx = ctx or (queries.ctx if isinstance(queries, Bank) else Context.get())
-    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
-    if fq.kind == "f32":
-        raise _OffLattice(unsupported + "the queries are off both lattices")
+    ctx, fq, n_rows, run_pass = _lattice_rows_walker(what, queries, bank, batch_size, ctx or (queries.ctx if isinstance(queries, Bank) else None),
+                                                     reduce_fn, chunk_bytes, index_base)
     c32, h_eff = kde_coef(h, fq.d, fq.kind)
     order = np.argsort(-c32, kind="stable")                # the library sees the coefficients descending (bandwidths ascending)
-    if not prepared:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
-
-    def chunks():
-        """the prepared Banks of one pass over the local rows, with the rows of each that take part"""
-        if prepared:
-            if n_rows:
-                yield bank, n_rows
-            return
-        for lo in range(0, n_rows, step):
-            hi = min(lo + step, n_rows)
-            if generated:
-                chunk = bank.rows(lo, hi)
-            elif isinstance(bank, DeviceArray):
-                chunk = bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
-            else:
-                chunk = bank[lo:hi]
-            if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
-                raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
-            try:
-                yield Bank.from_images(chunk, ctx, index_base=base + lo, force_kind=fq.kind, norms64=fq.wide), hi - lo
-            except ValueError as e:
-                raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
-
+    coef = np.ascontiguousarray(c32[order])
     # the rows that take part over all shards
     n_eff = n_rows
     if reduce_sum is not None:
@@ -1108,26 +1218,11 @@ def kde_scores(queries, bank, bandwidths, batch_size=64, ctx=None, reduce_fn=Non
         if n_eff >= KDE_MAX_ROWS:
             raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d over all shards)" % n_eff)
     # pass 1: the exact nearest sample of every query
-    keys = ctx.empty((max(fq.n, 1),), np.uint64)
-    check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), fq.n))
-    for b, n in chunks():
-        if b.kind != fq.kind:
-            raise _OffLattice(unsupported + "got %r queries, %r bank" % (fq.kind, b.kind))
-        knn_keys(b, fq, n, keys=keys)
-        ctx.sync()
-    if reduce_min is not None:               # (a shard without rows takes part with empty keys)
-        keys = reduce_min(keys)
+    keys = run_pass(lambda: _new_keys(ctx, fq.n), [], lambda b, q, dev, n, out: knn_keys(b, q, n, keys=out), reduce_min)
     shift = min(32, 63 - int(65025 * fq.d).bit_length())     # gl_l2_key_shift: keys are S << shift | index
     S0 = (keys.numpy()[:fq.n] >> np.uint64(shift)).astype(np.int64)
-    # pass 2: the weights of all rows relative to it
-    sums = new_counts(ctx, fq.n, len(c32))
-    if fq.n:
-        s0_dev = ctx.to_device(S0)
-        for b, n in chunks():
-            kde_sums(b, fq, s0_dev, c32[order], n, sums)
-        ctx.sync()                           # s0_dev is released on return
-    if reduce_sum is not None:
-        sums = reduce_sum(sums)
+    # pass 2: the weights of all rows relative to it (S0 is uploaded once for all chunks)
+    sums = run_pass(lambda: new_counts(ctx, fq.n, len(coef)), [S0], lambda b, q, dev, n, out: kde_sums(b, q, dev[0], coef, n, out), reduce_sum)
     W = np.empty((fq.n, len(c32)), np.uint64)
     W[:, order] = sums.numpy()[:fq.n]
     return kde_loss(W, S0, h_eff, n_eff, fq.d, fq.kind), W, S0
@@ -1270,61 +1365,13 @@ def distance_quantiles(queries, bank, quantiles, batch_size=64, ctx=None, reduce
               summed first-level histogram.
     Exact-integer L2 only: rows off both lattices, LPIPS feature rows and distance='l2-lpips' raise NotImplementedError."""
     q = _check_quantiles(quantiles)          # before any Context: these checks run without a GPU
-    unsupported = "distance quantiles are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
     if distance not in ("l2", "l2-lpips"):
         raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
     if distance == "l2-lpips":
-        raise NotImplementedError(unsupported + "distance='l2-lpips' is not (its float32 distance bits would radix-select the same way)")
-    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
-        raise NotImplementedError(unsupported + "got LPIPS feature rows")
-    prepared = isinstance(bank, Bank)
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx = bank.ctx
-        base = bank.index_base
-    else:
-        ctx = ctx or Context.get()
-        base = int(index_base)
-    shard = reduce_fn is not None or base != 0
-    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
-    if n_rows == 0 and reduce_fn is None:
-        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-    if prepared and bank.kind == "f32":
-        raise _OffLattice(unsupported + "the bank is off both lattices")
-    fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64=bank.wide if prepared else "auto")
-    if fq.kind == "f32":
-        raise _OffLattice(unsupported + "the queries are off both lattices")
-    if not prepared:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
-
-    def rows(lo, hi):
-        if generated:
-            return bank.rows(lo, hi)
-        if isinstance(bank, DeviceArray):
-            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
-        return bank[lo:hi]
-
-    def one_pass(lo, shift, n_bins):
-        hist = new_hist(ctx, n_bins)                         # fresh bins per pass
-        if prepared:
-            pair_histogram(bank, fq, lo, shift, n_bins, n_rows, hist)
-        else:
-            for r0 in range(0, n_rows, step):
-                r1 = min(r0 + step, n_rows)
-                chunk = rows(r0, r1)
-                if fq.kind == "int" and getattr(chunk, "dtype", None) == np.uint8:
-                    raise _OffLattice(unsupported + "the queries are an integer table, the bank 8-bit image codes")
-                try:
-                    b = Bank.from_images(chunk, ctx, index_base=base + r0, force_kind=fq.kind, norms64=fq.wide)
-                except ValueError as e:
-                    raise _OffLattice(unsupported + "the bank is not on the queries' lattice (%s)" % (e,)) from None
-                pair_histogram(b, fq, lo, shift, n_bins, hist=hist)
-                ctx.sync()
-        if reduce_fn is not None:            # (a shard without rows takes part with zeros)
-            hist = reduce_fn(hist)
-        return hist.numpy().reshape(-1)[:n_bins].astype(np.int64)
-
+        raise NotImplementedError("distance quantiles are built for the exact-integer L2 search (8-bit images or integer tables on both sides); "
+                                  "distance='l2-lpips' is not (its float32 distance bits would radix-select the same way)")
+    ctx, fq, _, run_pass = _lattice_rows_walker("distance quantiles are", queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    one_pass = _hist_passes(ctx, lambda *a: pair_histogram(*a), run_pass, reduce_fn)
     pairs = []
 
     def ranks(total):
@@ -1416,71 +1463,6 @@ def pair_histogram_f32(bank, queries, lo, shift, n_bins, n_rows=None, hist=None)
     return hist
 
 
-def _float_rows(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base, k=None, eps=None):
-    """nearest_neighbours / ball_counts (distance='l2', float_path='exact') with every row in fp32: 8-bit codes and integer tables decoded,
-    floats as they are.  The bank passes through HBM in chunks of at most `chunk_bytes` of fp32 rows (one chunk when it fits), every chunk
-    folds into the same [Q, k] lists (k given) or adds to the same [Q, T] counters (eps: float32 radii in the caller's order)."""
-    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
-        raise NotImplementedError("distance='l2' takes images or tables; got LPIPS feature rows")
-    prepared = isinstance(bank, Bank)
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx = bank.ctx
-        base = bank.index_base
-    else:
-        ctx = ctx or Context.get()
-        base = int(index_base)
-    shard = reduce_fn is not None or base != 0
-    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
-    if n_rows == 0 and reduce_fn is None:
-        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-    if k is not None and not shard and k > n_rows:
-        raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_rows))
-    fq = queries.as_f32() if isinstance(queries, Bank) else Bank.from_images(queries, ctx, force_kind="f32")
-    if eps is not None:
-        # the library sees the radii sorted; the columns are put back in the caller's order at the end
-        order = np.argsort(eps, kind="stable")
-        thr = np.ascontiguousarray(eps[order])
-    acc = None                               # the key lists or the counters
-
-    def fold(b, n):
-        return topk_keys_f32(b, fq, k, n, acc) if k is not None else count_balls_f32(b, fq, thr, n, acc)
-
-    if prepared:
-        acc = fold(bank.as_f32(), n_rows)
-    else:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        step = max(1, int(chunk_bytes // (4 * fq.d)))
-
-        def rows(lo, hi):
-            if generated:
-                return bank.rows(lo, hi)
-            if isinstance(bank, DeviceArray):
-                return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
-            return bank[lo:hi]
-
-        for lo in range(0, n_rows, step):
-            hi = min(lo + step, n_rows)
-            b = Bank.from_images(rows(lo, hi), ctx, index_base=base + lo, force_kind="f32")
-            acc = fold(b, b.n)
-            ctx.sync()
-    if k is not None:
-        if acc is None:                      # a shard without rows still takes part in the reduction
-            acc = ctx.empty((max(fq.n, 1), k), np.uint64)
-            check(ctx.lib.gl_topk_init(ctx.handle, _p(acc.ptr), fq.n, k))
-        if reduce_fn is not None:
-            acc = reduce_fn(acc)
-        return unpack_topk_f32(ctx, acc, fq.n, k)
-    if acc is None:
-        acc = new_counts(ctx, fq.n, len(thr))
-    if reduce_fn is not None:
-        acc = reduce_fn(acc)
-    host = acc.numpy()[:fq.n]
-    out = np.empty((fq.n, len(thr)), np.int64)
-    out[:, order] = host.astype(np.int64)
-    return out
-
-
 def _feature_row_bytes(ctx, model, images):
     h, w = int(images.shape[2]), int(images.shape[3])
     if model.search_rows == "fp16":
@@ -1510,15 +1492,12 @@ def _lpips_resident_rows(queries, bank, prepared, model, index_base):
     return fb, fq
 
 
-def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath=None, index_base=0, count_thr=None, topk=None):
+def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath=None, index_base=0):
     """bank rows [0, n_rows) pass through HBM in chunks of at most `chunk_bytes` of prepared rows (int8 rows for 'l2', feature
     rows for 'l2-lpips'); the packed keys accumulate the minimum across chunks (atomicMin), so the result is the one the
     resident form gives.  `bank` is a GeneratedBank or a host array / DeviceArray of images (`index_base`: global index of its row 0).
-    count_thr ('l2-lpips' only; ascending float32 thresholds): the same stream with lpips.feat_count in place of the search -- the [Q, T]
-    counters accumulate across chunks, reduce_fn is the cross-shard sum, and the result is the host array of counts, uint64 [Q, T].
-    topk ('l2-lpips' only; 1..32): the same stream with lpips.feat_topk_keys -- the [Q, topk] key lists fold chunk after chunk, reduce_fn is
-    the cross-shard merge, the result (dist [Q, topk], idx [Q, topk]).  Lists, unlike a minimum or a count, must see every row once: when an
-    off-lattice chunk makes the stream start over in the hi / lo layout, the lists start over from gl_topk_init with it."""
+    Only the minimum search runs here: a minimum may see a row twice, so a stream that starts over in another layout keeps nothing wrong.
+    Everything else that is reduced from the pairs runs on the walkers (_pair_rows_walker_lpips)."""
     generated = getattr(bank, "kind", None) == "generated"
     base = bank.index_base if generated else int(index_base)
 
@@ -1528,18 +1507,6 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
         return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1))) if isinstance(bank, DeviceArray) else bank[lo:hi]
 
     def finish(keys, nq, d, kind):
-        if count_thr is not None:
-            counts = new_counts(ctx, nq, len(count_thr)) if keys is None else keys
-            if reduce_fn is not None:
-                counts = reduce_fn(counts)
-            return counts.numpy()[:nq]
-        if topk is not None:
-            if keys is None:
-                keys = ctx.empty((max(nq, 1), topk), np.uint64)
-                check(ctx.lib.gl_topk_init(ctx.handle, _p(keys.ptr), nq, topk))
-            if reduce_fn is not None:
-                keys = reduce_fn(keys)
-            return unpack_topk_f32(ctx, keys, nq, topk)
         if keys is None:                 # a shard without rows still takes part in the reduction
             keys = ctx.empty((max(nq, 1),), np.uint64)
             check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), nq))
@@ -1555,10 +1522,8 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
             per_q = _feature_row_bytes(ctx, model, queries)
             q_step = max(1, int(_query_budget_bytes(chunk_bytes, ctx) // per_q))
             if len(queries) > q_step:
-                parts = [_attack_streamed(queries[a:a + q_step], bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath, index_base, count_thr, topk)
+                parts = [_attack_streamed(queries[a:a + q_step], bank, n_rows, distance, ctx, reduce_fn, model, chunk_bytes, fpath, index_base)
                          for a in range(0, len(queries), q_step)]
-                if count_thr is not None:
-                    return np.concatenate(parts)
                 return np.concatenate([p[0] for p in parts]), np.concatenate([p[1] for p in parts])
         raw_queries = getattr(queries, "kind", None) != "feat"
         fq = model.features(queries, role=model.search_role("query")) if raw_queries else queries
@@ -1569,7 +1534,7 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
             step = max(1, int(chunk_bytes // (fq.K * (2 if fq.role else 4))))
             if fq.role:
                 step = _lp.preferred_bank_rows(step, fq.n)
-            keys, buf, ok = None, None, True         # (key lists of an abandoned layout are dropped here: nothing of them survives)
+            keys, buf, ok = None, None, True
             for lo in range(0, n_rows, step):
                 hi = min(lo + step, n_rows)
                 try:
@@ -1579,10 +1544,7 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
                         raise
                     ok = False
                     break
-                if topk is not None:
-                    keys = _lp.feat_topk_keys(buf, fq, topk, keys=keys)
-                else:
-                    keys = _lp.feat_knn_keys(buf, fq, keys=keys) if count_thr is None else _lp.feat_count(buf, fq, count_thr, counts=keys)
+                keys = _lp.feat_knn_keys(buf, fq, keys=keys)
                 ctx.sync()
             if ok:
                 return finish(keys, fq.n, fq.K, "f32")
@@ -1636,51 +1598,9 @@ def _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base):
     unless the bank is a shard (index_base != 0 or reduce_fn given)"""
     if isinstance(bank, Bank):
         raise TypeError("this Bank holds int8 rows for distance='l2'; 'l2-lpips' needs images, a FeatureBank or a GeneratedBank")
-    prepared = getattr(bank, "kind", None) == "feat"
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx, index_base = bank.ctx, bank.index_base
-    else:
-        ctx, index_base = ctx or Context.get(), int(index_base)
-    shard = reduce_fn is not None or index_base != 0
-    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
-    if n_rows == 0 and reduce_fn is None:
-        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-    return prepared, generated, ctx, index_base, n_rows
-
-
-def _ball_counts_lpips(queries, bank, e32, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base):
-    """ball_counts(distance='l2-lpips'): attack()'s resident / streamed decision and row preparation, lpips.feat_count for the search"""
-    from . import lpips as _lp
-    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
-    if model is None and not (prepared and getattr(queries, "kind", None) == "feat"):      # prepared rows on both sides need no VGG16
-        model = _lp.default_model()
-    # the library sees the radii sorted; the columns are put back in the caller's order at the end
-    order = np.argsort(e32, kind="stable")
-    thr = np.ascontiguousarray(e32[order])
-    host = None
-    if not prepared:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
-            need = chunk_bytes + 1
-        else:
-            per_img = _feature_row_bytes(ctx, model, bank)
-            need = per_img * n_rows
-            if getattr(queries, "kind", None) != "feat" and len(queries) * per_img > chunk_bytes:
-                need = chunk_bytes + 1       # the query rows alone exceed a chunk: streamed form (queries resident or in slices)
-        if need > chunk_bytes:
-            host = _attack_streamed(queries, bank, n_rows, "l2-lpips", ctx, reduce_fn, model, chunk_bytes, None, index_base, count_thr=thr)
-        else:
-            bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
-    if host is None:
-        fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
-        counts = _lp.feat_count(fb, fq, thr, n_rows)
-        if reduce_fn is not None:
-            counts = reduce_fn(counts)
-        host = counts.numpy()[:fq.n]
-    out = np.empty((len(host), len(thr)), np.int64)
-    out[:, order] = host.astype(np.int64)
-    return out
+    kind = getattr(bank, "kind", None)
+    ctx, index_base, n_rows = _rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
+    return kind == "feat", kind == "generated", ctx or Context.get(), index_base, n_rows
 
 
 def nearest_neighbours(queries, bank, k, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, index_base=0,
@@ -1724,31 +1644,14 @@ def nearest_neighbours(queries, bank, k, distance="l2-lpips", batch_size=64, ctx
             except _OffLattice:
                 if float_path is None:
                     raise
-        return _float_rows(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base, k=k)
+        _check_k_rows(k, bank, batch_size, reduce_fn, index_base)
+        ctx, nq, _, run_pass = _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+        return unpack_topk_f32(ctx, _topk_lists(ctx, nq, k, lambda *a: topk_keys_f32(*a), run_pass, reduce_fn), nq, k)
     from . import lpips as _lp
-    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
-    if reduce_fn is None and index_base == 0 and k > n_rows:
-        raise ValueError("k=%d exceeds the %d bank rows that take part" % (k, n_rows))
-    model = lpips
-    if model is None and not (prepared and getattr(queries, "kind", None) == "feat"):      # prepared rows on both sides need no VGG16
-        model = _lp.default_model()
-    if not prepared:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
-            need = chunk_bytes + 1
-        else:
-            per_img = _feature_row_bytes(ctx, model, bank)
-            need = per_img * n_rows
-            if getattr(queries, "kind", None) != "feat" and len(queries) * per_img > chunk_bytes:
-                need = chunk_bytes + 1       # the query rows alone exceed a chunk: streamed form (queries resident or in slices)
-        if need > chunk_bytes:
-            return _attack_streamed(queries, bank, n_rows, "l2-lpips", ctx, reduce_fn, model, chunk_bytes, None, index_base, topk=k)
-        bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
-    fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
-    keys = _lp.feat_topk_keys(fb, fq, k, n_rows)
-    if reduce_fn is not None:
-        keys = reduce_fn(keys)
-    return unpack_topk_f32(ctx, keys, fq.n, k)
+    _check_k_rows(k, bank, batch_size, reduce_fn, index_base)
+    # (the walker's layout argument stays None: _layout has never reached this distance)
+    ctx, nq, _, run_pass = _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, None)
+    return unpack_topk_f32(ctx, _topk_lists(ctx, nq, k, lambda *a: _lp.feat_topk_keys(*a), run_pass, reduce_fn), nq, k)
 
 
 F32_BITS_MAX = 0x7F800000                    # the pattern of +inf: the largest uint32 pattern of a float32 distance that is not NaN
@@ -1774,159 +1677,6 @@ def _select_float_bits(one_pass, q, ctx, reduce_fn, local_pairs):
 
     key, _ = select_ranks(one_pass, ranks, F32_BITS_MAX)
     return key.astype(np.uint32).view(np.float32), key, pairs[0]
-
-
-def _pair_quantiles_f32(queries, bank, q, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
-    """pair_distance_quantiles(distance='l2', float_path='exact') with every row in fp32: _float_rows' rows, chunks and n_eff, one
-    pair_histogram_f32 pass per level.  A bank of one chunk is uploaded once, a longer one once per pass."""
-    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
-        raise NotImplementedError("distance='l2' takes images or tables; got LPIPS feature rows")
-    prepared = isinstance(bank, Bank)
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx = bank.ctx
-        base = bank.index_base
-    else:
-        ctx = ctx or Context.get()
-        base = int(index_base)
-    shard = reduce_fn is not None or base != 0
-    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
-    if n_rows == 0 and reduce_fn is None:
-        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-    fq = queries.as_f32() if isinstance(queries, Bank) else Bank.from_images(queries, ctx, force_kind="f32")
-    resident = None
-    if prepared:
-        resident = bank.as_f32()
-    else:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        step = max(1, int(chunk_bytes // (4 * fq.d)))
-
-    def rows(lo, hi):
-        if generated:
-            return bank.rows(lo, hi)
-        if isinstance(bank, DeviceArray):
-            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
-        return bank[lo:hi]
-
-    if resident is None and 0 < n_rows <= step:
-        resident = Bank.from_images(rows(0, n_rows), ctx, index_base=base, force_kind="f32")
-
-    def one_pass(lo, shift, n_bins):
-        hist = new_hist(ctx, n_bins)                         # fresh bins per pass
-        if resident is not None:
-            pair_histogram_f32(resident, fq, lo, shift, n_bins, n_rows, hist)
-        else:
-            for r0 in range(0, n_rows, step):
-                b = Bank.from_images(rows(r0, min(r0 + step, n_rows)), ctx, index_base=base + r0, force_kind="f32")
-                pair_histogram_f32(b, fq, lo, shift, n_bins, hist=hist)
-                ctx.sync()
-        if reduce_fn is not None:            # (a shard without rows takes part with zeros)
-            hist = reduce_fn(hist)
-        return hist.numpy().reshape(-1)[:n_bins].astype(np.int64)
-
-    return _select_float_bits(one_pass, q, ctx, reduce_fn, fq.n * n_rows)
-
-
-def _pair_quantiles_lpips(queries, bank, q, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
-    """pair_distance_quantiles(distance='l2-lpips'): ball_counts' resident / streamed decision and row preparation, one lpips.feat_hist pass
-    per level.  layout: None, or 'hilo' to put fp16 search rows of both sides in the hi / lo layout from the start (DeviceGroup)."""
-    from . import lpips as _lp
-    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
-    q_feat = getattr(queries, "kind", None) == "feat"
-    if model is None and not (prepared and q_feat):        # prepared rows on both sides need no VGG16
-        model = _lp.default_model()
-    streamed = False
-    if not prepared:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
-            streamed = True
-        else:
-            per_img = _feature_row_bytes(ctx, model, bank)
-            streamed = per_img * n_rows > chunk_bytes or (not q_feat and len(queries) * per_img > chunk_bytes)
-        if not streamed:
-            bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
-
-    if not streamed:
-        if layout == "hilo" and model is not None and model.search_role("bank"):
-            fb = bank if prepared else model.features(bank, index_base=index_base, role="bank", fmt="hilo")
-            fq = queries if q_feat else model.features(queries, role="query", fmt="hilo")
-        else:
-            fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
-        nq = fq.n
-
-        def one_pass(lo, shift, n_bins):
-            hist = _lp.feat_hist(fb, fq, lo, shift, n_bins, n_rows)
-            if reduce_fn is not None:
-                hist = reduce_fn(hist)
-            return hist.numpy().reshape(-1)[:n_bins].astype(np.int64)
-    else:
-        # The stream of _attack_streamed, once per level.  One row layout for ALL levels: 8-bit codes give lattice rows until a query slice
-        # or a bank chunk turns out to be off-lattice floats; then the pass starts over with fresh bins in the hi / lo layout, and every
-        # later pass starts there.  Nothing of an abandoned layout survives in a histogram.
-        def rows(lo, hi):
-            if generated:
-                return bank.rows(lo, hi)
-            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1))) if isinstance(bank, DeviceArray) else bank[lo:hi]
-
-        role_q = None if q_feat else model.search_role("query")
-        nq = queries.n if q_feat else len(queries)
-        if q_feat or nq == 0:
-            slices = [(0, nq)]
-        else:
-            q_step = max(1, int(_query_budget_bytes(chunk_bytes, ctx) // _feature_row_bytes(ctx, model, queries)))
-            slices = [(a, min(a + q_step, nq)) for a in range(0, nq, q_step)]
-        state = {"fmt": "hilo" if (layout == "hilo" and role_q) else None, "fq": None}
-
-        def query_rows(a, b):
-            if q_feat:
-                return queries
-            if len(slices) == 1 and state["fq"] is not None and getattr(state["fq"], "fmt", None) == state["fmt"]:
-                return state["fq"]           # one slice: featurised once per layout, not once per pass
-            fq = model.features(queries[a:b], role=role_q, fmt=state["fmt"] if role_q else None)
-            if len(slices) == 1:
-                state["fq"] = fq
-            return fq
-
-        def stream(lo, shift, n_bins, hist):
-            """False: an off-lattice slice or chunk met lattice rows"""
-            for a, b in slices:
-                try:
-                    fq = query_rows(a, b)
-                except ValueError:
-                    if state["fmt"] != "lattice":
-                        raise
-                    return False
-                if role_q and state["fmt"] is None:
-                    state["fmt"] = fq.fmt    # the first slice settles it: 'lattice' for 8-bit codes, else 'hilo'
-                b_role = "bank" if getattr(fq, "role", None) else None
-                step = max(1, int(chunk_bytes // (fq.K * (2 if fq.role else 4))))
-                if fq.role:
-                    step = _lp.preferred_bank_rows(step, fq.n)
-                buf = None
-                for r0 in range(0, n_rows, step):
-                    try:
-                        buf = model.features(rows(r0, min(r0 + step, n_rows)), index_base=index_base + r0, role=b_role, out=buf,
-                                             fmt=getattr(fq, "fmt", None))
-                    except ValueError:
-                        if q_feat or getattr(fq, "fmt", None) != "lattice":
-                            raise
-                        return False
-                    _lp.feat_hist(buf, fq, lo, shift, n_bins, hist=hist)
-                    ctx.sync()
-            return True
-
-        def one_pass(lo, shift, n_bins):
-            hist = new_hist(ctx, n_bins)
-            if not stream(lo, shift, n_bins, hist):
-                state["fmt"], state["fq"] = "hilo", None
-                hist = new_hist(ctx, n_bins)             # the bins of the abandoned layout are dropped
-                if not stream(lo, shift, n_bins, hist):
-                    raise AssertionError("unreachable")
-            if reduce_fn is not None:
-                hist = reduce_fn(hist)
-            return hist.numpy().reshape(-1)[:n_bins].astype(np.int64)
-
-    return _select_float_bits(one_pass, q, ctx, reduce_fn, nq * n_rows)
 
 
 def pair_distance_quantiles(queries, bank, quantiles, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None,
@@ -1963,7 +1713,9 @@ def pair_distance_quantiles(queries, bank, quantiles, distance="l2-lpips", batch
         raise ValueError("distance must be 'l2' or 'l2-lpips', got %r" % (distance,))
     float_path = _check_rows_float_path(float_path)
     if distance == "l2-lpips":
-        return _pair_quantiles_lpips(queries, bank, q, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, _layout)
+        from . import lpips as _lp
+        ctx, nq, n_rows, run_pass = _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, _layout)
+        return _select_float_bits(_hist_passes(ctx, lambda *a: _lp.feat_hist(*a), run_pass, reduce_fn), q, ctx, reduce_fn, nq * n_rows)
     if float_path is None or _layout != "f32":
         try:
             return distance_quantiles(queries, bank, q, batch_size=batch_size, ctx=ctx, reduce_fn=reduce_fn, chunk_bytes=chunk_bytes,
@@ -1971,7 +1723,8 @@ def pair_distance_quantiles(queries, bank, quantiles, distance="l2-lpips", batch
         except _OffLattice:
             if float_path is None:
                 raise                        # nothing of the integer pass survives: the fp32 rows start over
-    return _pair_quantiles_f32(queries, bank, q, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    ctx, nq, n_rows, run_pass = _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
+    return _select_float_bits(_hist_passes(ctx, lambda *a: pair_histogram_f32(*a), run_pass, reduce_fn), q, ctx, reduce_fn, nq * n_rows)
 
 
 def eps_rows_to_bits(eps):
@@ -2018,13 +1771,6 @@ def count_balls_rows_f32(bank, queries, thr, n_rows=None, counts=None):
     return counts
 
 
-def _slice_rows(arr, a, b):
-    """rows [a, b) of a DeviceArray whose first axis runs over the queries"""
-    rest = tuple(arr.shape[1:])
-    row_bytes = arr.dtype.itemsize * int(np.prod(rest, dtype=np.int64))
-    return arr.view((b - a,) + rest, offset_bytes=a * row_bytes)
-
-
 def _count_launch_f32(b, fq, per_query, n, out):
     count_balls_rows_f32(b, fq, per_query[0], n, out)
 
@@ -2034,205 +1780,14 @@ def _count_launch_lpips(b, fq, per_query, n, out):
     _lp.feat_count_rows(b, fq, per_query[0], n, out)
 
 
-def _counter_of(ctx, nq, reduce_fn, launch, run_pass):
-    """count_pass(thr int64 [Q, T] on patterns, rows ascending) -> int64 [Q, T] on a walker's run_pass"""
-    def count_pass(thr):
-        thr = np.ascontiguousarray(thr, np.int64)
-        counts = run_pass(lambda: new_counts(ctx, nq, thr.shape[1]), [thr], launch, reduce_fn)
-        return counts.numpy()[:nq].astype(np.int64)
-    return count_pass
-
-
-def _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
-    """one pass over the fp32 rows of a bank, whatever is reduced from the pairs: _pair_quantiles_f32's rows, chunks and n_eff.  Returns
-    (ctx, nq, n_rows, run_pass) with run_pass(new_out, per_query, launch, reduce) -> DeviceArray: new_out() makes the fresh output of the
-    pass (first axis: the queries), per_query is a list of host arrays [Q, ...] that are uploaded once for all chunks, and
-    launch(bank rows, query rows, per_query DeviceArrays, n_rows or None, out) is the per-chunk launch that adds to `out`; reduce (or
-    None) is the cross-shard reduction of the output.  A bank of one chunk is uploaded once, a longer one once per pass."""
-    if getattr(bank, "kind", None) == "feat" or getattr(queries, "kind", None) == "feat":
-        raise NotImplementedError("distance='l2' takes images or tables; got LPIPS feature rows")
-    prepared = isinstance(bank, Bank)
-    generated = getattr(bank, "kind", None) == "generated"
-    if prepared or generated:
-        ctx = bank.ctx
-        base = bank.index_base
-    else:
-        ctx = ctx or Context.get()
-        base = int(index_base)
-    shard = reduce_fn is not None or base != 0
-    n_rows = len(bank) if shard else (len(bank) // int(batch_size)) * int(batch_size)
-    if n_rows == 0 and reduce_fn is None:
-        raise ValueError("bank holds no full batch of %d samples (attack_models/fbb.py:77-83)" % int(batch_size))
-    fq = queries.as_f32() if isinstance(queries, Bank) else Bank.from_images(queries, ctx, force_kind="f32")
-    resident = None
-    if prepared:
-        resident = bank.as_f32()
-    else:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        step = max(1, int(chunk_bytes // (4 * fq.d)))
-
-    def rows(lo, hi):
-        if generated:
-            return bank.rows(lo, hi)
-        if isinstance(bank, DeviceArray):
-            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1)))
-        return bank[lo:hi]
-
-    if resident is None and 0 < n_rows <= step:
-        resident = Bank.from_images(rows(0, n_rows), ctx, index_base=base, force_kind="f32")
-
-    def run_pass(new_out, per_query, launch, reduce):
-        out = new_out()                                      # fresh per pass
-        if fq.n and n_rows:
-            dev = [ctx.to_device(np.ascontiguousarray(a)) for a in per_query]
-            if resident is not None:
-                launch(resident, fq, dev, n_rows, out)
-            else:
-                for r0 in range(0, n_rows, step):
-                    b = Bank.from_images(rows(r0, min(r0 + step, n_rows)), ctx, index_base=base + r0, force_kind="f32")
-                    launch(b, fq, dev, None, out)
-                    ctx.sync()
-            ctx.sync()                                       # the uploads are released on return
-        if reduce is not None:               # (a shard without rows takes part with an untouched output)
-            out = reduce(out)
-        return out
-
-    return ctx, fq.n, n_rows, run_pass
-
-
-def _pair_rows_counter_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base):
-    """the per-query counts on fp32 rows, on _pair_rows_walker_f32.  Returns (ctx, nq, n_rows, count_pass) with count_pass(thr int64 [Q, T]
-    on patterns, rows ascending) -> int64 [Q, T], summed over the chunks and -- through reduce_fn -- the shards."""
+def _pair_rows_counter(queries, bank, distance, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, layout):
+    """the per-query counts on the float paths: (ctx, nq, n_rows, count_pass) with count_pass(thr int64 [Q, T] on patterns, rows ascending)
+    -> int64 [Q, T], one lpips.feat_count_rows / count_balls_rows_f32 pass over the bank per call"""
+    if distance == "l2-lpips":
+        ctx, nq, n_rows, run_pass = _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, layout)
+        return ctx, nq, n_rows, _counter_of(ctx, nq, reduce_fn, _count_launch_lpips, run_pass)
     ctx, nq, n_rows, run_pass = _pair_rows_walker_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
     return ctx, nq, n_rows, _counter_of(ctx, nq, reduce_fn, _count_launch_f32, run_pass)
-
-
-def _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
-    """one pass over the 'l2-lpips' rows of a bank, whatever is reduced from the pairs: _pair_quantiles_lpips' resident / streamed
-    decision, row preparation, query slices and single row layout per call.  Returns (ctx, nq, n_rows, run_pass) as
-    _pair_rows_walker_f32 does; the launch sees FeatureBanks, and of the per-query arrays and the output the rows of its query slice."""
-    from . import lpips as _lp
-    prepared, generated, ctx, index_base, n_rows = _lpips_rows_in_play(bank, batch_size, ctx, reduce_fn, index_base)
-    q_feat = getattr(queries, "kind", None) == "feat"
-    if model is None and not (prepared and q_feat):        # prepared rows on both sides need no VGG16
-        model = _lp.default_model()
-    streamed = False
-    if not prepared:
-        chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        if generated or n_rows == 0:         # (an empty shard still takes part in the reduction: the streamed form handles it)
-            streamed = True
-        else:
-            per_img = _feature_row_bytes(ctx, model, bank)
-            streamed = per_img * n_rows > chunk_bytes or (not q_feat and len(queries) * per_img > chunk_bytes)
-        if not streamed:
-            bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
-
-    if not streamed:
-        if layout == "hilo" and model is not None and model.search_role("bank"):
-            fb = bank if prepared else model.features(bank, index_base=index_base, role="bank", fmt="hilo")
-            fq = queries if q_feat else model.features(queries, role="query", fmt="hilo")
-        else:
-            fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
-        nq = fq.n
-
-        def run_pass(new_out, per_query, launch, reduce):
-            out = new_out()                                      # fresh per pass
-            if nq and n_rows:
-                dev = [ctx.to_device(np.ascontiguousarray(a)) for a in per_query]
-                launch(fb, fq, dev, n_rows, out)
-                ctx.sync()                                       # the uploads are released on return
-            if reduce is not None:
-                out = reduce(out)
-            return out
-    else:
-        # The stream of _pair_quantiles_lpips, once per pass.  One row layout for ALL passes: 8-bit codes give lattice rows until a query
-        # slice or a bank chunk turns out to be off-lattice floats; then the pass starts over with a fresh output in the hi / lo layout,
-        # and every later pass starts there.  Nothing of an abandoned layout survives in an output.
-        def rows(lo, hi):
-            if generated:
-                return bank.rows(lo, hi)
-            return bank.view((hi - lo,) + tuple(bank.shape[1:]), offset_bytes=lo * (bank.nbytes // max(len(bank), 1))) if isinstance(bank, DeviceArray) else bank[lo:hi]
-
-        role_q = None if q_feat else model.search_role("query")
-        nq = queries.n if q_feat else len(queries)
-        if q_feat or nq == 0:
-            slices = [(0, nq)]
-        else:
-            q_step = max(1, int(_query_budget_bytes(chunk_bytes, ctx) // _feature_row_bytes(ctx, model, queries)))
-            slices = [(a, min(a + q_step, nq)) for a in range(0, nq, q_step)]
-        state = {"fmt": "hilo" if (layout == "hilo" and role_q) else None, "fq": None}
-
-        def query_rows(a, b):
-            if q_feat:
-                return queries
-            if len(slices) == 1 and state["fq"] is not None and getattr(state["fq"], "fmt", None) == state["fmt"]:
-                return state["fq"]           # one slice: featurised once per layout, not once per pass
-            fq = model.features(queries[a:b], role=role_q, fmt=state["fmt"] if role_q else None)
-            if len(slices) == 1:
-                state["fq"] = fq
-            return fq
-
-        def stream(dev, launch, out):
-            """False: an off-lattice slice or chunk met lattice rows"""
-            for a, b in slices:
-                if b == a:
-                    continue
-                try:
-                    fq = query_rows(a, b)
-                except ValueError:
-                    if state["fmt"] != "lattice":
-                        raise
-                    return False
-                if role_q and state["fmt"] is None:
-                    state["fmt"] = fq.fmt    # the first slice settles it: 'lattice' for 8-bit codes, else 'hilo'
-                b_role = "bank" if getattr(fq, "role", None) else None
-                step = max(1, int(chunk_bytes // (fq.K * (2 if fq.role else 4))))
-                if fq.role:
-                    step = _lp.preferred_bank_rows(step, fq.n)
-                # the slice's rows of the per-query arrays and of the output
-                dev_s = [_slice_rows(x, a, b) for x in dev]
-                out_s = _slice_rows(out, a, b)
-                buf = None
-                for r0 in range(0, n_rows, step):
-                    try:
-                        buf = model.features(rows(r0, min(r0 + step, n_rows)), index_base=index_base + r0, role=b_role, out=buf,
-                                             fmt=getattr(fq, "fmt", None))
-                    except ValueError:
-                        if q_feat or getattr(fq, "fmt", None) != "lattice":
-                            raise
-                        return False
-                    launch(buf, fq, dev_s, None, out_s)
-                    ctx.sync()
-            return True
-
-        def run_pass(new_out, per_query, launch, reduce):
-            out = new_out()
-            if nq and n_rows:
-                dev = [ctx.to_device(np.ascontiguousarray(a)) for a in per_query]      # once per pass, for all slices and chunks
-                if not stream(dev, launch, out):
-                    state["fmt"], state["fq"] = "hilo", None
-                    out = new_out()                          # the output of the abandoned layout is dropped
-                    if not stream(dev, launch, out):
-                        raise AssertionError("unreachable")
-                ctx.sync()                                   # the uploads are released on return
-            if reduce is not None:           # (a shard without rows takes part with an untouched output)
-                out = reduce(out)
-            return out
-
-    return ctx, nq, n_rows, run_pass
-
-
-def _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout):
-    """the per-query counts under 'l2-lpips', on _pair_rows_walker_lpips: one lpips.feat_count_rows pass per call of count_pass.  Returns
-    (ctx, nq, n_rows, count_pass) as _pair_rows_counter_f32 does."""
-    ctx, nq, n_rows, run_pass = _pair_rows_walker_lpips(queries, bank, batch_size, ctx, reduce_fn, model, chunk_bytes, index_base, layout)
-    return ctx, nq, n_rows, _counter_of(ctx, nq, reduce_fn, _count_launch_lpips, run_pass)
-
-
-def _pair_rows_counter(queries, bank, distance, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, layout):
-    if distance == "l2-lpips":
-        return _pair_rows_counter_lpips(queries, bank, batch_size, ctx, reduce_fn, lpips, chunk_bytes, index_base, layout)
-    return _pair_rows_counter_f32(queries, bank, batch_size, ctx, reduce_fn, chunk_bytes, index_base)
 
 
 def pair_ball_counts_rows(queries, bank, eps, distance="l2-lpips", batch_size=64, ctx=None, reduce_fn=None, lpips=None, chunk_bytes=None, index_base=0,
@@ -2441,9 +1996,7 @@ def pair_kde_scores(queries, bank, bandwidths, distance="l2-lpips", batch_size=6
             if float_path is None:
                 raise                        # nothing of the integer passes survives: the fp32 rows start over
     reduce_min, reduce_sum = reduce_fn if reduce_fn is not None else (None, None)
-    base = getattr(bank, "index_base", None)
-    base = int(index_base) if base is None else int(base)
-    n_local = len(bank) if (reduce_fn is not None or base != 0) else (len(bank) // int(batch_size)) * int(batch_size)
+    _, _, n_local = _rows_in_play(bank, batch_size, None, reduce_fn, index_base)
     if n_local >= KDE_MAX_ROWS:
         raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d given): 2^23 weights of 2^40 overflow 64 bits" % n_local)
     c32, h_eff = kde_coef(h, 1, "f32")
@@ -2470,12 +2023,7 @@ def pair_kde_scores(queries, bank, bandwidths, distance="l2-lpips", batch_size=6
             raise ValueError("kernel-density sums take fewer than 2^23 bank rows per query (%d over all shards)" % n_eff)
 
     # pass 1: the nearest sample of every query; the key's upper half is the pattern of its float32 distance
-    def new_keys():
-        keys = ctx.empty((max(nq, 1),), np.uint64)
-        check(ctx.lib.gl_keys_init(ctx.handle, _p(keys.ptr), nq))
-        return keys
-
-    keys = run_pass(new_keys, [], knn_launch, reduce_min)
+    keys = run_pass(lambda: _new_keys(ctx, nq), [], knn_launch, reduce_min)
     key = (keys.numpy()[:nq] >> np.uint64(32)).astype(np.int64)
     D0 = key.astype(np.uint32).view(np.float32)
     if not np.all(np.isfinite(D0)):
@@ -2517,7 +2065,7 @@ def pair_distances(queries, bank, distance="l2-lpips", batch_size=64, lpips=None
     if model is None and not (prepared and getattr(queries, "kind", None) == "feat"):
         model = _lp.default_model()
     if not prepared:
-        bank = bank.view((n_rows,) + tuple(bank.shape[1:])) if isinstance(bank, DeviceArray) else bank[:n_rows]
+        bank = _bank_rows(bank, 0, n_rows)
     fb, fq = _lpips_resident_rows(queries, bank, prepared, model, index_base)
     return _lp.feat_pair_dist(fb, fq, n_rows)
 

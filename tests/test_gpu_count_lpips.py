@@ -144,6 +144,16 @@ def test_counts_do_not_depend_on_chunks_slices_shards_or_prepared_rows(gl, synth
     monkeypatch.setenv("GANLEAKS_QUERY_GB", repr(20.5 * row / (1 << 30)))
     assert np.array_equal(gl.ball_counts(q, bank, eps, chunk_bytes=100 * row, **kw), resident)
     assert np.array_equal(gl.ball_counts(q, gen, eps, chunk_bytes=100 * row, **kw), resident)
+    # reduce_fn fires once per pass over the bank with the counters of ALL queries, not once per slice
+    shapes = []
+
+    def recording(counts):
+        shapes.append(tuple(counts.shape))
+        return counts
+
+    sliced = gl.ball_counts(q, bank[:n_eff], eps, chunk_bytes=100 * row, reduce_fn=recording, **kw)    # (a shard is not truncated again)
+    assert shapes == [(len(q), len(eps))]
+    assert np.array_equal(sliced, resident)
     monkeypatch.delenv("GANLEAKS_QUERY_GB")
     # two shards of the truncated bank: index_base on the second, a world-of-one reduction on the first
     a = gl.ball_counts(q, bank[:150], eps, reduce_fn=shard.allreduce_sum_counts, **kw)

@@ -180,6 +180,15 @@ def test_lists_do_not_depend_on_chunks_slices_shards_or_prepared_rows(gl, synth,
     monkeypatch.setenv("GANLEAKS_QUERY_GB", repr(20.5 * row / (1 << 30)))
     equal(gl.nearest_neighbours(q, bank, k, chunk_bytes=100 * row, **kw))
     equal(gl.nearest_neighbours(q, gen, k, chunk_bytes=100 * row, **kw))
+    # reduce_fn fires once per pass over the bank with the key lists of ALL queries, not once per slice
+    shapes = []
+
+    def recording(keys):
+        shapes.append(tuple(keys.shape))
+        return keys
+
+    equal(gl.nearest_neighbours(q, bank[:n_eff], k, chunk_bytes=100 * row, reduce_fn=recording, **kw))    # (a shard is not truncated again)
+    assert shapes == [(len(q), k)]
     monkeypatch.delenv("GANLEAKS_QUERY_GB")
     # two shards of the truncated bank: index_base on the second, a world-of-one reduction on the first; merged on the host
     a = gl.nearest_neighbours(q, bank[:150], k, reduce_fn=lambda keys: shard.allreduce_topk_keys(keys, k), **kw)

@@ -741,3 +741,12 @@ int gl_dcgan_forward(gl_dcgan *g, const float *z_dev, int64_t n, float *out_f32_
 }
 
 }  // extern "C"
+
+#ifdef GL_TUNING
+// tuning build only, below the file's last __LINE__-bearing check of the production code (the production object stays what it was):
+// ONE launch of attention_core_kernel<C, SPLIT>, as gl_dcgan_forward launches it (gl_tune_attention, csrc/gl_tune.hip)
+int gl_tune_attention_core(gl_ctx *ctx, int C, int split, const float *qkv, const float *x, float *y, int64_t images, float gamma)
+{
+    return C == 128 ? launch_attention_core<128>(ctx, split != 0, qkv, x, y, images, gamma) : launch_attention_core<64>(ctx, split != 0, qkv, x, y, images, gamma);
+}
+#endif

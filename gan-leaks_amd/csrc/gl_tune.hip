@@ -1,6 +1,7 @@
 // TUNING BUILD ONLY (linked into libganleaks_hip_tuning.so, never into libganleaks_hip.so; not part of include/ganleaks.h).
-// Three entries: gl_tune_winograd_bound (a timing experiment, below), gl_tune_conv_layer (one convolution launch on host arrays, for the
-// per-layer tests) and gl_tune_split_post (one launch of a stand-alone PixelNorm / LPIPS tap kernel on a split activation; at the end of the file).
+// Four entries: gl_tune_winograd_bound (a timing experiment, below), gl_tune_conv_layer (one convolution launch on host arrays, for the
+// per-layer tests), gl_tune_split_post (one launch of a stand-alone PixelNorm / LPIPS tap kernel on a split activation) and gl_tune_attention
+// (one launch of the self-attention kernel of gl_dcgan.hip; at the end of the file).
 //
 // gl_tune_winograd_bound: the measured UPPER bound of what Winograd F(2x2,3x3) could buy on the split-fp16 convolution path (VERDICT r2
 // "Next 1").  F(2x2,3x3) replaces a 3x3 convolution over P positions by 16 independent GEMMs  M_j = U_j (C_out x C_in) . V_j (C_in x P/4)
@@ -443,6 +444,71 @@ extern "C" int gl_tune_split_post(gl_ctx *ctx, GlTuneSplitPost *q)
             TUNE_HIP(hipMemcpy(host[b], bufs[b] + OG, (size_t)bytes[b], hipMemcpyDeviceToHost));
         }
     }
+#undef TUNE_HIP
+#undef TUNE_RC
+    cleanup();
+    return GL_OK;
+}
+
+// gl_tune_attention: ONE launch of launch_attention_core<64 | 128> (csrc/gl_dcgan.hip) on plain host arrays, for tests/test_gpu_attention.py.
+// qkv fp32 [n_img][256][2 C / 8 + C]; x and y are RAW bytes, n_img * 256 * C * 4 of them: fp32 NHWC, or with `split` the split-fp16 layout the
+// kernel reads and writes (encoding and decoding it is the test's job, so the layout is under test as well).  Same treatment as above: qkv and x
+// each sit between 4 KiB guards of `poison` (fp32 values; fp16 halves of the same value around a split x), y is pre-filled with `sentinel` and
+// sits between 4 KiB sentinel guards, which come back.
+struct GlTuneAttention {                 // mirrored field by field in tests/attention_common.py
+    int32_t C, split;
+    int64_t n_img;
+    float gamma, poison;
+    int32_t sentinel, reserved_i;
+    const float *qkv;
+    const void *x;
+    void *y;                             // <- n_img * 256 * C * 4 bytes
+    void *out_guards;                    // <- 2 * 4096 bytes: below | above y
+    int64_t sat_delta;                   // <- change of the context's split-store saturation counter
+};
+
+int gl_tune_attention_core(gl_ctx *ctx, int C, int split, const float *qkv, const float *x, float *y, int64_t images, float gamma);   // gl_dcgan.hip
+
+extern "C" int gl_tune_attention(gl_ctx *ctx, GlTuneAttention *q)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && q && q->qkv && q->x && q->y && q->out_guards, "gl_tune_attention: NULL argument");
+    GL_REQUIRE((q->C == 64 || q->C == 128) && q->n_img > 0 && q->n_img <= 4096, "gl_tune_attention: C must be 64 or 128, n_img in 1..4096");
+    constexpr int64_t G = 4096;
+    const int64_t qkv_bytes = q->n_img * 256 * (2 * (q->C / 8) + q->C) * 4, x_bytes = q->n_img * 256 * q->C * 4;
+    char *d_qkv = nullptr, *d_x = nullptr, *d_y = nullptr;
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(ctx->stream);
+        (void)hipFree(d_qkv); (void)hipFree(d_x); (void)hipFree(d_y);
+    };
+#define TUNE_HIP(e) do { if ((e) != hipSuccess) { gl_set_error("gl_tune_attention: %s failed", #e); cleanup(); return GL_ERR_HIP; } } while (0)
+#define TUNE_RC(e) do { const int rc_ = (e); if (rc_ != GL_OK) { cleanup(); return rc_; } } while (0)
+    TUNE_HIP(hipMalloc((void **)&d_qkv, (size_t)(qkv_bytes + 2 * G)));
+    TUNE_HIP(hipMalloc((void **)&d_x, (size_t)(x_bytes + 2 * G)));
+    TUNE_HIP(hipMalloc((void **)&d_y, (size_t)(x_bytes + 2 * G)));
+    {
+        std::vector<float> gf((size_t)(G / 4), q->poison);
+        std::vector<_Float16> gh((size_t)(G / 2), (_Float16)q->poison);
+        const void *gx = q->split ? (const void *)gh.data() : (const void *)gf.data();
+        TUNE_HIP(hipMemcpy(d_qkv, gf.data(), (size_t)G, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_qkv + G, q->qkv, (size_t)qkv_bytes, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_qkv + G + qkv_bytes, gf.data(), (size_t)G, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_x, gx, (size_t)G, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_x + G, q->x, (size_t)x_bytes, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_x + G + x_bytes, gx, (size_t)G, hipMemcpyHostToDevice));
+    }
+    TUNE_HIP(hipMemset(d_y, q->sentinel & 0xFF, (size_t)(x_bytes + 2 * G)));
+    int sat0 = 0, sat1 = 0;
+    TUNE_HIP(hipDeviceSynchronize());
+    TUNE_HIP(hipMemcpy(&sat0, ctx->h3_sat, 4, hipMemcpyDeviceToHost));
+    TUNE_RC(gl_tune_attention_core(ctx, q->C, q->split, reinterpret_cast<const float *>(d_qkv + G), reinterpret_cast<const float *>(d_x + G),
+                                   reinterpret_cast<float *>(d_y + G), q->n_img, q->gamma));
+    TUNE_HIP(hipStreamSynchronize(ctx->stream));
+    TUNE_HIP(hipMemcpy(&sat1, ctx->h3_sat, 4, hipMemcpyDeviceToHost));
+    q->sat_delta = (int64_t)sat1 - sat0;
+    TUNE_HIP(hipMemcpy(q->out_guards, d_y, (size_t)G, hipMemcpyDeviceToHost));
+    TUNE_HIP(hipMemcpy(reinterpret_cast<char *>(q->out_guards) + G, d_y + G + x_bytes, (size_t)G, hipMemcpyDeviceToHost));
+    TUNE_HIP(hipMemcpy(q->y, d_y + G, (size_t)x_bytes, hipMemcpyDeviceToHost));
 #undef TUNE_HIP
 #undef TUNE_RC
     cleanup();

@@ -12,8 +12,8 @@ import torch
 import torch.nn.functional as F
 
 
-def _t(a):
-    return torch.from_numpy(np.asarray(a)).double()
+def _t(a, dtype=torch.float64):
+    return torch.from_numpy(np.asarray(a)).to(dtype)
 
 
 def _l2n(v, eps=1e-12):
@@ -21,8 +21,10 @@ def _l2n(v, eps=1e-12):
 
 
 class VaeganOracle:
-    def __init__(self, sd):
-        self.sd = {k: _t(v) for k, v in sd.items() if not k.endswith("num_batches_tracked")}
+    def __init__(self, sd, dtype=torch.float64):
+        """dtype=torch.float32: the same evaluation in single precision, the yardstick of the per-vector spectral-norm bounds"""
+        self.dtype = dtype
+        self.sd = {k: _t(v, dtype) for k, v in sd.items() if not k.endswith("num_batches_tracked")}
 
     def _sn_weight(self, name):
         w = self.sd[name + ".module.weight_bar"]
@@ -51,7 +53,7 @@ class VaeganOracle:
 
     def forward(self, z):
         s = self.sd
-        x = _t(z).reshape(len(z), -1, 1, 1)
+        x = _t(z, self.dtype).reshape(len(z), -1, 1, 1)
         x = F.relu(self._bn(F.conv_transpose2d(x, self._sn_weight("deconv1"), s["deconv1.module.bias"], 1, 0), "deconv1_bn"))
         x = F.relu(self._bn(F.conv_transpose2d(x, self._sn_weight("deconv2"), s["deconv2.module.bias"], 2, 1), "deconv2_bn"))
         x = self._attention(F.relu(self._bn(F.conv_transpose2d(x, self._sn_weight("deconv3"), s["deconv3.module.bias"], 2, 1), "deconv3_bn")))

@@ -1,5 +1,10 @@
 """GPU parity of the VAEGAN generator (spectral-norm ConvTranspose stack + self-attention) against two consecutive
-forwards of the reference's own Generator (tests/golden/vaegan_gen.npz).  Tolerance 5e-5 on outputs in (-1,1)."""
+forwards of the reference's own Generator (tests/golden/vaegan_gen.npz).  Tolerance 5e-5 on outputs in (-1,1).
+
+The spectral-norm kernels are pinned through the public ABI: after each of two forwards all eight weight_u / weight_v of state_dict() against
+VaeganOracle in float64, bound 4 x the error of the same oracle in float32 (floor: one float32 ulp of the vector's largest element), for
+(z_dim, d) = (100, 64), (64, 32) and, with d = 32, z_dim = 300 (H > 256) and 3.  Measured on an MI355X over all 96 vectors: device 5.4e-9 - 6.4e-8,
+float32 oracle 7.8e-9 - 1.3e-7, device / bound 0.02 - 0.36."""
 import os
 
 import numpy as np
@@ -8,6 +13,43 @@ import pytest
 import gpu_common  # noqa: F401
 
 pytestmark = pytest.mark.gpu
+
+SN_KEYS = ["deconv%d.module.weight_%s" % (l, w) for l in (1, 2, 3, 4) for w in "uv"]
+_steps = {}
+
+
+def oracle_steps(synth, seed, z_dim, d, z, steps=2):
+    """`steps` consecutive forwards of VaeganOracle in float64 and, on the same state dict, in float32: per forward the float64 output and, for each
+    of the eight power-iteration vectors, (float64 vector, largest error of the float32 evaluation against it).  Computed once per generator."""
+    key = (seed, z_dim, d, steps)
+    if key not in _steps:
+        import torch
+        import vaegan_oracle
+        sd = synth.vaegan_state_dict(seed, z_dim, d)
+        o64, o32 = vaegan_oracle.VaeganOracle(sd), vaegan_oracle.VaeganOracle(sd, torch.float32)
+        res = []
+        for _ in range(steps):
+            out = o64.forward(z)
+            o32.forward(z)
+            res.append((out, {k: (o64.sd[k].numpy().copy(), float(np.abs(o32.sd[k].double().numpy() - o64.sd[k].numpy()).max())) for k in SN_KEYS}))
+        _steps[key] = res
+    return _steps[key]
+
+
+def check_spectral_state(got, want, tag):
+    """every weight_u / weight_v within 4 x the float32 oracle's own error (tests/test_gpu_wb.py's margin), with a floor of one float32 ulp of the
+    vector's largest element"""
+    late = []
+    for k in SN_KEYS:
+        w64, e32 = want[k]
+        ulp = float(np.spacing(np.float32(np.abs(w64).max())))
+        err = float(np.abs(got[k].astype(np.float64) - w64).max())
+        bound = max(4.0 * e32, ulp)
+        print("%s %s [%d]: device %.3e  float32 oracle %.3e  bound %.3e  device / bound %.2f" % (tag, k, w64.size, err, e32, bound, err / bound))
+        assert got[k].shape == w64.shape
+        if not err <= bound:
+            late.append((k, err, e32, bound))
+    assert not late, (tag, late)
 
 
 @pytest.mark.parametrize("precision", [1, 0])
@@ -101,3 +143,39 @@ def test_vaegan_bank_attack_against_c_oracle(synth):
     f = gen2.eval()(z)
     diff = hb.astype(np.int32) - oracle.quantize_to_u8(f).astype(np.int32)
     assert np.abs(diff).max() <= 1 and (diff != 0).mean() < 1e-3          # forward() and generate_u8 are separate launches of the same arithmetic
+
+
+@pytest.mark.parametrize("z_dim,d,seed", [(100, 64, 777), (64, 32, 778)])
+def test_spectral_state_of_all_layers_after_each_of_two_forwards(z_dim, d, seed, synth):
+    """all eight power-iteration vectors through the public state_dict() (gl_dcgan_get_spectral_state), after the first and after the second forward"""
+    from ganleaks_amd.gan_models.vaegan.train import Generator
+    z = synth.latent(21, 2, z_dim)
+    steps = oracle_steps(synth, seed, z_dim, d, z)
+    gen = Generator(z_dim, d)
+    gen.load_state_dict(synth.vaegan_state_dict(seed, z_dim, d))
+    for s, (out64, want) in enumerate(steps):
+        out = gen(z)
+        assert np.abs(out - out64).max() < 5e-5
+        check_spectral_state(gen.state_dict(), want, "z_dim=%d d=%d forward %d" % (z_dim, d, s + 1))
+
+
+@pytest.mark.parametrize("precision", [1, 0])
+@pytest.mark.parametrize("z_dim", [300, 3])
+def test_vaegan_latent_wider_than_one_stride_and_tiny(z_dim, precision, synth):
+    """z_dim = 300: H > 256, the second trip of every 256-stride loop of the spectral-norm kernels and a z_pad above 256; z_dim = 3: one partial
+    32-wide K slice.  d = 32, n = 2, two forwards, outputs and all eight vectors against VaeganOracle"""
+    from ganleaks_amd.gan_models.vaegan.train import Generator
+    seed = 780 + z_dim
+    z = synth.latent(22, 2, z_dim)
+    steps = oracle_steps(synth, seed, z_dim, 32, z)
+    gen = Generator(z_dim, 32)
+    gen.load_state_dict(synth.vaegan_state_dict(seed, z_dim, 32))
+    gen.set_precision(precision)
+    for s, (out64, want) in enumerate(steps):
+        out = gen(z)
+        assert out.shape == (2, 3, 64, 64)
+        e = np.abs(out - out64).max()
+        print("z_dim=%d precision=%d forward %d: output error %.3e" % (z_dim, precision, s + 1, e))
+        assert e < 5e-5, e
+        check_spectral_state(gen.state_dict(), want, "z_dim=%d precision=%d forward %d" % (z_dim, precision, s + 1))
+    assert gen._precision == precision                  # no saturation fallback happened

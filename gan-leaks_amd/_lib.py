@@ -123,6 +123,7 @@ SIGNATURES = {
     "gl_dcgan_set_spectral_norm": (_i, [_p, _i, _p, _p, _p, _p, _p, _i]),
     "gl_dcgan_get_spectral_state": (_i, [_p, _i, _p, _p]),
     "gl_dcgan_set_spectral_hold": (_i, [_p, _i]),
+    "gl_dcgan_advance_spectral": (_i, [_p, _i]),
     "gl_dcgan_set_fuse_tail": (_i, [_p, _i]),
     "gl_dcgan_set_attention": (_i, [_p, _p, _p, _p, _p, _p, _p, ctypes.c_float]),
     "gl_dcgan_vjp_z": (_i, [_p, _p, _i64, _p, _p, _p]),

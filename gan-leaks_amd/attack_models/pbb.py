@@ -10,9 +10,13 @@ only improve on.
     python -m ganleaks_amd.attack_models.pbb --local_config config_attack_fbb.yaml --gan {dcgan,wgangp,pggan} --generator_path generator.pth
            [--nz --ngf --in_channels --steps --alpha] [--noise_path npz | --num_init N --init_seed s]
            [--rounds --population --sigma --seed] [--BATCH_SIZE]
+    python -m ganleaks_amd.attack_models.pbb ... --gan vaegan --sn_forwards K [--nz Z --ngf d]
     python -m ganleaks_amd.attack_models.pbb ... --pair_distance l2-lpips
 
 --gan, --generator_path  the generator class and its state dict (what the training scripts save as generator.pth)
+--sn_forwards            VAEGAN only, no default: VAEGAN's spectral normalisation advances with every forward, so the generator searched is the one
+                         its K-th forward after loading would have run, held from then on (Generator(nz, d=--ngf).frozen(K)); K >= 1,
+                         --resolution 64.  Without it --gan vaegan is refused
 --nz, --ngf              DCGAN / WGAN-GP: latent length and width (features_g); --nz, --in_channels, --steps, --alpha: PGGAN
 --noise_path             the .npz the generate branches write under npz_noise/ (array `noise`): the latents of the sample bank
 --num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
@@ -45,6 +49,7 @@ from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, sa
 
 # options added after params.txt got its form: an unused one leaves the file as it was before the option existed
 LATER_OPTIONS = ("pair_distance",)
+VAEGAN_OPTIONS = ("sn_forwards",)        # the same: params.txt names K only where --gan vaegan gave it
 
 
 def parse_arguments(argv=None):
@@ -56,7 +61,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--resolution', '-resolution', type=int, default=64, help='images that differ are resized to this square size')
     parser.add_argument('--BATCH_SIZE', type=int, default=30)
     parser.add_argument('--local_config', type=str, default=None)
-    parser.add_argument('--gan', type=str, default='dcgan', choices=['dcgan', 'wgangp', 'pggan'], help='the generator class')
+    parser.add_argument('--gan', type=str, default='dcgan', choices=['dcgan', 'wgangp', 'pggan', 'vaegan'], help='the generator class (vaegan: with --sn_forwards)')
     parser.add_argument('--generator_path', type=str, default=None, help="the generator's state dict (generator.pth)")
     parser.add_argument('--nz', type=int, default=None, help='length of a latent vector (default 100; 256 for pggan)')
     parser.add_argument('--ngf', type=int, default=64, help='dcgan / wgangp: width parameter of the generator (features_g)')
@@ -64,6 +69,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--in_channels', type=int, default=256, help='pggan: channel count of the first block')
     parser.add_argument('--steps', type=int, default=4, help='pggan: resolution steps (4 * 2^steps pixels)')
     parser.add_argument('--alpha', type=float, default=1.0, help='pggan: fade-in weight of the last block')
+    parser.add_argument('--sn_forwards', type=int, default=None, help='vaegan: hold the spectral-norm state of the K-th forward after loading; no default')
     parser.add_argument('--noise_path', type=str, default=None, help="npz with the bank's latents (array 'noise'), as the generate branches write it")
     parser.add_argument('--num_init', type=int, default=None, help='without --noise_path: draw this many starting latents')
     parser.add_argument('--init_seed', type=int, default=0, help='seed of the drawn starting latents')
@@ -91,8 +97,19 @@ def _request(args):
         raise SystemExit("--num_init must be at least 1, got %s" % (args.num_init,))
     if int(args.rounds) < 0 or int(args.population) < 1 or not (np.isfinite(args.sigma) and args.sigma > 0):
         raise SystemExit("--rounds must be >= 0, --population >= 1 and --sigma positive, got %s, %s, %s" % (args.rounds, args.population, args.sigma))
-    if args.gan not in ("dcgan", "wgangp", "pggan"):
-        raise SystemExit("--gan must be dcgan, wgangp or pggan, got %r (VAEGAN's generator changes with every forward)" % (args.gan,))
+    if args.gan not in ("dcgan", "wgangp", "pggan", "vaegan"):
+        raise SystemExit("--gan must be dcgan, wgangp, pggan or vaegan, got %r" % (args.gan,))
+    sn = getattr(args, "sn_forwards", None)
+    if args.gan == "vaegan":
+        if sn is None:
+            raise SystemExit("--gan vaegan needs --sn_forwards K: vaegan's generator changes with every forward, so the generator to search has "
+                             "to be named -- the one its K-th forward after loading runs, held from then on; there is no default")
+        if int(sn) < 1:
+            raise SystemExit("--sn_forwards must be at least 1, got %s" % (sn,))
+        if int(args.resolution) != 64:
+            raise SystemExit("--gan vaegan makes 64 x 64 images; --resolution is %s" % (args.resolution,))
+    elif sn is not None:
+        raise SystemExit("--sn_forwards belongs to --gan vaegan, got --gan %s" % (args.gan,))
 
 
 def load_generator(args):
@@ -103,6 +120,12 @@ def load_generator(args):
         from ..gan_models.pggan.model_torch import Generator
         nz = 256 if args.nz is None else int(args.nz)
         gen, kw = Generator(nz, int(args.in_channels), int(args.nc)), {"steps": int(args.steps), "alpha": float(args.alpha)}
+    elif args.gan == "vaegan":
+        from ..gan_models.vaegan.train import Generator
+        nz = 100 if args.nz is None else int(args.nz)
+        gen = Generator(nz, d=int(args.ngf))
+        gen.load_state_dict(sd)
+        return gen.frozen(int(args.sn_forwards)), {}, nz
     else:
         from ..gan_models.dcgan.model_torch import Generator     # wgangp shares it (gan_models/wgangp/model.py)
         nz = 100 if args.nz is None else int(args.nz)
@@ -115,7 +138,7 @@ def main(args):
     _request(args)
     assert os.path.exists(args.generator_path)
     save_dir = check_folder(os.path.join(os.getcwd(), 'pbb_attack', args.exp_name))
-    lines = ["%s:%s" % (key, value) for key, value in vars(args).items() if not (key in LATER_OPTIONS and value is None)]
+    lines = ["%s:%s" % (key, value) for key, value in vars(args).items() if not (key in LATER_OPTIONS + VAEGAN_OPTIONS and value is None)]
     with open(os.path.join(save_dir, 'params.txt'), 'w') as handle:
         handle.write("".join(line + "\n" for line in lines))
     print("\n".join(lines))

@@ -45,4 +45,13 @@ struct gl_dcgan {
     int64_t gws_chunk;           // images the gradient workspaces hold
     float *gws_y, *gws_g4, *gws_patch;   // kept fp32 output, cot * tanh', its 4 x 4 patches [pos][64]
     float *gws_da[4], *gws_gp[4];        // dL/da_l (NHWC, mirrors ws_a) and its masked, scaled, phase-planar form
+    // backward of the attention block (gl_attention_grad.hip): the [q | k | v] 1x1 convolution weights as given ([2 C/8 + C][C], rows as att_w),
+    // their transposed pack [C -> cols_pad][2 C/8 + C -> a multiple of 32], the rows [dq | dk | dv | 0] and the statistics (m, 1 / l, D) per position
+    std::vector<float> h_att_w;
+    float *gw_att, *gws_dqkv, *gws_att_stats;
 };
+
+// gl_attention_grad.hip: [dq | dk | dv | zero columns] rows of gl_attention_grad_cols(C) floats and [image][3][256] statistics from the forward's
+// qkv rows and dY, the gradient with respect to the attention block's output
+int gl_attention_grad_cols(int C);
+int gl_launch_attention_grad(gl_ctx *ctx, int C, const float *qkv, const float *dY, float gamma, int64_t images, float *dqkv, float *stats);

@@ -311,6 +311,7 @@ int gl_dcgan_create(gl_ctx *ctx, int z_dim, int channels_img, int features_g, gl
     g->gws_y = g->gws_g4 = g->gws_patch = nullptr;
     for (int l = 0; l < 5; ++l) g->gw[l] = nullptr;
     for (int l = 0; l < 4; ++l) g->gws_da[l] = g->gws_gp[l] = nullptr;
+    g->gw_att = g->gws_dqkv = g->gws_att_stats = nullptr;
     {
         std::vector<float> one(16 * channels_img, 1.0f), zero(16 * channels_img, 0.0f);
         int rc = upload(ctx, &g->ident_scale, one);
@@ -341,6 +342,7 @@ int gl_dcgan_destroy(gl_dcgan *g)
     for (int l = 0; l < 5; ++l) (void)hipFree(g->gw[l]);
     (void)hipFree(g->gws_y); (void)hipFree(g->gws_g4); (void)hipFree(g->gws_patch);
     for (int l = 0; l < 4; ++l) { (void)hipFree(g->gws_da[l]); (void)hipFree(g->gws_gp[l]); }
+    (void)hipFree(g->gw_att); (void)hipFree(g->gws_dqkv); (void)hipFree(g->gws_att_stats);
     for (int l = 0; l < 4; ++l) { (void)hipFree(g->sn_w[l]); (void)hipFree(g->sn_u[l]); (void)hipFree(g->sn_v[l]); (void)hipFree(g->sn_wv[l]); (void)hipFree(g->sn_bns[l]); }
     delete g;
     return GL_OK;
@@ -559,6 +561,8 @@ int gl_dcgan_set_attention(gl_dcgan *g, const float *wq, const float *bq, const 
     if (!g->have_att) g->ws_chunk = 0;            // the attention workspaces are allocated with the others
     g->att_gamma = gamma;
     g->have_att = true;
+    g->h_att_w.assign(pk.begin(), pk.begin() + (size_t)cols * C);
+    g->grad_dirty = true;
     return GL_OK;
 }
 
@@ -601,6 +605,49 @@ static int dcgan_prepare_h3(gl_dcgan *g)
     return GL_OK;
 }
 
+// one step of every spectrally normalised layer: `power_iterations` rounds of v = normalise(W^T u), u = normalise(W v) on the device, then
+// sigma = u . W v into the layer's epilogue scale (and its split-path copy).  What every gl_dcgan_forward does first unless the state is held,
+// and what gl_dcgan_advance_spectral repeats
+static int dcgan_advance_spectral(gl_dcgan *g)
+{
+    gl_ctx *ctx = g->ctx;
+    for (int l = 0; l < 4; ++l) {
+        if (!g->have_sn[l]) continue;
+        if (!g->scale_h3[l]) {                                      // fp32 mode never built the split-path copies
+            const int rc = dcgan_prepare_h3(g);
+            if (rc != GL_OK) return rc;
+        }
+        const int H = g->cin[l], C = g->cout[l], Wd = C * 16;
+        for (int it = 0; it < g->sn_iters; ++it) {
+            hipLaunchKernelGGL(sn_wt_u_kernel, dim3((unsigned)gl_ceil_div(Wd, 256)), dim3(256), 0, ctx->stream, g->sn_w[l], g->sn_u[l], H, Wd, g->sn_v[l]);
+            hipLaunchKernelGGL(sn_normalize_kernel, dim3(1), dim3(256), 0, ctx->stream, g->sn_v[l], Wd);
+            hipLaunchKernelGGL(sn_w_v_kernel, dim3((unsigned)H), dim3(256), 0, ctx->stream, g->sn_w[l], g->sn_v[l], Wd, g->sn_wv[l]);
+            hipLaunchKernelGGL(sn_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, g->sn_wv[l], H, g->sn_u[l], it + 1 == g->sn_iters ? 1 : 0, g->sn_bns[l], C,
+                               g->scale[l], g->scale_h3[l], std::ldexp(1.0f, -g->wexp[l]));
+        }
+        GL_LAUNCH_CHECK();
+    }
+    return GL_OK;
+}
+
+/* `times` steps of the spectral-norm state, each what one gl_dcgan_forward does before its first layer -- whether or not the state is held: with
+ * gl_dcgan_set_spectral_hold this makes a generator that stays the one the times-th next forward would have been */
+int gl_dcgan_advance_spectral(gl_dcgan *g, int times)
+{
+    gl_make_current(g ? g->ctx : nullptr);
+    GL_REQUIRE(g && times >= 0, "gl_dcgan_advance_spectral: bad argument");
+    for (int l = 0; l < 5; ++l)
+        if (!g->have_w[l] || (l < 4 && !g->have_bn[l])) {
+            gl_set_error("gl_dcgan_advance_spectral: weights of layer %d not loaded", l);
+            return GL_ERR_STATE;
+        }
+    for (int t = 0; t < times; ++t) {
+        const int rc = dcgan_advance_spectral(g);
+        if (rc != GL_OK) return rc;
+    }
+    return GL_OK;
+}
+
 int gl_dcgan_forward(gl_dcgan *g, const float *z_dev, int64_t n, float *out_f32_dev, uint8_t *out_u8_dev)
 {
     gl_make_current(g ? g->ctx : nullptr);
@@ -623,21 +670,9 @@ int gl_dcgan_forward(gl_dcgan *g, const float *z_dev, int64_t n, float *out_f32_
         rc = dcgan_prepare_h3(g);
         if (rc != GL_OK) return rc;
     }
-    for (int l = 0; l < 4; ++l) {
-        if (!g->have_sn[l] || g->sn_hold) continue;
-        if (!g->scale_h3[l]) {                                      // fp32 mode never built the split-path copies
-            rc = dcgan_prepare_h3(g);
-            if (rc != GL_OK) return rc;
-        }
-        const int H = g->cin[l], C = g->cout[l], Wd = C * 16;
-        for (int it = 0; it < g->sn_iters; ++it) {
-            hipLaunchKernelGGL(sn_wt_u_kernel, dim3((unsigned)gl_ceil_div(Wd, 256)), dim3(256), 0, ctx->stream, g->sn_w[l], g->sn_u[l], H, Wd, g->sn_v[l]);
-            hipLaunchKernelGGL(sn_normalize_kernel, dim3(1), dim3(256), 0, ctx->stream, g->sn_v[l], Wd);
-            hipLaunchKernelGGL(sn_w_v_kernel, dim3((unsigned)H), dim3(256), 0, ctx->stream, g->sn_w[l], g->sn_v[l], Wd, g->sn_wv[l]);
-            hipLaunchKernelGGL(sn_finish_kernel, dim3(1), dim3(256), 0, ctx->stream, g->sn_wv[l], H, g->sn_u[l], it + 1 == g->sn_iters ? 1 : 0, g->sn_bns[l], C,
-                               g->scale[l], g->scale_h3[l], std::ldexp(1.0f, -g->wexp[l]));
-        }
-        GL_LAUNCH_CHECK();
+    if (!g->sn_hold) {
+        rc = dcgan_advance_spectral(g);
+        if (rc != GL_OK) return rc;
     }
     auto launch = [&](GlGatherConv &p, int layer, int phases) {
         if (!h3) return gl_launch_gather_conv(ctx, p, phases);

@@ -15,6 +15,9 @@
 //   * the 3-channel layer: patch_rgb_kernel gathers the 4 x 4 x 3 window of g4 behind every 32 x 32 position into [pos][48 -> 64] rows
 //     (the mirror of col2im_rgb_tanh_kernel), then a one-tap GEMM with K = 64 gives the C_3 columns.
 //   * layer 0 is a plain GEMM [m][16 C1] x [16 C1][z_dim] written straight into grad_z (rows of z_dim, no padding), its K in chunks of 4096.
+//   * VAEGAN's stack with its spectral-norm state held: s_l = bn_scale / sigma is what g->scale[l] holds, and layer 3 reads y = gamma out + x of the
+//     self-attention block, so its data gradient is dY.  gl_attention_grad.hip turns dY and the forward's rows [q | k | v] into rows
+//     [dq | dk | dv | 0], and one one-tap GEMM with the transposed 1x1 weights adds them to dY in place (residual): dX = dA_2.
 // The FLOP count equals the forward's.  Transposed weight packs and workspaces are built on the first gradient call only.
 #include "gl_dcgan.h"
 #include <cmath>
@@ -191,6 +194,16 @@ int pack_grad_weights(gl_dcgan *g)
         const int rc = upload_pack(g->ctx, &g->gw[l], pk);
         if (rc != GL_OK) return rc;
     }
+    if (g->have_att) {
+        // [C -> cols_pad][K = 2 C/8 + C -> a multiple of 32], k the column of the rows [dq | dk | dv | 0]: one tap, so the K order is the identity
+        const int C = g->cout[2], rows = g->att_cols;
+        const size_t K = (size_t)gl_attention_grad_cols(C), cols_pad = (size_t)gl_ceil_div(C, 128) * 128;
+        std::vector<float> pk(cols_pad * K, 0.0f);
+        for (int c = 0; c < C; ++c)
+            for (int k = 0; k < rows; ++k) pk[(size_t)c * K + k] = g->h_att_w[(size_t)k * C + c];
+        const int rc = upload_pack(g->ctx, &g->gw_att, pk);
+        if (rc != GL_OK) return rc;
+    }
     g->grad_dirty = false;
     return GL_OK;
 }
@@ -209,10 +222,11 @@ int ensure_grad_workspace(gl_dcgan *g, int64_t n)
 {
     int64_t want = grad_pass_images(g);
     if (n < want) want = n;
-    if (want <= g->gws_chunk) return GL_OK;
+    if (want <= g->gws_chunk && (!g->have_att || g->gws_dqkv)) return GL_OK;
+    if (want < g->gws_chunk) want = g->gws_chunk;
     GL_HIP(hipStreamSynchronize(g->ctx->stream));
     float **all[] = {&g->gws_y, &g->gws_g4, &g->gws_patch, &g->gws_da[0], &g->gws_da[1], &g->gws_da[2], &g->gws_da[3],
-                     &g->gws_gp[0], &g->gws_gp[1], &g->gws_gp[2], &g->gws_gp[3]};
+                     &g->gws_gp[0], &g->gws_gp[1], &g->gws_gp[2], &g->gws_gp[3], &g->gws_dqkv, &g->gws_att_stats};
     for (float **p : all) { (void)hipFree(*p); *p = nullptr; }
     g->gws_chunk = 0;
     GL_HIP(gl_device_alloc(g->ctx, (void **)&g->gws_y, (size_t)want * IMG * 4));
@@ -223,6 +237,10 @@ int ensure_grad_workspace(gl_dcgan *g, int64_t n)
         GL_HIP(gl_device_alloc(g->ctx, (void **)&g->gws_da[l], (size_t)want * hw * g->cout[l] * 4));
         GL_HIP(gl_device_alloc(g->ctx, (void **)&g->gws_gp[l], (size_t)want * hw * g->cout[l] * 4));
         hw *= 4;
+    }
+    if (g->have_att) {
+        GL_HIP(gl_device_alloc(g->ctx, (void **)&g->gws_dqkv, (size_t)want * 256 * gl_attention_grad_cols(g->cout[2]) * 4));
+        GL_HIP(gl_device_alloc(g->ctx, (void **)&g->gws_att_stats, (size_t)want * 3 * 256 * 4));
     }
     g->gws_chunk = want;
     return GL_OK;
@@ -281,6 +299,21 @@ int backward_pass(gl_dcgan *g, int64_t m, const float *y, const float *cot, cons
                 const int rc = gl_launch_gather_conv(ctx, p, 1);
                 if (rc != GL_OK) return rc;
             }
+        if (l == 3 && g->have_att) {
+            // layer 3 read the attention block's output: gws_da[2] is dY.  dX = dY + [dq | dk | dv | 0] x [Wq; Wk; Wv], in place
+            const int C = g->cout[2], K = gl_attention_grad_cols(C);
+            int rc = gl_launch_attention_grad(ctx, C, g->ws_qkv, g->gws_da[2], g->att_gamma, m, g->gws_dqkv, g->gws_att_stats);
+            if (rc != GL_OK) return rc;
+            GlGatherConv p = {};
+            p.in = g->gws_dqkv; p.positions = m * 256; p.H = 16; p.W = 16; p.Cin = K;
+            p.wpack = g->gw_att; p.cols = C; p.cols_pad = (int)gl_ceil_div(C, 128) * 128; p.ntaps = 1;
+            p.tap_dy[0] = 1; p.tap_dx[0] = 1;
+            p.out = g->gws_da[2]; p.Ho = 16; p.Wo = 16; p.omul = 1;
+            p.scale = g->ident_scale; p.shift = g->ident_shift; p.cmod = 1; p.act = 0; p.zero = ctx->zero_page;
+            p.residual = g->gws_da[2];
+            rc = gl_launch_gather_conv(ctx, p, 1);
+            if (rc != GL_OK) return rc;
+        }
         hw /= 2;
     }
     // layer 0: gpre_0 rows [m][16 C1] x gw[0]^T -> grad_z [m][z_dim].  K = 16 C1 is by far the longest sum of the path (16 384 terms at
@@ -344,7 +377,9 @@ int grad_enter(gl_dcgan *g, int64_t n, const char *who, bool *run)
     if (!g->have_bias) { gl_set_error("%s: gen.4.bias not loaded", who); return GL_ERR_STATE; }
     bool sn = false;
     for (int l = 0; l < 4; ++l) sn |= g->have_sn[l];
-    if (g->have_att || sn) {
+    // with the spectral-norm state held (gl_dcgan_set_spectral_hold) g->scale[l] carries bn_scale / sigma and G is a fixed function of z; a state that
+    // every forward advances is not, and that includes the plain VAEGAN stack (attention comes with spectral normalisation there)
+    if ((g->have_att || sn) && !g->sn_hold) {
         gl_set_error("%s: generators with self-attention or spectral normalisation (VAEGAN) have no backward pass", who);
         return GL_ERR_STATE;
     }

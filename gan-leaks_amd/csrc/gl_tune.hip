@@ -514,3 +514,64 @@ extern "C" int gl_tune_attention(gl_ctx *ctx, GlTuneAttention *q)
     cleanup();
     return GL_OK;
 }
+
+// gl_tune_attention_grad: ONE launch sequence of the attention backward (gl_launch_attention_grad, csrc/gl_attention_grad.hip: the row kernel, then the
+// column kernel) on plain host arrays, for tests/test_gpu_attention_grad.py.  qkv fp32 [n_img][256][2 C / 8 + C] and dY fp32 [n_img][256][C] each sit
+// between 4 KiB guards of `poison`; dqkv [n_img][256][cols] (cols = 2 C / 8 + C rounded up to a multiple of 32: the zero columns of the projection
+// GEMM come back as well) and stats [n_img][3][256] (m, 1 / l, D) are pre-filled with `sentinel` and sit between 4 KiB sentinel guards, which come back.
+struct GlTuneAttentionGrad {             // mirrored field by field in tests/attention_grad_common.py
+    int32_t C, cols;                     // cols <- the row length of dqkv
+    int64_t n_img;
+    float gamma, poison;
+    int32_t sentinel, reserved_i;
+    const float *qkv, *dY;
+    float *dqkv;                         // <- n_img * 256 * cols floats
+    float *stats;                        // <- n_img * 3 * 256 floats
+    void *out_guards;                    // <- 4 * 4096 bytes: below | above dqkv, below | above stats
+};
+
+int gl_attention_grad_cols(int C);                                                                                                      // gl_attention_grad.hip
+int gl_launch_attention_grad(gl_ctx *ctx, int C, const float *qkv, const float *dY, float gamma, int64_t images, float *dqkv, float *stats);
+
+extern "C" int gl_tune_attention_grad(gl_ctx *ctx, GlTuneAttentionGrad *q)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx && q && q->qkv && q->dY && q->dqkv && q->stats && q->out_guards, "gl_tune_attention_grad: NULL argument");
+    GL_REQUIRE((q->C == 64 || q->C == 128) && q->n_img > 0 && q->n_img <= 4096, "gl_tune_attention_grad: C must be 64 or 128, n_img in 1..4096");
+    constexpr int64_t G = 4096;
+    q->cols = gl_attention_grad_cols(q->C);
+    const int64_t in_bytes[2] = {q->n_img * 256 * (2 * (q->C / 8) + q->C) * 4, q->n_img * 256 * q->C * 4};
+    const int64_t out_bytes[2] = {q->n_img * 256 * q->cols * 4, q->n_img * 3 * 256 * 4};
+    const void *in_host[2] = {q->qkv, q->dY};
+    void *out_host[2] = {q->dqkv, q->stats};
+    char *d_in[2] = {nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (int b = 0; b < 2; ++b) { (void)hipFree(d_in[b]); (void)hipFree(d_out[b]); }
+    };
+#define TUNE_HIP(e) do { if ((e) != hipSuccess) { gl_set_error("gl_tune_attention_grad: %s failed", #e); cleanup(); return GL_ERR_HIP; } } while (0)
+#define TUNE_RC(e) do { const int rc_ = (e); if (rc_ != GL_OK) { cleanup(); return rc_; } } while (0)
+    std::vector<float> gf((size_t)(G / 4), q->poison);
+    for (int b = 0; b < 2; ++b) {
+        TUNE_HIP(hipMalloc((void **)&d_in[b], (size_t)(in_bytes[b] + 2 * G)));
+        TUNE_HIP(hipMalloc((void **)&d_out[b], (size_t)(out_bytes[b] + 2 * G)));
+        TUNE_HIP(hipMemcpy(d_in[b], gf.data(), (size_t)G, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_in[b] + G, in_host[b], (size_t)in_bytes[b], hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_in[b] + G + in_bytes[b], gf.data(), (size_t)G, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemset(d_out[b], q->sentinel & 0xFF, (size_t)(out_bytes[b] + 2 * G)));
+    }
+    TUNE_HIP(hipDeviceSynchronize());
+    TUNE_RC(gl_launch_attention_grad(ctx, q->C, reinterpret_cast<const float *>(d_in[0] + G), reinterpret_cast<const float *>(d_in[1] + G), q->gamma, q->n_img,
+                                     reinterpret_cast<float *>(d_out[0] + G), reinterpret_cast<float *>(d_out[1] + G)));
+    TUNE_HIP(hipStreamSynchronize(ctx->stream));
+    for (int b = 0; b < 2; ++b) {
+        char *og = reinterpret_cast<char *>(q->out_guards) + 2 * b * G;
+        TUNE_HIP(hipMemcpy(og, d_out[b], (size_t)G, hipMemcpyDeviceToHost));
+        TUNE_HIP(hipMemcpy(og + G, d_out[b] + G + out_bytes[b], (size_t)G, hipMemcpyDeviceToHost));
+        TUNE_HIP(hipMemcpy(out_host[b], d_out[b] + G, (size_t)out_bytes[b], hipMemcpyDeviceToHost));
+    }
+#undef TUNE_HIP
+#undef TUNE_RC
+    cleanup();
+    return GL_OK;
+}

@@ -53,7 +53,8 @@ def _check_arguments(generator, z_init, rounds, population, sigma, distance, up,
         raise TypeError("generator must provide generate_u8(z, ...) -> u8 DeviceArray")
     if getattr(generator, "power_iterations", None) is not None:
         raise NotImplementedError("VAEGAN's generator advances its spectral-norm state with every forward, so G is not a fixed function of z: "
-                                  "the result of a latent search would depend on how the candidates are blocked")
+                                  "the result of a latent search would depend on how the candidates are blocked -- hand over "
+                                  "Generator.frozen(k), the same generator with that state held")
     if int(rounds) != rounds or rounds < 0:
         raise ValueError("rounds must be an integer >= 0, got %r" % (rounds,))
     if int(population) != population or population < 1:

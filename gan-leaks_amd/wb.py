@@ -42,7 +42,8 @@ def _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, blo
         if distance != "l2-lpips":
             raise ValueError("distance must be 'l2-lpips', got %r" % (distance,))
     if getattr(generator, "power_iterations", None) is not None:
-        raise NotImplementedError("VAEGAN's generator (spectral normalisation advanced by every forward, self-attention) has no backward pass")
+        raise NotImplementedError("VAEGAN's generator (spectral normalisation advanced by every forward, self-attention) has no backward pass "
+                                  "while its state moves: hand over Generator.frozen(k), the same generator with that state held")
     if not hasattr(generator, gradient) or not hasattr(generator, "generate_u8"):
         raise NotImplementedError("%s.%s has no %s: the backward pass is built for the DCGAN / WGAN-GP generator and for PGGAN at a "
                                   "fixed depth -- hand over pggan's Generator.at(steps, alpha)"

@@ -473,6 +473,11 @@ int gl_dcgan_set_spectral_norm(gl_dcgan *g, int layer, const float *w_bar_host, 
 int gl_dcgan_get_spectral_state(gl_dcgan *g, int layer, float *u_host, float *v_host);
 /* hold != 0: forwards reuse the current u, v, sigma (re-running the SAME call, e.g. in the other arithmetic mode) */
 int gl_dcgan_set_spectral_hold(gl_dcgan *g, int hold);
+/* `times` >= 0 steps of the spectral-norm state on the device, each exactly what one gl_dcgan_forward does before its first layer (the same
+ * kernels through the same function), held or not.  A generator loaded with another's weights and current u, v, advanced k times and then
+ * held for good is a FIXED function of z, equal bit for bit to that generator's k-th next forward in both precisions: what the
+ * partial-black-box and the white-box attack search (gan_models/vaegan/train.py Generator.frozen).  GL_ERR_STATE before the weights are loaded. */
+int gl_dcgan_advance_spectral(gl_dcgan *g, int times);
 int gl_dcgan_set_attention(gl_dcgan *g, const float *wq_host, const float *bq_host, const float *wk_host, const float *bk_host, const float *wv_host,
                            const float *bv_host, float gamma);
 /* The generator's gradient with respect to its latent input (the white-box attack's hot path, csrc/gl_dcgan_grad.hip).  Both calls run
@@ -481,8 +486,13 @@ int gl_dcgan_set_attention(gl_dcgan *g, const float *wq_host, const float *bq_ho
  * weights (the data gradient of ConvTranspose2d(k4 s2 p1)), then one GEMM to z_dim columns.  All products are fp32; every output element is
  * one fixed-order sum (no atomics, no split K), so the gradient row of an image does not depend on which images share the call or the pass.
  * Passes honour gl_dcgan_set_chunk and the 3 GiB-per-tensor cap.  The transposed weight packs and the gradient workspaces are allocated on
- * the first gradient call, not before; precision, fuse_tail and chunk are left as found.  Generators with self-attention or spectral
- * normalisation (VAEGAN) are refused with GL_ERR_STATE.  n = 0 returns GL_OK; on the context's stream, no synchronisation. */
+ * the first gradient call, not before; precision, fuse_tail and chunk are left as found.  n = 0 returns GL_OK; on the context's stream, no
+ * synchronisation.
+ * Generators with self-attention or spectral normalisation (VAEGAN) are differentiated exactly when their spectral-norm state is held
+ * (gl_dcgan_set_spectral_hold): the epilogue scale of a layer is then the constant bn_scale / sigma, and the attention block between layers 2 and 3
+ * goes backwards through csrc/gl_attention_grad.hip -- P rebuilt from the forward's q, k rows with the forward's instructions, all products on
+ * the fp32 matrix cores, fixed-order in-wave sums, the 1x1 convolutions as one GEMM added to dY in place; the biases and gamma get no gradient.
+ * While every forward advances the state, G is no fixed function of z and both calls return GL_ERR_STATE. */
 /* vector-Jacobian product: grad_z[n][z_dim] = (dG/dz)^T cot, cot [n][3][64][64] fp32 (NCHW, 16-byte aligned).  out_f32_dev (may be NULL;
  * 16-byte aligned) receives G(z) of the fp32-product forward: the values gl_dcgan_forward gives under precision 0 */
 int gl_dcgan_vjp_z(gl_dcgan *g, const float *z_dev, int64_t n, const float *cot_dev, float *grad_z_dev, float *out_f32_dev);

@@ -111,6 +111,10 @@ SIGNATURES = {
     "gl_pbb_accept": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p]),
     "gl_wb_adam_step": (_i, [_p, _p, _p, _p, _p, _i64, _i64] + [ctypes.c_float] * 7),
     "gl_wb_diag_keys": (_i, [_p, _p, _i64, _i64, _p]),
+    "gl_wb_lbfgs_push": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64]),
+    "gl_wb_lbfgs_direction": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, _p]),
+    "gl_wb_lbfgs_candidates": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, _p]),
+    "gl_wb_lbfgs_advance": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64]),
     "gl_dcgan_create": (_i, [_p, _i, _i, _i, _pp]),
     "gl_dcgan_destroy": (_i, [_p]),
     "gl_dcgan_set_conv_weight": (_i, [_p, _i, _p]),

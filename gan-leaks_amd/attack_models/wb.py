@@ -8,6 +8,7 @@ so that eval_roc.py scores the result unchanged.  The search is ganleaks_amd.wb.
 
     python -m ganleaks_amd.attack_models.wb --local_config config_attack_fbb.yaml --gan {dcgan,wgangp} --generator_path generator.pth
            [--nz --ngf] [--noise_path npz | --num_init N --init_seed s] [--steps --lr --beta1 --beta2] [--BATCH_SIZE]
+           [--optimizer {adam,lbfgs} [--memory m --ladder L --step0 s]]
     python -m ganleaks_amd.attack_models.wb ... --gan pggan --pg_steps N [--alpha a] [--in_channels C] --nz Z --resolution R ...
     python -m ganleaks_amd.attack_models.wb ... --gan vaegan --sn_forwards K [--nz Z --ngf d]
     python -m ganleaks_amd.attack_models.wb ... --pair_distance l2-lpips
@@ -23,6 +24,10 @@ so that eval_roc.py scores the result unchanged.  The search is ganleaks_amd.wb.
 --num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
 --BATCH_SIZE             only the first (N // BATCH_SIZE) * BATCH_SIZE latents take part in the start, as in fbb.py:77
 --steps, --lr, --beta1, --beta2   the descent (ganleaks_amd.wb.wb_attack)
+--optimizer              adam (the default) or lbfgs, the paper's optimiser: L-BFGS over the last --memory pairs (default 8, 1..16), every step
+                         scoring a ladder of --ladder step widths (default 8, 1..32) in one batched forward; a steepest-descent step first tries
+                         length --step0 (default 1) in latent space.  --steps counts gradient evaluations under both; --lr, --beta1, --beta2
+                         are not used by lbfgs, and --memory, --ladder, --step0 belong to it
 --pair_distance l2-lpips (default absent) the same attack under 0.2 * LPIPS + L2, the distance fbb.py hard-wires and the paper's white-box loss
                          (ganleaks_amd.wb.pair_wb_attack); VGG16 and lin weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH; the
                          start is the bank latent nearest under that distance; the resolution must be a multiple of 16.  {pos,neg}_key.npy
@@ -50,7 +55,8 @@ from .fbb import update_args  # noqa: F401  (the YAML overlay of the command lin
 from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, save_files
 
 # options added after params.txt got its form: an unused one leaves the file as it was before the option existed
-LATER_OPTIONS = ("pg_steps", "alpha", "in_channels", "pair_distance", "sn_forwards")
+LATER_OPTIONS = ("pg_steps", "alpha", "in_channels", "pair_distance", "sn_forwards", "optimizer", "memory", "ladder", "step0")
+LBFGS_DEFAULTS = (("memory", 8), ("ladder", 8), ("step0", 1.0))
 PGGAN_OPTIONS = LATER_OPTIONS[:3]
 
 
@@ -81,7 +87,22 @@ def parse_arguments(argv=None):
     parser.add_argument('--beta2', type=float, default=0.999)
     parser.add_argument('--pair_distance', type=str, default=None, choices=['l2-lpips'],
                         help='run the descent under 0.2 * LPIPS + L2 (weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH)')
+    parser.add_argument('--optimizer', type=str, default=None, choices=['adam', 'lbfgs'], help="adam (the default) or lbfgs, the paper's optimiser")
+    parser.add_argument('--memory', type=int, default=None, help='lbfgs: pairs kept per query (default 8, 1..16)')
+    parser.add_argument('--ladder', type=int, default=None, help='lbfgs: step widths scored per step (default 8, 1..32)')
+    parser.add_argument('--step0', type=float, default=None, help='lbfgs: length of the first steepest-descent trial in latent space (default 1)')
     return parser.parse_args(argv)
+
+
+def _optimizer_keywords(args):
+    """the optimiser's keywords for wb_attack / pair_wb_attack"""
+    if getattr(args, "optimizer", None) != "lbfgs":
+        return {}
+    kw = {"optimizer": "lbfgs"}
+    for name, default in LBFGS_DEFAULTS:
+        v = getattr(args, name, None)
+        kw[name] = default if v is None else v
+    return kw
 
 
 def _request(args):
@@ -117,6 +138,17 @@ def _request(args):
                                                                                                    args.resolution))
     elif any(v is not None for v in pg):
         raise SystemExit("--pg_steps, --alpha and --in_channels belong to --gan pggan (PGGAN), got --gan %s" % (args.gan,))
+    opt = getattr(args, "optimizer", None)
+    if opt not in (None, "adam", "lbfgs"):
+        raise SystemExit("--optimizer must be adam or lbfgs, got %r" % (opt,))
+    given = [name for name, _ in LBFGS_DEFAULTS if getattr(args, name, None) is not None]
+    if opt != "lbfgs" and given:
+        raise SystemExit("--%s belongs to --optimizer lbfgs" % given[0])
+    if opt == "lbfgs":
+        kw = _optimizer_keywords(args)
+        if not 1 <= int(kw["memory"]) <= 16 or not 1 <= int(kw["ladder"]) <= 32 or not (np.isfinite(kw["step0"]) and kw["step0"] > 0):
+            raise SystemExit("--memory must lie in 1..16, --ladder in 1..32 and --step0 be finite and positive, got %s, %s, %s"
+                             % (kw["memory"], kw["ladder"], kw["step0"]))
     if getattr(args, "generator_path", None) is None:
         raise SystemExit("--generator_path is needed: the white-box attacker holds the generator")
     if (getattr(args, "noise_path", None) is None) == (getattr(args, "num_init", None) is None):
@@ -153,6 +185,8 @@ def main(args):
     _request(args)
     assert os.path.exists(args.generator_path)
     save_dir = check_folder(os.path.join(os.getcwd(), 'wb_attack', args.exp_name))
+    for name, value in _optimizer_keywords(args).items():                             # params.txt names what the optimiser ran with
+        setattr(args, name, value)
     lines = ["%s:%s" % (key, value) for key, value in vars(args).items() if not (key in LATER_OPTIONS and value is None)]
     with open(os.path.join(save_dir, 'params.txt'), 'w') as handle:
         handle.write("".join(line + "\n" for line in lines))
@@ -180,7 +214,7 @@ def main(args):
         return _main_pair(args, save_dir, both, n_pos, gen, z_bank)
     z_init, _ = pbb_init_from_bank(both, gen, z_bank, batch_size=int(args.BATCH_SIZE))
     dist, z_star, S, trace = wb_attack(both, gen, z_init, steps=int(args.steps), lr=float(args.lr), beta1=float(args.beta1), beta2=float(args.beta2),
-                                       history=True)
+                                       history=True, **_optimizer_keywords(args))
     d = int(np.prod(both.shape[1:]))
     init = _dist32(trace[0], d, "u8")                                                 # attack()'s float32 for the starting S
     loss, init_loss, S = dist.astype(np.float64).reshape(-1, 1), init.astype(np.float64).reshape(-1, 1), S.reshape(-1, 1)
@@ -202,7 +236,7 @@ def _main_pair(args, save_dir, both, n_pos, gen, z_bank):
     assert (np.asarray(idx) < n_eff).all()
     z_init = z_bank[np.asarray(idx)]
     dist, z_star, key, trace = pair_wb_attack(both, gen, z_init, steps=int(args.steps), lr=float(args.lr), beta1=float(args.beta1),
-                                              beta2=float(args.beta2), history=True, lpips=model)
+                                              beta2=float(args.beta2), history=True, lpips=model, **_optimizer_keywords(args))
     init = trace[0].astype(np.uint32).view(np.float32)                                # attack()'s float32 for the start
     loss, init_loss, key = dist.astype(np.float64).reshape(-1, 1), init.astype(np.float64).reshape(-1, 1), key.reshape(-1, 1)
     save_files(save_dir, ['pos_loss', 'neg_loss'], [np.ascontiguousarray(loss[:n_pos]), np.ascontiguousarray(loss[n_pos:])])

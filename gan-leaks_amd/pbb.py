@@ -32,6 +32,8 @@ _f = ctypes.c_float
 
 GL_PBB_GROUP = 16            # include/ganleaks.h
 GL_PBB_PARTIAL_BYTES = 16
+POPULATION_IMAGES = 16384    # candidate images of one block of pbb_attack, and of one ladder of wb_attack(optimizer="lbfgs")
+PAIR_POPULATION_IMAGES = 4096    # the same for pair_pbb_attack and pair_wb_attack(optimizer="lbfgs"): every image also has its search row
 
 
 def _check_arguments(generator, z_init, rounds, population, sigma, distance, up, down, sigma_min, sigma_max, z_max, block_images, query_base,
@@ -81,7 +83,7 @@ def _check_arguments(generator, z_init, rounds, population, sigma, distance, up,
 
 
 def pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=0.5, seed=0, up=1.5, down=1.5 ** -0.25, sigma_min=1e-4, sigma_max=4.0,
-               z_max=4.0, block_images=16384, query_base=0, history=False, distance="l2", **generate_kwargs):
+               z_max=4.0, block_images=POPULATION_IMAGES, query_base=0, history=False, distance="l2", **generate_kwargs):
     """gradient-free latent search for every query.
 
     queries   : [Q,C,H,W] 8-bit images (u8, or floats on the lattice 2*(u/255.)-1); numpy / torch / DeviceArray
@@ -147,8 +149,56 @@ def pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=0.5, 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
 # the same search under 0.2 * LPIPS + L2, the distance fbb.py hard-wires and the loss of the paper (section 5.3)
+def _pair_blocking(fq, Q, per_block):
+    """(queries per block, queries per gl_feat_pair_dist* call) for a wish of per_block queries: K-blocked rows (images from 96 x 96) come
+    in blocks of PAIR_BLOCK = 256, and the block of pair distances M is [tile][tile * lambda]"""
+    from .wb import PAIR_BLOCK
+    if fq.blocked and per_block < Q:
+        per_block = -(-per_block // PAIR_BLOCK) * PAIR_BLOCK
+    per_block = min(per_block, Q)
+    return per_block, min(PAIR_BLOCK, per_block)
+
+
+def _pair_population_buffers(ctx, fq, per_block, lam, tile, nz, what):
+    """(cand [per_block * lam, nz] float32, M [tile, tile * lam] float32) of one block, allocated once; ValueError where the candidates' rows
+    and the block of pair distances do not fit the device.  what: the keyword that sets lam, for the message"""
+    esz = 2 if fq.role else 4
+    rows = per_block * lam
+    cap = int(ctx.lib.gl_lpips_search_rows_capacity(rows, fq.K)) if fq.role else rows
+    need, avail = cap * fq.K * esz + tile * tile * lam * 4, ctx.mem_info()[0]
+    if need > avail:
+        raise ValueError("a block of %d queries x %d candidates needs %d bytes for the candidates' rows and their pair distances; %d are "
+                         "available: lower %s or block_images" % (per_block, lam, need, avail, what))
+    return ctx.empty((rows, nz), np.float32), ctx.empty((tile, tile * lam), np.float32)
+
+
+def _pair_group_min(ctx, model, fq, lo, u8_images, lam, tile, M, fb, S_new, j_new):
+    """every query of the block that starts at query lo against its OWN lam images under 0.2 * LPIPS + L2: the images' search rows (the
+    bank's role, written into fb where given), per tile of queries one gl_feat_pair_dist* call of the tile's queries against the tile's
+    images, and gl_pbb_group_min_keys over every query's own lam columns into S_new, j_new.  u8_images [nb * lam, 3, H, W].
+    -> the rows (the first block is the largest: its rows are the buffer every later call writes into)"""
+    lib = ctx.lib
+    nb = u8_images.shape[0] // lam
+    esz = 2 if fq.role else 4
+    fb = model.features(u8_images, role=model.search_role("bank"), fmt=fq.fmt, out=fb)
+    if fb.K != fq.K or fb.fmt != fq.fmt:
+        raise ValueError("the candidates' rows and the queries' rows differ in layout")
+    for b0 in range(0, nb, tile):
+        m = min(tile, nb - b0)
+        # where the rows are stored K-blocked, tile = 256 and lo is a multiple of 256: lo + b0 and b0 * lambda are whole blocks
+        qV, qn = fq.V.ptr + (lo + b0) * fq.K * esz, fq.norms.ptr + (lo + b0) * 4
+        bV, bn = fb.V.ptr + b0 * lam * fb.K * esz, fb.norms.ptr + b0 * lam * 4
+        if fq.role:
+            check(lib.gl_feat_pair_dist_h1_scaled(ctx.handle, _p(bV), _p(bn), m * lam, _p(qV), _p(qn), m, fb.K, _f(fb.scale), _p(M.ptr), tile * lam))
+        else:
+            check(lib.gl_feat_pair_dist(ctx.handle, _p(bV), _p(bn), m * lam, _p(qV), _p(qn), m, fb.K, _p(M.ptr), tile * lam))
+        check(lib.gl_pbb_group_min_keys(ctx.handle, _p(M.ptr), m, lam, tile * lam, _p(S_new.ptr + b0 * 8), _p(j_new.ptr + b0 * 4)))
+    return fb
+
+
 def pair_pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=0.5, seed=0, up=1.5, down=1.5 ** -0.25, sigma_min=1e-4,
-                    sigma_max=4.0, z_max=4.0, block_images=4096, query_base=0, history=False, distance="l2-lpips", lpips=None, **generate_kwargs):
+                    sigma_max=4.0, z_max=4.0, block_images=PAIR_POPULATION_IMAGES, query_base=0, history=False, distance="l2-lpips", lpips=None,
+                    **generate_kwargs):
     """pbb_attack under 0.2 * LPIPS + L2: the same (1 + lambda) strategy, scored by the distance attack(distance='l2-lpips') searches.
 
     queries, generator, z_init, rounds .. z_max, seed, query_base, history, generate_kwargs: as pbb_attack; [Q,3,H,W] images, H and W
@@ -177,7 +227,7 @@ def pair_pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=
     if len(image_shape) != 3 or image_shape[0] != 3 or image_shape[1] % 16 or image_shape[2] % 16 or min(image_shape[1:]) < 16:
         raise ValueError("the l2-lpips path needs [Q,3,H,W] images with H and W multiples of 16, got %r" % (image_shape,))
     from . import lpips as _lp
-    from .wb import PAIR_BLOCK, _pair_keys
+    from .wb import _pair_keys
     ctx = generator.ctx
     lib = ctx.lib
     model = lpips if lpips is not None else _lp.default_model()
@@ -191,22 +241,10 @@ def pair_pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=
         return (dist, z_star, key_out, trace) if history else (dist, z_star, key_out)
     bank_role = model.search_role("bank")
     fq = model.features(qu8.view((Q,) + image_shape), role="query" if bank_role else None)
-    per_block = max(1, int(block_images) // lam)
-    if fq.blocked and per_block < Q:
-        per_block = -(-per_block // PAIR_BLOCK) * PAIR_BLOCK            # K-blocked rows (images from 96 x 96) come in blocks of 256
-    per_block = min(per_block, Q)
-    tile = min(PAIR_BLOCK, per_block)                    # queries per gl_feat_pair_dist* call; M is [tile][tile * lambda]
-    esz = 2 if fq.role else 4
+    per_block, tile = _pair_blocking(fq, Q, max(1, int(block_images) // lam))
     cand = fb = M = None
     if rounds:
-        rows = per_block * lam
-        cap = int(lib.gl_lpips_search_rows_capacity(rows, fq.K)) if fq.role else rows
-        need, avail = cap * fq.K * esz + tile * tile * lam * 4, ctx.mem_info()[0]
-        if need > avail:
-            raise ValueError("a block of %d queries x %d candidates needs %d bytes for the candidates' rows and their pair distances; %d are "
-                             "available: lower population or block_images" % (per_block, lam, need, avail))
-        cand = ctx.empty((rows, nz), np.float32)
-        M = ctx.empty((tile, tile * lam), np.float32)
+        cand, M = _pair_population_buffers(ctx, fq, per_block, lam, tile, nz, "population")
 
     def images(z_dev, n):
         u8 = generator.generate_u8(z_dev, **generate_kwargs)
@@ -229,20 +267,7 @@ def pair_pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=
             check(lib.gl_pbb_candidates(ctx.handle, _p(z.ptr), _p(sig.ptr), nb, nz, lam, ctypes.c_uint64(seed), ctypes.c_uint32(r), query_base + lo,
                                         _f(z_max), _p(cz.ptr)))
             # the first block is the largest: its rows are the buffer every later round and block writes into
-            fb = model.features(images(cz, nb * lam), role=bank_role, fmt=fq.fmt, out=fb)
-            if fb.K != fq.K or fb.fmt != fq.fmt:
-                raise ValueError("the candidates' rows and the queries' rows differ in layout")
-            for b0 in range(0, nb, tile):
-                m = min(tile, nb - b0)
-                # where the rows are stored K-blocked, tile = 256 and lo is a multiple of 256: lo + b0 and b0 * lambda are whole blocks
-                qV, qn = fq.V.ptr + (lo + b0) * fq.K * esz, fq.norms.ptr + (lo + b0) * 4
-                bV, bn = fb.V.ptr + b0 * lam * fb.K * esz, fb.norms.ptr + b0 * lam * 4
-                if fq.role:
-                    check(lib.gl_feat_pair_dist_h1_scaled(ctx.handle, _p(bV), _p(bn), m * lam, _p(qV), _p(qn), m, fb.K, _f(fb.scale), _p(M.ptr),
-                                                          tile * lam))
-                else:
-                    check(lib.gl_feat_pair_dist(ctx.handle, _p(bV), _p(bn), m * lam, _p(qV), _p(qn), m, fb.K, _p(M.ptr), tile * lam))
-                check(lib.gl_pbb_group_min_keys(ctx.handle, _p(M.ptr), m, lam, tile * lam, _p(S_new.ptr + b0 * 8), _p(j_new.ptr + b0 * 4)))
+            fb = _pair_group_min(ctx, model, fq, lo, images(cz, nb * lam), lam, tile, M, fb, S_new, j_new)
             check(lib.gl_pbb_accept(ctx.handle, _p(z.ptr), _p(sig.ptr), _p(S_cur.ptr), _p(cz.ptr), _p(S_new.ptr), _p(j_new.ptr), nb, nz, lam,
                                     _f(up), _f(down), _f(sigma_min), _f(sigma_max), _p(accepted.ptr)))
             if history:

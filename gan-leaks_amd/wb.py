@@ -12,6 +12,18 @@ z* = argmin_z L(x, G(z)) by gradient descent and scores the query x by L(x, G(z*
 Step 0 scores the starting point, so the score of a query never rises, S == SSD(generate_u8(z_star), query) exactly, and started from the
 nearest bank latent (pbb_init_from_bank) the attack can only lower the full-black-box answer.  The scoring forward per step is what makes
 the three attacks report the same quantity.  Every query's trajectory depends on that query alone, so results do not depend on block_images.
+
+optimizer="lbfgs" is the paper's optimiser with a parallel line search (csrc/gl_wb_lbfgs.hip).  A step, again for all queries at once:
+
+    l2_grad_z               as above
+    gl_wb_lbfgs_push        the pair (z - z_prev, g - g_prev) of a query that moved goes into its ring of `memory` pairs iff s.y > 0
+    gl_wb_lbfgs_direction   p = -H g by the two-loop recursion; -g with an empty ring or where -H g is no descent direction
+    gl_wb_lbfgs_candidates  the ladder z + (t 2^-j) p, j < `ladder`, clamped; t = 1 for a quasi-Newton step, step0 / |g| at first for -g
+    generate_u8             on all nb * ladder candidates, and gl_pbb_group_min with lambda = ladder: every query's best rung
+    gl_pbb_accept           the winner replaces the iterate where it is strictly closer: the iterate is itself the best so far
+    gl_wb_lbfgs_advance     a rejected quasi-Newton step drops the ring; steepest descent carries its width up or down the ladder
+
+The same driver (_lbfgs_block) runs both distances; what differs is the gradient and the scoring of a block of candidates.
 """
 from __future__ import annotations
 
@@ -26,6 +38,8 @@ _p = ctypes.c_void_p
 _f = ctypes.c_float
 
 GL_PBB_PARTIAL_BYTES = 16    # include/ganleaks.h
+GL_WB_LBFGS_MAX_M = 16
+GL_WB_LBFGS_MAX_LADDER = 32
 
 
 def _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, block_images, distance, gradient="l2_grad_z"):
@@ -68,8 +82,56 @@ def _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, blo
     return np.ascontiguousarray(z)
 
 
+def _check_optimizer(optimizer, memory, ladder, step0):
+    """the optimiser's keywords, refused without a GPU; -> (memory, ladder) as ints"""
+    if optimizer not in ("adam", "lbfgs"):
+        raise ValueError("optimizer must be 'adam' or 'lbfgs', got %r" % (optimizer,))
+    for name, v, hi in (("memory", memory, GL_WB_LBFGS_MAX_M), ("ladder", ladder, GL_WB_LBFGS_MAX_LADDER)):
+        if isinstance(v, bool) or int(v) != v or not 1 <= v <= hi:
+            raise ValueError("%s must be an integer in 1..%d, got %r" % (name, hi, v))
+    if not (np.isfinite(step0) and step0 > 0):
+        raise ValueError("step0 must be finite and positive, got %r" % (step0,))
+    return int(memory), int(ladder)
+
+
+def _lbfgs_block(ctx, z0, steps, memory, ladder, step0, z_max, gradient, score, record):
+    """L-BFGS with a ladder line search for one block of queries, on the device (csrc/gl_wb_lbfgs.hip, include/ganleaks.h).
+
+    z0 [nb, nz] float32 on the host; gradient(z_dev) -> the gradient at z, a DeviceArray [nb, nz]; score(latents_dev, lam, S_dev, j_dev)
+    writes every query's smallest key over its own lam consecutive latents and the rung that attains it, in the form gl_pbb_accept compares;
+    record(step, S_cur_dev) is called after the start (step 0) and after every step.  -> (z, S_cur) DeviceArrays"""
+    lib = ctx.lib
+    nb, nz = z0.shape
+    z = ctx.to_device(z0)
+    S_cur, S_new = ctx.empty((nb,), np.uint64), ctx.empty((nb,), np.uint64)
+    j_new, accepted = ctx.zeros((nb,), np.int32), ctx.zeros((nb,), np.uint8)
+    score(z, 1, S_cur, j_new)                                             # step 0: the starting point itself, straight into S_cur
+    record(0, S_cur)
+    if not steps:
+        return z, S_cur
+    z_prev, g_prev = ctx.zeros((nb, nz), np.float32), ctx.zeros((nb, nz), np.float32)
+    S_hist, Y_hist = ctx.zeros((nb, memory, nz), np.float32), ctx.zeros((nb, memory, nz), np.float32)
+    count, head, flag = ctx.zeros((nb,), np.int32), ctx.zeros((nb,), np.int32), ctx.zeros((nb,), np.uint8)
+    t = ctx.to_device(np.ones((nb,), np.float32))
+    one = ctx.to_device(np.ones((nb,), np.float32))                       # gl_pbb_accept's step width: not used here, stays 1
+    p, cand = ctx.empty((nb, nz), np.float32), ctx.empty((nb * ladder, nz), np.float32)
+    for k in range(1, steps + 1):
+        grad = gradient(z)
+        check(lib.gl_wb_lbfgs_push(ctx.handle, _p(z.ptr), _p(grad.ptr), _p(z_prev.ptr), _p(g_prev.ptr), _p(S_hist.ptr), _p(Y_hist.ptr), _p(count.ptr),
+                                   _p(head.ptr), _p(accepted.ptr), nb, nz, memory))
+        check(lib.gl_wb_lbfgs_direction(ctx.handle, _p(grad.ptr), _p(S_hist.ptr), _p(Y_hist.ptr), _p(count.ptr), _p(head.ptr), _p(t.ptr), _p(flag.ptr),
+                                        nb, nz, memory, _f(step0), _p(p.ptr)))
+        check(lib.gl_wb_lbfgs_candidates(ctx.handle, _p(z.ptr), _p(p.ptr), _p(t.ptr), nb, nz, ladder, _f(z_max), _p(cand.ptr)))
+        score(cand, ladder, S_new, j_new)
+        check(lib.gl_pbb_accept(ctx.handle, _p(z.ptr), _p(one.ptr), _p(S_cur.ptr), _p(cand.ptr), _p(S_new.ptr), _p(j_new.ptr), nb, nz, ladder,
+                                _f(1.0), _f(1.0), _f(1.0), _f(1.0), _p(accepted.ptr)))
+        check(lib.gl_wb_lbfgs_advance(ctx.handle, _p(t.ptr), _p(count.ptr), _p(head.ptr), _p(flag.ptr), _p(accepted.ptr), _p(j_new.ptr), nb, ladder))
+        record(k, S_cur)
+    return z, S_cur
+
+
 def wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.999, eps=1e-8, z_max=4.0, block_images=4096, history=False,
-              distance="l2"):
+              distance="l2", optimizer="adam", memory=8, ladder=8, step0=1.0):
     """gradient descent on the latent for every query.
 
     queries   : [Q,C,H,W] 8-bit images (u8, or floats on the lattice 2*(u/255.)-1); numpy / torch / DeviceArray; [Q,3,64,64] for DCGAN
@@ -78,9 +140,15 @@ def wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.
     z_init    : [Q, nz] or [Q, nz, 1, 1] starting latents (pbb_init_from_bank gives the nearest bank latents)
     steps, lr, beta1, beta2, eps: Adam on sum (G(z) - x)^2, float32; z_max: the iterate is clamped to [-z_max, z_max]
     block_images: queries go in blocks of that many; each block runs all its steps on the device
+    optimizer : 'adam' (the default) or 'lbfgs', the paper's optimiser: L-BFGS over the last `memory` (1..16) pairs, every step scoring a
+                ladder of `ladder` (1..32) step widths t 2^-j along its direction in one batched forward; a steepest-descent step (the first
+                one, and after a rejected step) tries length `step0` in latent space first.  steps is the number of gradient evaluations under
+                both optimisers; lr, beta1, beta2 and eps are not used by 'lbfgs', memory, ladder and step0 not by 'adam'.  A step scores
+                nb * ladder images: the block is capped at pbb.POPULATION_IMAGES // ladder queries, which does not change the results.
     returns (dist float32 [Q] -- the float32 attack() reports for the same S --, z_star float32 [Q, nz], S int64 [Q]), and with
     history=True also trace int64 [steps + 1, Q]: the best S after every step, trace[0] the starting point's."""
     z_host = _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, block_images, distance)
+    memory, ladder = _check_optimizer(optimizer, memory, ladder, step0)
     steps = int(steps)
     Q, nz = z_host.shape
     if len(queries) != Q:
@@ -103,6 +171,29 @@ def wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.
         if not isinstance(u8, DeviceArray) or u8.dtype != np.uint8 or u8.nbytes != n * d:
             raise ValueError("generate_u8 gave %s for %d latents; the queries hold %d values each" % (getattr(u8, "shape", None), n, d))
         return u8
+
+    if optimizer == "lbfgs":
+        from .pbb import GL_PBB_GROUP, POPULATION_IMAGES
+        per_block = min(per_block, max(1, POPULATION_IMAGES // ladder))
+        for lo in range(0, Q, per_block):
+            nb = min(per_block, Q - lo)
+            q_dev = qu8.view((nb, d), offset_bytes=lo * d)
+            work = ctx.empty((GL_PBB_PARTIAL_BYTES * nb * (-(-ladder // GL_PBB_GROUP)),), np.uint8)
+
+            def score(latents, lam, S, j):
+                u8 = images(latents, nb * lam)
+                check(lib.gl_pbb_group_min(ctx.handle, _p(q_dev.ptr), _p(u8.ptr), nb, lam, d, _p(S.ptr), _p(j.ptr), _p(work.ptr)))
+
+            def record(k, S):
+                if history:
+                    trace[k, lo:lo + nb] = S.numpy().astype(np.int64)
+
+            z, S_cur = _lbfgs_block(ctx, z_host[lo:lo + nb], steps, memory, ladder, step0, z_max,
+                                    lambda z_dev: generator.l2_grad_z(z_dev, q_dev.view((nb,) + image_shape))[0], score, record)
+            z_star[lo:lo + nb] = z.numpy()
+            S_out[lo:lo + nb] = S_cur.numpy().astype(np.int64)
+        dist = _dist32(S_out, d, "u8")
+        return (dist, z_star, S_out, trace) if history else (dist, z_star, S_out)
 
     for lo in range(0, Q, per_block):
         nb = min(per_block, Q - lo)
@@ -202,7 +293,7 @@ def _pair_keys(ctx, model, fq, lo, u8_images, keys):
 
 
 def pair_wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, beta2=0.999, eps=1e-8, z_max=4.0, block_images=1024, history=False,
-                   distance="l2-lpips", lpips=None):
+                   distance="l2-lpips", lpips=None, optimizer="adam", memory=8, ladder=8, step0=1.0):
     """wb_attack under 0.2 * LPIPS + L2: gradient descent on the latent for every query, scored by the distance attack(distance='l2-lpips')
     searches.
 
@@ -213,9 +304,13 @@ def pair_wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, bet
     order of the patterns is the order of the floats).  Step 0 scores the start, so a score never rises, and started from the nearest bank
     latent under l2-lpips the attack can only lower attack(distance='l2-lpips')'s answer.  block_images: queries per block (rounded up to a
     multiple of 256 for images from 96 x 96, whose search rows are stored in blocks of 256); results do not depend on it.
+    optimizer, memory, ladder, step0: as wb_attack.  With 'lbfgs' a step scores the nb * ladder candidates as pair_pbb_attack scores its
+    population (their search rows, gl_feat_pair_dist* per tile of 256 queries, gl_pbb_group_min_keys), the iterate is itself the best so
+    far, the block is capped at pbb.PAIR_POPULATION_IMAGES // ladder queries, and lr, beta1, beta2 and eps are not used.
     returns (dist float32 [Q] -- the float whose pattern is key --, z_star float32 [Q, nz], key int64 [Q]), and with history=True also
     trace int64 [steps + 1, Q]: the best key after every step, trace[0] the starting point's."""
     z_host = _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, block_images, distance, gradient="vjp_z")
+    memory, ladder = _check_optimizer(optimizer, memory, ladder, step0)
     steps = int(steps)
     Q, nz = z_host.shape
     if len(queries) != Q:
@@ -245,6 +340,33 @@ def pair_wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, bet
         if not isinstance(u8, DeviceArray) or u8.dtype != np.uint8 or u8.nbytes != n * d:
             raise ValueError("generate_u8 gave %s for %d latents; the queries hold %d values each" % (getattr(u8, "shape", None), n, d))
         return u8.view((n,) + image_shape)
+
+    if optimizer == "lbfgs" and Q:
+        from .pbb import PAIR_POPULATION_IMAGES, _pair_blocking, _pair_group_min, _pair_population_buffers
+        per_block, tile = _pair_blocking(fq, Q, min(int(block_images), max(1, PAIR_POPULATION_IMAGES // ladder)))
+        M = _pair_population_buffers(ctx, fq, per_block, ladder, tile, nz, "ladder")[1] if steps else None
+        rows = [None]                                                    # the candidates' search rows: the first block's, reused
+        for lo in range(0, Q, per_block):
+            nb = min(per_block, Q - lo)
+            q_dev = qu8.view((nb,) + image_shape, offset_bytes=lo * d)
+            ref = model.reference_rows(q_dev) if steps else None
+
+            def score(latents, lam, S, j):
+                if lam == 1:
+                    _pair_keys(ctx, model, fq, lo, images(latents, nb), S)
+                else:
+                    rows[0] = _pair_group_min(ctx, model, fq, lo, images(latents, nb * lam), lam, tile, M, rows[0], S, j)
+
+            def record(k, S):
+                if history:
+                    trace[k, lo:lo + nb] = S.numpy().astype(np.int64)
+
+            z, S_cur = _lbfgs_block(ctx, z_host[lo:lo + nb], steps, memory, ladder, step0, z_max,
+                                    lambda z_dev: pair_grad_z(generator, z_dev, q_dev, model, ref)[0], score, record)
+            z_star[lo:lo + nb] = z.numpy()
+            key_out[lo:lo + nb] = S_cur.numpy().astype(np.int64)
+        dist = key_out.astype(np.uint32).view(np.float32)
+        return (dist, z_star, key_out, trace) if history else (dist, z_star, key_out)
 
     for lo in range(0, Q, per_block):
         nb = min(per_block, Q - lo)

@@ -403,6 +403,56 @@ int gl_wb_adam_step(gl_ctx *ctx, float *z_dev, float *m_dev, float *v_dev, const
  * patterns is the order of the floats.  Asynchronous. */
 int gl_wb_diag_keys(gl_ctx *ctx, const float *M_dev, int64_t n, int64_t ld, uint64_t *keys_dev);
 
+/* ---------------------------------------------------------------- white-box attack: L-BFGS with a parallel line search
+ * The paper's optimiser (section 5.4 minimises over z with L-BFGS).  The line search is a ladder: every query scores L step widths along its
+ * direction in one batched forward, with the kernels of the partial-black-box attack.  A step, for all queries of a block:
+ *   g = the gradient at z -> gl_wb_lbfgs_push -> gl_wb_lbfgs_direction -> gl_wb_lbfgs_candidates -> the generator's 8-bit images of the
+ *   nq * L candidates -> gl_pbb_group_min (lambda = L; under 0.2 LPIPS + L2: gl_feat_pair_dist* and gl_pbb_group_min_keys) ->
+ *   gl_pbb_accept (lambda = L, its sigma a dummy) straight into z and S_cur -> gl_wb_lbfgs_advance.
+ * The iterate is itself the best so far.  Per-query state: z, z_prev, g_prev [nq][nz]; the ring S_hist, Y_hist [nq][m][nz] with count, head
+ * int32 [nq] (head: the slot the next pair goes to; the i-th newest pair sits in slot (head - 1 - i) mod m); the trial width t fp32 [nq]; a
+ * flag byte [nq].  A query whose t is 0, negative or not finite is FINISHED: all four calls leave its state alone, its direction is 0 and
+ * its candidates are copies of z (never strictly closer, so never accepted).  Start: count = head = flag = 0, t = 1 (any live value).
+ * All four run on the context's stream, do not synchronise, return GL_OK for nq == 0 without touching a pointer, read no tuning variable
+ * and use no atomics.  1 <= m <= GL_WB_LBFGS_MAX_M, 1 <= L <= GL_WB_LBFGS_MAX_LADDER, 1 <= nz < 2^31, nq < 2^31.
+ * Arithmetic: fp32, every product, sum and quotient rounded on its own (no fma, correctly rounded quotient and square root).  Every dot
+ * product a.b over nz elements has ONE order: lane l of the query's wave adds fl(a[c] b[c]) for c = l, l + 64, ... in ascending order
+ * into a sum that starts at +0, then the 64 sums go through the butterfly v = fl(v + v[lane ^ o]), o = 32, 16, 8, 4, 2, 1.  A host
+ * restatement in float32 reproduces the ring, p and t bit for bit. */
+#define GL_WB_LBFGS_MAX_M 16
+#define GL_WB_LBFGS_MAX_LADDER 32
+#define GL_WB_LBFGS_STEEPEST 1 /* flag bit: the direction of this step is -g */
+#define GL_WB_LBFGS_DROPPED 2  /* flag bit: -H g was no descent direction (g.p >= 0 or a value not finite): the ring was dropped */
+/* Where moved[q] != 0 (gl_pbb_accept's accepted[q] of the step before): s = fl(z - z_prev), y = fl(grad - g_prev); the pair goes into slot
+ * head iff s.y > 0 and fl(1 / s.y) is finite (the cautious update), head = (head + 1) mod m, count = min(count + 1, m).  Then, for every
+ * query, z_prev = z and g_prev = grad.  One wave per query. */
+int gl_wb_lbfgs_push(gl_ctx *ctx, const float *z_dev, const float *grad_dev, float *z_prev_dev, float *g_prev_dev, float *S_hist_dev, float *Y_hist_dev,
+                     int32_t *count_dev, int32_t *head_dev, const uint8_t *moved_dev, int64_t nq, int64_t nz, int64_t m);
+/* p = -H grad by the two-loop recursion over the query's count pairs; callable on its own on rings and gradients the caller uploaded.
+ *   q = grad; for i = 0 .. count-1 (newest first): rho_i = fl(1 / s_i.y_i), alpha_i = fl(rho_i (s_i.q)), q = fl(q - fl(alpha_i y_i));
+ *   r = fl(gamma q), gamma = fl(s_0.y_0 / y_0.y_0); for i = count-1 .. 0: beta = fl(rho_i (y_i.r)), r = fl(r + fl(s_i fl(alpha_i - beta)));
+ *   p = -r, flag = 0, t = 1.
+ * With count == 0: p = -grad, flag = GL_WB_LBFGS_STEEPEST.  If grad.p >= 0 or grad.p or an element of p is not finite: count = head = 0,
+ * p = -grad, flag = GL_WB_LBFGS_STEEPEST | GL_WB_LBFGS_DROPPED.  In both steepest-descent cases t stays as it is where the flag byte on
+ * entry had GL_WB_LBFGS_STEEPEST set (consecutive steepest-descent steps carry the width gl_wb_lbfgs_advance left), and is
+ * fl(step0 / fl(sqrt(grad.grad))) otherwise: a first trial of length step0 in latent space.  A zero gradient therefore finishes the query.
+ * count_dev, head_dev, t_dev, flag_dev are read and written; p_dev [nq][nz] also serves as the recursion's working vector.  step0 finite
+ * and positive.  One wave per query; the ring rows are read once per loop. */
+int gl_wb_lbfgs_direction(gl_ctx *ctx, const float *grad_dev, const float *S_hist_dev, const float *Y_hist_dev, int32_t *count_dev, int32_t *head_dev,
+                          float *t_dev, uint8_t *flag_dev, int64_t nq, int64_t nz, int64_t m, float step0, float *p_dev);
+/* out[(q * L + j) * nz + c] = clamp(fl(z[q][c] + fl(fl(t[q] 2^-j) p[q][c])), -z_max, z_max), j < L: the ladder of trial points, the per-query
+ * width read from the device array t_dev.  out_dev [nq * L][nz].  z_max finite and positive. */
+int gl_wb_lbfgs_candidates(gl_ctx *ctx, const float *z_dev, const float *p_dev, const float *t_dev, int64_t nq, int64_t nz, int64_t ladder, float z_max,
+                           float *out_dev);
+/* After gl_pbb_accept (accepted_dev, j_new_dev as it left and read them; flag_dev as gl_wb_lbfgs_direction left it):
+ *   accepted, steepest descent : t = fl(fl(2 t) 2^-j_new)      the next ladder starts one rung above the rung that won
+ *   accepted, quasi-Newton     : nothing (the next direction sets t = 1 again)
+ *   rejected, steepest descent : t = fl(t 2^-L)                the next ladder goes on below where this one ended
+ *   rejected, quasi-Newton     : count = head = 0              the ring is dropped; the next step is steepest descent at length step0
+ * A t that reaches 0 or leaves the finite range finishes the query. */
+int gl_wb_lbfgs_advance(gl_ctx *ctx, float *t_dev, int32_t *count_dev, int32_t *head_dev, const uint8_t *flag_dev, const uint8_t *accepted_dev,
+                        const int32_t *j_new_dev, int64_t nq, int64_t ladder);
+
 /* ---------------------------------------------------------------- sharded bank: the cross-GPU minimum (RCCL over xGMI) */
 /* The reference runs on one device (attack_models/fbb.py:40) and takes the minimum over the whole bank with torch.min (fbb.py:86).  With the bank
  * sharded over GPUs every rank holds keys[q] = min over ITS rows, global indices inside; the minimum over ranks of the unsigned

@@ -148,6 +148,7 @@ SIGNATURES = {
     "gl_medgan_set_decoder": (_i, [_p, _p, _p]),
     "gl_medgan_generate": (_i, [_p, _p, _i64, _p]),
     "gl_medgan_decode": (_i, [_p, _p, _i64, _p, _p]),
+    "gl_medgan_codes": (_i, [_p, _p, _p, _i64, _p]),
     "gl_lpips_create": (_i, [_p, _pp]),
     "gl_lpips_destroy": (_i, [_p]),
     "gl_lpips_set_conv": (_i, [_p, _i, _p, _p]),

@@ -72,6 +72,36 @@ def prepare_images(ctx, images):
     return out
 
 
+def prepare_table(ctx, rows):
+    """a 2-D table of whole numbers 0..255 -> u8 DeviceArray [count, F] holding the values: uint8 as it is, float rows encoded from the
+    integer lattice x == float(u); raises ValueError for anything else"""
+    shape = tuple(rows.shape) if hasattr(rows, "shape") else np.shape(rows)
+    if len(shape) != 2:
+        raise ValueError("a table generator's queries are a 2-D table [Q, F] on the integer lattice 0..255, got shape %r" % (tuple(shape),))
+    dev = _to_device_rows(ctx, rows)
+    if dev.dtype == np.uint8:
+        return dev
+    out, bad = encode_if_lattice(ctx, dev, integers=True)
+    if bad:
+        raise ValueError("%d values are not on the integer lattice 0..255" % bad)
+    return out
+
+
+def _prepare_for(generator, ctx, queries):
+    """(u8 query rows, the kind _dist32 takes) for a latent attack on `generator`: 8-bit images, or for a table generator (row_kind 'int') the
+    table's values"""
+    if getattr(generator, "row_kind", None) == "int":
+        return prepare_table(ctx, queries), "int"
+    return prepare_images(ctx, queries), "u8"
+
+
+def refuse_pair_for_tables(generator, what):
+    """the l2-lpips attacks are for images; before any GPU work"""
+    if getattr(generator, "row_kind", None) == "int":
+        raise NotImplementedError("%s runs under 0.2 * LPIPS + L2, and LPIPS is defined on images: a table generator (row_kind 'int') is "
+                                  "attacked under exact 'l2' by pbb_attack / wb_attack" % what)
+
+
 class Bank:
     """a sample bank (or query set) resident in HBM, prepared for one of the two L2 kernels.
 
@@ -190,7 +220,36 @@ class GeneratedBank:
         return len(self.z)
 
     def rows(self, lo, hi):
+        if getattr(self.generator, "row_kind", None) == "int":
+            # a table generator's bytes are the values themselves, and uint8 rows always mean image codes: its rows go to the walkers as
+            # floats on the integer lattice, which they prepare as kind 'int'
+            return self.generator.generate_rows(self.z[lo:hi], **self.kwargs)
         return self.generator.generate_u8(self.z[lo:hi], **self.kwargs)
+
+
+def _exact_chunk_row_bytes(bank, d):
+    """HBM one bank row of d values holds while a chunk of the exact-integer search is prepared: u8 codes + int8 rows; a table generator's
+    chunk arrives as float32 rows, made next to the decoded floats they are thresholded from and the two 128-wide hidden activations"""
+    if getattr(bank, "kind", None) == "generated" and getattr(bank.generator, "row_kind", None) == "int":
+        return 10 * d + 1024                 # 4 d rows + 4 d decoded + d codes + d int8 rows, 2 x 512 B hidden
+    return 2 * d
+
+
+def table_as_float_rows(ctx, rows):
+    """a 2-D table of whole numbers 0..255 for attack(): float rows as they are, uint8 holding the values decoded to float32 on the device
+    (uint8 handed to attack() itself always means image codes)"""
+    dev = prepare_table(ctx, rows) if _rows_dtype(rows) == np.uint8 else None
+    if dev is None:
+        return rows
+    out = ctx.empty(dev.shape, np.float32)
+    check(ctx.lib.gl_decode_u8_integers(ctx.handle, _p(dev.ptr), dev.shape[0] * dev.shape[1], _p(out.ptr)))
+    return out
+
+
+def _rows_dtype(rows):
+    if _is_torch(rows):
+        return np.dtype(np.uint8) if str(rows.dtype) == "torch.uint8" else None
+    return np.dtype(rows.dtype) if hasattr(rows, "dtype") else np.asarray(rows).dtype
 
 
 def _budget_bytes():
@@ -443,7 +502,7 @@ def _lattice_rows_walker(what, queries, bank, batch_size, ctx, reduce_fn, chunk_
         raise _OffLattice(unsupported + "got %r queries, %r bank" % (fq.kind, bank.kind))
     if not prepared:
         chunk_bytes = _budget_bytes() if chunk_bytes is None else int(chunk_bytes)
-        step = max(1, int(chunk_bytes // (2 * fq.d)))        # u8 codes + int8 rows
+        step = max(1, int(chunk_bytes // _exact_chunk_row_bytes(bank, fq.d)))
 
     def walk(out, new_out, dev, launch, out_per_query):
         if prepared:
@@ -1557,7 +1616,7 @@ def _attack_streamed(queries, bank, n_rows, distance, ctx, reduce_fn, model, chu
     fq = queries if isinstance(queries, Bank) else Bank.from_images(queries, ctx, keep_u8=True, norms64="auto")
     for force in ((fq.kind, "f32") if fq.kind != "f32" else ("f32",)):
         q_side = fq if fq.kind == force else fq.as_f32()
-        step = max(1, int(chunk_bytes // ((4 if force == "f32" else 2) * fq.d)))
+        step = max(1, int(chunk_bytes // (4 * fq.d if force == "f32" else _exact_chunk_row_bytes(bank, fq.d))))
         keys, ok = None, True
         for lo in range(0, n_rows, step):
             hi = min(lo + step, n_rows)

@@ -12,12 +12,19 @@ only improve on.
            [--rounds --population --sigma --seed] [--BATCH_SIZE]
     python -m ganleaks_amd.attack_models.pbb ... --gan vaegan --sn_forwards K [--nz Z --ngf d]
     python -m ganleaks_amd.attack_models.pbb ... --pair_distance l2-lpips
+    python -m ganleaks_amd.attack_models.pbb ... --gan medgan --generator_path generator.pth --autoencoder_path FILE --input_size F [--binary]
 
 --gan, --generator_path  the generator class and its state dict (what the training scripts save as generator.pth)
 --sn_forwards            VAEGAN only, no default: VAEGAN's spectral normalisation advances with every forward, so the generator searched is the one
                          its K-th forward after loading would have run, held from then on (Generator(nz, d=--ngf).frozen(K)); K >= 1,
                          --resolution 64.  Without it --gan vaegan is refused
 --nz, --ngf              DCGAN / WGAN-GP: latent length and width (features_g); --nz, --in_channels, --steps, --alpha: PGGAN
+--gan medgan             medGAN's tables: the generator is decoder(generator(z)) >= 0.5, the 0/1 rows of synthetic.npy (gan_models/medgan/train.py:
+                         306-312).  --autoencoder_path: the Autoencoder's state dict (decoder.0.{weight,bias}) or the reference's decoder.pth
+                         (0.{weight,bias}); --input_size F: the table's columns; --binary: the sigmoid decoder (default: ReLU); --nz is 128.
+                         --pos_data_dir / --neg_data_dir name 2-D .npy tables of whole numbers (bank_io.load_rows); --resolution is not
+                         consulted; the loss files hold fl32(S / F), S the number of differing columns; --pair_distance is refused (LPIPS is
+                         defined on images)
 --noise_path             the .npz the generate branches write under npz_noise/ (array `noise`): the latents of the sample bank
 --num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
 --BATCH_SIZE             only the first (N // BATCH_SIZE) * BATCH_SIZE latents take part in the start, as in fbb.py:77
@@ -50,6 +57,7 @@ from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, sa
 # options added after params.txt got its form: an unused one leaves the file as it was before the option existed
 LATER_OPTIONS = ("pair_distance",)
 VAEGAN_OPTIONS = ("sn_forwards",)        # the same: params.txt names K only where --gan vaegan gave it
+MEDGAN_OPTIONS = ("autoencoder_path", "input_size", "binary")        # and these only where --gan medgan gave them
 
 
 def parse_arguments(argv=None):
@@ -61,7 +69,7 @@ def parse_arguments(argv=None):
     parser.add_argument('--resolution', '-resolution', type=int, default=64, help='images that differ are resized to this square size')
     parser.add_argument('--BATCH_SIZE', type=int, default=30)
     parser.add_argument('--local_config', type=str, default=None)
-    parser.add_argument('--gan', type=str, default='dcgan', choices=['dcgan', 'wgangp', 'pggan', 'vaegan'], help='the generator class (vaegan: with --sn_forwards)')
+    parser.add_argument('--gan', type=str, default='dcgan', choices=['dcgan', 'wgangp', 'pggan', 'vaegan', 'medgan'], help='the generator class (vaegan: with --sn_forwards)')
     parser.add_argument('--generator_path', type=str, default=None, help="the generator's state dict (generator.pth)")
     parser.add_argument('--nz', type=int, default=None, help='length of a latent vector (default 100; 256 for pggan)')
     parser.add_argument('--ngf', type=int, default=64, help='dcgan / wgangp: width parameter of the generator (features_g)')
@@ -79,6 +87,9 @@ def parse_arguments(argv=None):
     parser.add_argument('--seed', type=int, default=0, help='seed of the search noise')
     parser.add_argument('--pair_distance', type=str, default=None, choices=['l2-lpips'],
                         help='run the search under 0.2 * LPIPS + L2 (weights from $GANLEAKS_VGG16_PATH / $GANLEAKS_LPIPS_LIN_PATH)')
+    parser.add_argument('--autoencoder_path', type=str, default=None, help="medgan: the autoencoder's state dict (decoder.0.*), or decoder.pth (0.*)")
+    parser.add_argument('--input_size', type=int, default=None, help="medgan: columns of the table")
+    parser.add_argument('--binary', action='store_const', const=True, default=None, help="medgan: the sigmoid decoder (default: ReLU)")
     return parser.parse_args(argv)
 
 
@@ -87,7 +98,7 @@ def _request(args):
     pair = getattr(args, "pair_distance", None)
     if pair not in (None, "l2-lpips"):
         raise SystemExit("--pair_distance must be l2-lpips, got %r (without it the search runs on exact l2)" % (pair,))
-    if pair is not None and int(args.resolution) % 16:
+    if pair is not None and args.gan != "medgan" and int(args.resolution) % 16:
         raise SystemExit("--pair_distance l2-lpips needs a --resolution that is a multiple of 16 (VGG16 pools four times), got %s" % (args.resolution,))
     if getattr(args, "generator_path", None) is None:
         raise SystemExit("--generator_path is needed: the partial-black-box attacker holds the generator")
@@ -97,8 +108,10 @@ def _request(args):
         raise SystemExit("--num_init must be at least 1, got %s" % (args.num_init,))
     if int(args.rounds) < 0 or int(args.population) < 1 or not (np.isfinite(args.sigma) and args.sigma > 0):
         raise SystemExit("--rounds must be >= 0, --population >= 1 and --sigma positive, got %s, %s, %s" % (args.rounds, args.population, args.sigma))
-    if args.gan not in ("dcgan", "wgangp", "pggan", "vaegan"):
-        raise SystemExit("--gan must be dcgan, wgangp, pggan or vaegan, got %r" % (args.gan,))
+    if args.gan not in ("dcgan", "wgangp", "pggan", "vaegan", "medgan"):
+        raise SystemExit("--gan must be dcgan, wgangp, pggan, vaegan or medgan, got %r" % (args.gan,))
+    if args.gan == "medgan" or any(getattr(args, name, None) is not None for name in ("autoencoder_path", "input_size", "binary")):
+        medgan_request(args)
     sn = getattr(args, "sn_forwards", None)
     if args.gan == "vaegan":
         if sn is None:
@@ -112,8 +125,42 @@ def _request(args):
         raise SystemExit("--sn_forwards belongs to --gan vaegan, got --gan %s" % (args.gan,))
 
 
+def medgan_request(args):
+    """--gan medgan and its options, before any file is read; settles --nz where it was not given"""
+    own = [name for name in MEDGAN_OPTIONS if getattr(args, name, None) is not None]
+    if args.gan != "medgan":
+        raise SystemExit("--%s belongs to --gan medgan, got --gan %s" % (own[0], args.gan))
+    if getattr(args, "autoencoder_path", None) is None:
+        raise SystemExit("--gan medgan needs --autoencoder_path: the rows are decoder(generator(z)), and the decoder belongs to the autoencoder "
+                         "(its state dict with decoder.0.{weight,bias}, or decoder.pth)")
+    if getattr(args, "input_size", None) is None or int(args.input_size) < 1:
+        raise SystemExit("--gan medgan needs --input_size F >= 1: the number of columns of the table")
+    if getattr(args, "nz", None) is None:
+        args.nz = 128
+    if int(args.nz) != 128:
+        raise SystemExit("--gan medgan has latents of length 128 (the residual generator, gan_models/medgan/model.py:49-71); --nz is %s" % (args.nz,))
+    if getattr(args, "pair_distance", None) is not None:
+        raise SystemExit("--pair_distance %s is refused for --gan medgan: LPIPS is defined on images, and medGAN's rows are a table; the "
+                         "search runs on exact l2" % (args.pair_distance,))
+
+
+def load_tables(args):
+    """--pos_data_dir and --neg_data_dir of --gan medgan: 2-D tables of --input_size columns (bank_io.load_rows)"""
+    from ..bank_io import load_rows
+    tables = []
+    for name in ("pos_data_dir", "neg_data_dir"):
+        rows = load_rows(getattr(args, name))
+        if rows.ndim != 2 or rows.shape[1] != int(args.input_size):
+            raise SystemExit("--%s: --gan medgan takes a 2-D .npy table of %d columns, got shape %r" % (name, int(args.input_size), rows.shape))
+        tables.append(rows)
+    return tables
+
+
 def load_generator(args):
     """-> (generator, generate_kwargs, nz)"""
+    if args.gan == "medgan":
+        from ..gan_models.medgan.model import load_table_generator
+        return load_table_generator(args.generator_path, args.autoencoder_path, args.input_size, bool(args.binary)), {}, 128
     import torch
     sd = torch.load(args.generator_path, map_location="cpu", weights_only=True)
     if args.gan == "pggan":
@@ -138,14 +185,19 @@ def main(args):
     _request(args)
     assert os.path.exists(args.generator_path)
     save_dir = check_folder(os.path.join(os.getcwd(), 'pbb_attack', args.exp_name))
-    lines = ["%s:%s" % (key, value) for key, value in vars(args).items() if not (key in LATER_OPTIONS + VAEGAN_OPTIONS and value is None)]
+    lines = ["%s:%s" % (key, value) for key, value in vars(args).items() if not (key in LATER_OPTIONS + VAEGAN_OPTIONS + MEDGAN_OPTIONS and value is None)]
     with open(os.path.join(save_dir, 'params.txt'), 'w') as handle:
         handle.write("".join(line + "\n" for line in lines))
     print("\n".join(lines))
 
-    resolution = args.resolution
-    pos_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.pos_data_dir, ext='png'), resolution)
-    neg_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.neg_data_dir, ext='png'), resolution)
+    kind = "u8"
+    if args.gan == "medgan":
+        kind = "int"
+        pos_query_imgs, neg_query_imgs = load_tables(args)
+    else:
+        resolution = args.resolution
+        pos_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.pos_data_dir, ext='png'), resolution)
+        neg_query_imgs = read_images_u8_nchw(get_filepaths_from_dir(args.neg_data_dir, ext='png'), resolution)
     both = np.concatenate([pos_query_imgs, neg_query_imgs])
     n_pos = len(pos_query_imgs)
 
@@ -167,7 +219,7 @@ def main(args):
     dist, z_star, S, trace = pbb_attack(both, gen, z_init, rounds=int(args.rounds), population=int(args.population), sigma=float(args.sigma),
                                         seed=int(args.seed), history=True, **kw)
     d = int(np.prod(both.shape[1:]))
-    init = _dist32(trace[0], d, "u8")                                                 # attack()'s float32 for the starting S
+    init = _dist32(trace[0], d, kind)                                                 # attack()'s float32 for the starting S
     loss, init_loss, S = dist.astype(np.float64).reshape(-1, 1), init.astype(np.float64).reshape(-1, 1), S.reshape(-1, 1)
     save_files(save_dir, ['pos_loss', 'neg_loss'], [np.ascontiguousarray(loss[:n_pos]), np.ascontiguousarray(loss[n_pos:])])
     save_files(save_dir, ['pos_z', 'neg_z'], [np.ascontiguousarray(z_star[:n_pos]), np.ascontiguousarray(z_star[n_pos:])])

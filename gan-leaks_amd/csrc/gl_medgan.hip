@@ -15,7 +15,11 @@ struct gl_medgan {
     float *w[3], *scale[3], *shift[3];
     bool have_gen, have_dec;
     int64_t ws_rows;
-    float *ws_a, *ws_b;
+    float *ws_a, *ws_b;         // ws_a: out1 of gl_medgan_generate
+    // gl_medgan_codes: the hidden rows [rows][128] of the handle in the generator's role, the decoded rows [rows][F] of the handle in the
+    // decoder's role -- one buffer per role, each with its own row count, since a handle may carry both sets of weights and take either role
+    float *ws_hidden, *ws_decoded;
+    int64_t ws_hidden_rows, ws_decoded_rows;
 };
 
 namespace {
@@ -55,6 +59,24 @@ __global__ void threshold_kernel(const float *__restrict__ x, int64_t count, flo
     for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) out[i] = x[i] >= 0.5f ? 1.0f : 0.0f;
 }
 
+__global__ void threshold_u8_kernel(const float *__restrict__ x, int64_t count, uint8_t *__restrict__ out)
+{
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += (int64_t)gridDim.x * blockDim.x) out[i] = x[i] >= 0.5f ? 1 : 0;
+}
+
+// *buf holds at least `rows` rows of `width` floats (`width` is fixed per buffer), grown as gl_medgan_generate grows its own
+int mg_grow(gl_ctx *ctx, float **buf, int64_t *have_rows, int64_t rows, int width)
+{
+    if (rows <= *have_rows) return GL_OK;
+    GL_HIP(hipStreamSynchronize(ctx->stream));
+    (void)hipFree(*buf);
+    *buf = nullptr;
+    *have_rows = 0;
+    GL_HIP(hipMalloc((void **)buf, (size_t)rows * width * 4));
+    *have_rows = rows;
+    return GL_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -71,7 +93,7 @@ int gl_medgan_create(gl_ctx *ctx, int z_dim, int hidden_size, int input_size, in
     g->ctx = ctx; g->z_dim = z_dim; g->hidden = hidden_size; g->F = input_size; g->binary = binary != 0;
     for (int l = 0; l < 3; ++l) g->w[l] = g->scale[l] = g->shift[l] = nullptr;
     g->have_gen = g->have_dec = false;
-    g->ws_rows = 0; g->ws_a = g->ws_b = nullptr;
+    g->ws_rows = g->ws_hidden_rows = g->ws_decoded_rows = 0; g->ws_a = g->ws_b = g->ws_hidden = g->ws_decoded = nullptr;
     *out = g;
     return GL_OK;
 }
@@ -82,7 +104,7 @@ int gl_medgan_destroy(gl_medgan *g)
     if (!g) return GL_OK;
     (void)hipStreamSynchronize(g->ctx->stream);
     for (int l = 0; l < 3; ++l) { (void)hipFree(g->w[l]); (void)hipFree(g->scale[l]); (void)hipFree(g->shift[l]); }
-    (void)hipFree(g->ws_a); (void)hipFree(g->ws_b);
+    (void)hipFree(g->ws_a); (void)hipFree(g->ws_b); (void)hipFree(g->ws_hidden); (void)hipFree(g->ws_decoded);
     delete g;
     return GL_OK;
 }
@@ -161,6 +183,35 @@ int gl_medgan_decode(gl_medgan *g, const float *hidden_dev, int64_t n, float *de
         GL_LAUNCH_CHECK();
     }
     return GL_OK;
+}
+
+/* the rows the generate branch writes, as bytes: codes_u8_dev [n][F] = gl_medgan_decode(dec, gl_medgan_generate(gen, z)) >= 0.5.  The layers
+ * go through gl_medgan_generate and gl_medgan_decode themselves, a block of rows at a time, so the decoded floats are theirs bit for bit */
+int gl_medgan_codes(gl_medgan *gen, gl_medgan *dec, const float *z_dev, int64_t n, uint8_t *codes_u8_dev)
+{
+    gl_make_current(gen ? gen->ctx : nullptr);
+    GL_REQUIRE(gen && dec && n >= 0, "gl_medgan_codes: bad argument");
+    GL_REQUIRE(gen->ctx == dec->ctx, "gl_medgan_codes: the generator and the autoencoder live on different contexts");
+    if (!gen->have_gen) { gl_set_error("gl_medgan_codes: generator blocks not loaded"); return GL_ERR_STATE; }
+    if (!dec->have_dec) { gl_set_error("gl_medgan_codes: decoder not loaded"); return GL_ERR_STATE; }
+    if (n == 0) return GL_OK;
+    GL_REQUIRE(z_dev && codes_u8_dev, "gl_medgan_codes: NULL device pointer");
+    constexpr int64_t BLOCK = 32768;            // rows per pass: bounds the decoded floats at 128 KiB * F
+    const int64_t rows = n < BLOCK ? n : BLOCK;
+    int rc = mg_grow(gen->ctx, &gen->ws_hidden, &gen->ws_hidden_rows, rows, 128);
+    if (rc == GL_OK) rc = mg_grow(dec->ctx, &dec->ws_decoded, &dec->ws_decoded_rows, rows, dec->F);
+    for (int64_t lo = 0; rc == GL_OK && lo < n; lo += BLOCK) {
+        const int64_t m = n - lo < BLOCK ? n - lo : BLOCK;
+        rc = gl_medgan_generate(gen, z_dev + lo * 128, m, gen->ws_hidden);
+        if (rc == GL_OK) rc = gl_medgan_decode(dec, gen->ws_hidden, m, dec->ws_decoded, nullptr);
+        if (rc != GL_OK) break;
+        const int64_t count = m * dec->F;
+        int64_t blocks = gl_ceil_div(count, 256);
+        if (blocks > 4096) blocks = 4096;
+        hipLaunchKernelGGL(threshold_u8_kernel, dim3((unsigned)blocks), dim3(256), 0, gen->ctx->stream, dec->ws_decoded, count, codes_u8_dev + lo * dec->F);
+        GL_LAUNCH_CHECK();
+    }
+    return rc;
 }
 
 }  // extern "C"

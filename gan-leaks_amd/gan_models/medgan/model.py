@@ -137,3 +137,67 @@ def generate_synthetic(generator, autoencoder, z):
     hidden = generator.forward_device(z)
     _, binr = autoencoder.decode_device(hidden, want_binary=True)
     return binr.numpy()
+
+
+def load_table_generator(generator_path, autoencoder_path, input_size, binary=False):
+    """the table_generator of two saved state dicts (the attack drivers' --gan medgan): generator.pth, and an Autoencoder's state dict
+    (decoder.0.{weight,bias}) or the reference's decoder.pth, the decoder alone (0.{weight,bias}, medgan/train.py:296)"""
+    import torch
+    gsd = torch.load(generator_path, map_location="cpu", weights_only=True)
+    asd = torch.load(autoencoder_path, map_location="cpu", weights_only=True)
+    if "decoder.0.weight" not in asd:
+        if "0.weight" not in asd or "0.bias" not in asd:
+            raise ValueError("%s holds neither decoder.0.{weight,bias} nor 0.{weight,bias}" % (autoencoder_path,))
+        asd = {"decoder.0.weight": asd["0.weight"], "decoder.0.bias": asd["0.bias"]}
+    gen, ae = Generator(128, 128), Autoencoder(int(input_size), 128, binary=bool(binary))
+    gen.load_state_dict(gsd)
+    ae.load_state_dict(asd)
+    return table_generator(gen, ae)
+
+
+class table_generator:
+    """the generator the partial-black-box attack holds (pbb_attack, pbb_init_from_bank, GeneratedBank): z -> the 0/1 rows the generate branch writes to
+    synthetic.npy, decoder(generator(z)) >= 0.5 (medgan/train.py:306-312), as a view of a loaded Generator and a loaded Autoencoder on one
+    context.  row_kind 'int': its rows are a table of whole numbers, scored by S = the number of differing columns and dist = fl32(S / F)."""
+    row_kind = "int"
+    z_dim = 128
+
+    def __init__(self, generator, autoencoder):
+        if not isinstance(generator, Generator) or not isinstance(autoencoder, Autoencoder):
+            raise TypeError("table_generator(generator, autoencoder) takes medgan's Generator and Autoencoder")
+        if not generator._loaded:
+            raise RuntimeError("Generator: load_state_dict() has not been called")
+        if not autoencoder._loaded:
+            raise RuntimeError("Autoencoder: load_state_dict() has not been called")
+        if generator.ctx is not autoencoder.ctx:
+            raise ValueError("the generator and the autoencoder live on different contexts")
+        if generator.z_dim != self.z_dim or autoencoder.hidden_size != 128:
+            raise ValueError("expected z_dim == hidden_size == 128, got %d / %d" % (generator.z_dim, autoencoder.hidden_size))
+        self.generator, self.autoencoder = generator, autoencoder
+        self.ctx = generator.ctx
+        self.image_shape = (autoencoder.input_size,)
+
+    def _z_device(self, z):
+        zd = as_device(self.ctx, z, np.float32)
+        if zd.nbytes % (self.z_dim * 4) or (len(zd.shape) > 1 and zd.shape[1] != self.z_dim):
+            raise ValueError("expected z of shape [N,%d], got %s" % (self.z_dim, zd.shape))
+        return zd, zd.nbytes // (self.z_dim * 4)
+
+    def generate_u8(self, z):
+        """u8 DeviceArray [N, F] of 0 / 1: the bytes are the values themselves (not image codes)"""
+        zd, n = self._z_device(z)
+        out = self.ctx.empty((n, self.image_shape[0]), np.uint8)
+        check(self.ctx.lib.gl_medgan_codes(self.generator._handle, self.autoencoder._handle, _p(zd.ptr), n, _p(out.ptr)))
+        return out
+
+    def generate_rows(self, z):
+        """generate_synthetic without the host copy: float32 DeviceArray [N, F] of 0. / 1."""
+        zd, n = self._z_device(z)
+        hidden = self.generator.forward_device(zd.view((n, self.z_dim)))
+        return self.autoencoder.decode_device(hidden, want_binary=True)[1]
+
+    def forward(self, z):
+        """the decoded floats before the threshold, float32 DeviceArray [N, F]"""
+        zd, n = self._z_device(z)
+        hidden = self.generator.forward_device(zd.view((n, self.z_dim)))
+        return self.autoencoder.decode_device(hidden)[0]

@@ -25,7 +25,7 @@ import ctypes
 import numpy as np
 
 from ._lib import DeviceArray, check
-from .attack import GeneratedBank, _dist32, attack, prepare_images
+from .attack import GeneratedBank, _dist32, _prepare_for, attack, prepare_images, refuse_pair_for_tables, table_as_float_rows
 
 _p = ctypes.c_void_p
 _f = ctypes.c_float
@@ -88,6 +88,9 @@ def pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=0.5, 
 
     queries   : [Q,C,H,W] 8-bit images (u8, or floats on the lattice 2*(u/255.)-1); numpy / torch / DeviceArray
     generator : anything with generate_u8(z, **generate_kwargs) -> u8 DeviceArray (DCGAN / WGAN-GP / PGGAN Generator)
+                A table generator (row_kind 'int': medgan's table_generator, whose bytes are the values themselves) takes a 2-D table
+                [Q, F] of whole numbers 0..255 -- float rows on the integer lattice or uint8 holding the values; S is then the number of
+                differing columns of 0/1 rows and dist = fl32(S / F), what attack() reports for such rows
     z_init    : [Q, nz] or [Q, nz, 1, 1] starting latents (pbb_init_from_bank gives the nearest bank latents)
     rounds, population: number of rounds and candidates per query and round (lambda); sigma: the initial step width
     seed, query_base  : the noise of query q is a function of (seed, round, query_base + q, j, c): the queries of a larger set can be
@@ -104,8 +107,10 @@ def pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=0.5, 
         raise ValueError("%d queries but %d starting latents" % (len(queries), Q))
     ctx = generator.ctx
     lib = ctx.lib
-    qu8 = prepare_images(ctx, queries)                   # raises ValueError off the 8-bit lattice
+    qu8, kind = _prepare_for(generator, ctx, queries)    # raises ValueError off the 8-bit lattice (a table generator: the integer lattice)
     d = qu8.shape[1]
+    if kind == "int" and (d,) != tuple(generator.image_shape):
+        raise ValueError("the queries are rows of %d columns, the generator makes %d" % (d, generator.image_shape[0]))
     z_star = np.empty((Q, nz), np.float32)
     S_out = np.empty((Q,), np.int64)
     trace = np.empty((rounds + 1, Q), np.int64) if history else None
@@ -143,7 +148,7 @@ def pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=0.5, 
         z_star[lo:lo + nb] = z.numpy()
         S_out[lo:lo + nb] = S_cur.numpy().astype(np.int64)
         del u8
-    dist = _dist32(S_out, d, "u8")
+    dist = _dist32(S_out, d, kind)
     return (dist, z_star, S_out, trace) if history else (dist, z_star, S_out)
 
 
@@ -217,6 +222,7 @@ def pair_pbb_attack(queries, generator, z_init, rounds=32, population=64, sigma=
     round when they do not fit the device.
     returns (dist float32 [Q] -- the float whose pattern is key --, z_star float32 [Q, nz], key int64 [Q]), and with history=True also
     trace int64 [rounds + 1, Q]: the key after every round, trace[0] the starting point's."""
+    refuse_pair_for_tables(generator, "pair_pbb_attack")
     z_host = _check_arguments(generator, z_init, rounds, population, sigma, distance, up, down, sigma_min, sigma_max, z_max, block_images,
                               query_base, pair=True)
     rounds, lam, seed, query_base = int(rounds), int(population), int(seed) & 0xFFFFFFFFFFFFFFFF, int(query_base)
@@ -282,6 +288,7 @@ def pair_pbb_init_from_bank(queries, generator, z_bank, batch_size=64, lpips=Non
     """the start of pair_pbb_attack: the latent of every query's nearest bank sample under 0.2 * LPIPS + L2 -- the full-black-box answer,
     attack(queries, GeneratedBank(generator, z_bank), distance='l2-lpips', batch_size=..., lpips=...).
     -> (z_bank[idx] float32 [Q, nz], idx int64 [Q])"""
+    refuse_pair_for_tables(generator, "pair_pbb_init_from_bank")
     if type(z_bank).__module__.startswith("torch"):
         z_bank = z_bank.detach().cpu().numpy()
     z_bank = np.asarray(z_bank, np.float32)
@@ -295,5 +302,7 @@ def pbb_init_from_bank(queries, generator, z_bank, batch_size=64, **generate_kwa
     if type(z_bank).__module__.startswith("torch"):
         z_bank = z_bank.detach().cpu().numpy()
     z_bank = np.asarray(z_bank, np.float32)
+    if getattr(generator, "row_kind", None) == "int":
+        queries = table_as_float_rows(generator.ctx, queries)       # a uint8 table holds the values; attack() reads uint8 as image codes
     _, idx = attack(queries, GeneratedBank(generator, z_bank, **generate_kwargs), distance="l2", batch_size=batch_size)
     return np.ascontiguousarray(z_bank[idx].reshape(len(idx), -1)), idx

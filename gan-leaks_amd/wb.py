@@ -32,7 +32,7 @@ import ctypes
 import numpy as np
 
 from ._lib import DeviceArray, check
-from .attack import _dist32, prepare_images
+from .attack import _dist32, prepare_images, refuse_pair_for_tables
 
 _p = ctypes.c_void_p
 _f = ctypes.c_float
@@ -253,6 +253,7 @@ def pair_grad_z(generator, z, targets_u8, lpips=None, ref=None):
     -> (grad DeviceArray [n, nz], loss DeviceArray [n]), float32.  G(z) is the generator's fp32-product forward, the image gradient is
     LpipsModel.grad_image's (csrc/gl_lpips_grad.hip) and the last step the generator's own vjp_z (DCGAN / WGAN-GP, pggan's
     Generator.at(steps, alpha)).  lpips: the LpipsModel (default: lpips.default_model()); ref: its reference_rows(targets_u8)."""
+    refuse_pair_for_tables(generator, "pair_grad_z")
     from . import lpips as _lp
     from ._lib import as_device
     if not hasattr(generator, "vjp_z"):
@@ -309,6 +310,7 @@ def pair_wb_attack(queries, generator, z_init, steps=64, lr=0.05, beta1=0.9, bet
     far, the block is capped at pbb.PAIR_POPULATION_IMAGES // ladder queries, and lr, beta1, beta2 and eps are not used.
     returns (dist float32 [Q] -- the float whose pattern is key --, z_star float32 [Q, nz], key int64 [Q]), and with history=True also
     trace int64 [steps + 1, Q]: the best key after every step, trace[0] the starting point's."""
+    refuse_pair_for_tables(generator, "pair_wb_attack")
     z_host = _check_arguments(generator, z_init, steps, lr, beta1, beta2, eps, z_max, block_images, distance, gradient="vjp_z")
     memory, ladder = _check_optimizer(optimizer, memory, ladder, step0)
     steps = int(steps)

@@ -598,6 +598,11 @@ int gl_medgan_set_decoder(gl_medgan *g, const float *w_host, const float *b_host
 int gl_medgan_generate(gl_medgan *g, const float *z_dev, int64_t n, float *hidden_out_dev);
 /* Autoencoder.decode: hidden_dev [n][128] -> decoded_dev [n][input_size]; binary_dev (may be NULL) = (decoded >= 0.5), train.py:311-312 */
 int gl_medgan_decode(gl_medgan *g, const float *hidden_dev, int64_t n, float *decoded_dev, float *binary_dev);
+/* The partial-black-box attack on tables.  gen: a handle with both generator blocks loaded, dec: a handle with the decoder loaded (the same handle where it carries
+ * both), both on one context (GL_ERR_INVALID otherwise, GL_ERR_STATE for missing weights); n == 0 returns GL_OK.
+ * gl_medgan_codes: codes_u8_dev [n][input_size] = (gl_medgan_decode(dec, gl_medgan_generate(gen, z)) >= 0.5) as bytes 0 / 1 -- the rows the
+ * generate branch writes, through the forward's own launches, so bit for bit what gl_medgan_decode's binary_dev holds. */
+int gl_medgan_codes(gl_medgan *gen, gl_medgan *dec, const float *z_dev, int64_t n, uint8_t *codes_u8_dev);
 
 /* ---------------------------------------------------------------- LPIPS (0.2 * LPIPS + L2, the reference's fbb distance) */
 /* PerceptualLoss(model='net-lin', net='vgg') (attack_models/lpips_pytorch/__init__.py:9-32) -> PNetLin

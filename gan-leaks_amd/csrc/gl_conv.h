@@ -69,6 +69,9 @@ struct GlGatherConv {
     int tap_fmt;
     char *tap_pool;
     float tap_scale, tap_eps;   // V = v * (tap_scale / (sqrt(sum v^2) + tap_eps)) * coef
+#ifdef GL_TUNING
+    unsigned long long *stamps; // tuning build only: 8 cycle stamps per workgroup of a stamped launch (gl_tune_h3_stamp_begin), else nullptr
+#endif
 };
 
 // fp16 search rows (LPIPS feature rows for the nearest-neighbour search) come in two layouts, chosen by the row length alone so that writers and

@@ -18,6 +18,7 @@
 #include "gl_conv.h"
 #include "gl_conv_h3_epi.h"
 #include <cstdlib>
+#include <cstring>
 #include <type_traits>
 
 namespace {
@@ -66,10 +67,33 @@ constexpr int h3_x_rows(int htp, bool xonce) { return xonce ? 10 * 17 + 1 : htp;
 //   convolution; every wave skips (nearly) the same number per slice, so the SIMDs stay in step.  Same images per tile as the raster
 //   order, hence the same L2 footprint (the border-sorted order above lost exactly that).  Adding a zero product changes no bit: outputs are
 //   identical to the raster form's (tests/test_gpu_dcgan.py).
-template <int WC, int WP, int TC = 4, int TP = 4, bool FUSE_TAIL = false, bool UP = false, bool T4 = false, bool XONCE = false>
+// EPI16 (round 5; the 256 x 256 tile without UP): the split store as 16 bytes per lane after a lane swap (gl_conv_h3_epi.h).
+// STAMP (tuning build only; tools/stamp_conv_tile.py): wave 0 of each workgroup leaves 5 s_memtime stamps in p.stamps -- kernel entry, before the
+// input pieces of slice 0, after the K loop, after the last conversion of the epilogue, after its last store has landed (the stamped build
+// alone waits for that).  No output depends on them; the production object has no stamp.
+template <int WC, int WP, int TC = 4, int TP = 4, bool FUSE_TAIL = false, bool UP = false, bool T4 = false, bool XONCE = false, bool EPI16 = false, bool STAMP = false>
 __global__ void __launch_bounds__(64 * WC * WP, 2) gather_conv_h3_kernel(const GlGatherConv p, int m_tiles, int n_tiles, int phases)
 {
 #if __HIP_DEVICE_COMPILE__
+    static_assert(!EPI16 || (TC == 8 && !FUSE_TAIL && !UP && !XONCE), "EPI16: the 8 x 4 wave tiles, plain epilogue");
+    static_assert(!STAMP || !XONCE, "STAMP: the forms with one stage per slice");
+#ifdef GL_TUNING
+    unsigned long long stamp[5] = {0, 0, 0, 0, 0};
+    auto take_stamp = [&](int k) {
+        if constexpr (STAMP) {
+            unsigned long long t;
+            __builtin_amdgcn_sched_barrier(0);
+            asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t) :: "memory");
+            __builtin_amdgcn_sched_barrier(0);
+            stamp[k] = t;
+        }
+    };
+#define H3_STAMP(k) take_stamp(k)
+#else
+    static_assert(!STAMP, "STAMP: the tuning build only");
+#define H3_STAMP(k) ((void)0)
+#endif
+    H3_STAMP(0);
     constexpr int HTC = 16 * TC * WC, HTP = 16 * TP * WP;        // tile: channels x positions (a wave owns TC x TP tiles of 16 x 16)
     constexpr int XROWS = h3_x_rows(HTP, XONCE);
     constexpr int W_BYTES = HTC * HBK_BYTES, X_BYTES = XROWS * HBK_BYTES, BUF = W_BYTES + X_BYTES;
@@ -293,12 +317,14 @@ __global__ void __launch_bounds__(64 * WC * WP, 2) gather_conv_h3_kernel(const G
             if (++tap == 4) { tap = 0; ++cc; }
         }
     } else {
+        H3_STAMP(1);
         stage(0, smem);
         for (int kt = 0; kt < nk; ++kt) {
             __syncthreads();
             if (kt + 1 < nk) stage(kt + 1, smem + ((kt + 1) & 1) * BUF);
             compute(smem + (kt & 1) * BUF, kt);
         }
+        H3_STAMP(2);
     }
 
     // ---- epilogue.  C tile (16 x 16): column (position) = lane & 15, row (channel) = 4 * (lane >> 4) + reg.
@@ -398,9 +424,21 @@ __global__ void __launch_bounds__(64 * WC * WP, 2) gather_conv_h3_kernel(const G
                 }
         }
     } else {
-        saturated |= gl_h3::epilogue<WC, WP, TC, TP>(p, acc, c0, wc, wp_, lane, o4, smem, p.tap_V ? (p.Wo >> 4) : 0);
+        saturated |= gl_h3::epilogue<WC, WP, TC, TP, EPI16>(p, acc, c0, wc, wp_, lane, o4, smem, p.tap_V ? (p.Wo >> 4) : 0);
     }
+#ifdef GL_TUNING
+    if constexpr (STAMP) {
+        H3_STAMP(3);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        H3_STAMP(4);
+        if (tid == 0 && p.stamps) {
+#pragma unroll
+            for (int k = 0; k < 5; ++k) p.stamps[(size_t)blockIdx.x * 8 + k] = stamp[k];
+        }
+    }
+#endif
     if (__any(saturated) && lane == 0) atomicAdd(p.sat_flag, 1);
+#undef H3_STAMP
 #endif
 }
 
@@ -425,15 +463,54 @@ __global__ void __launch_bounds__(256) split_rows_kernel(const float *__restrict
 // tuning build only: how many launches took the staged-once form (tests/test_gpu_conv_xonce.py: the A/B arms really differ)
 static long long h3_xonce_launches = 0;
 extern "C" long long gl_tune_h3_xonce_launches(void) { return h3_xonce_launches; }
+// likewise for the 16-byte split stores (tests/test_gpu_conv_epilogue16.py)
+static long long h3_epi16_launches = 0;
+extern "C" long long gl_tune_h3_epi16_launches(void) { return h3_epi16_launches; }
+// Cycle stamps of the 256 x 256 tile (tools/stamp_conv_tile.py): between gl_tune_h3_stamp_begin and gl_tune_h3_stamp_end every launch of that tile
+// takes its STAMP instantiation and gets 8 words per workgroup of a buffer that nothing else reads.  gl_tune_h3_stamp_end copies the words
+// to `host` (room for the max_tiles * 8 of _begin), writes 8 numbers per stamped launch to `info` (first workgroup, workgroups, H, W, K slices,
+// T4, EPI16, 0; room for 256 launches) and returns the number of launches.
+static struct {
+    gl_ctx *ctx;                // the context that began: launches of another context are not stamped
+    unsigned long long *dev;
+    long long cap, used;
+    int n;
+    long long info[256][8];
+} h3_stamp;
+extern "C" int gl_tune_h3_stamp_begin(gl_ctx *ctx, long long max_tiles)
+{
+    GL_REQUIRE(ctx && max_tiles > 0 && !h3_stamp.dev, "gl_tune_h3_stamp_begin: bad argument, or stamping already");
+    gl_make_current(ctx);
+    GL_HIP(hipMalloc((void **)&h3_stamp.dev, (size_t)max_tiles * 64));
+    GL_HIP(hipMemsetAsync(h3_stamp.dev, 0, (size_t)max_tiles * 64, ctx->stream));
+    h3_stamp.ctx = ctx; h3_stamp.cap = max_tiles; h3_stamp.used = 0; h3_stamp.n = 0;
+    return GL_OK;
+}
+extern "C" int gl_tune_h3_stamp_end(gl_ctx *ctx, unsigned long long *host, long long *info)
+{
+    if (!ctx || !h3_stamp.dev || ctx != h3_stamp.ctx) return -1;     // the context that began
+    gl_make_current(ctx);
+    const int n = h3_stamp.n;
+    (void)hipStreamSynchronize(ctx->stream);
+    const bool ok = host && info && hipMemcpy(host, h3_stamp.dev, (size_t)h3_stamp.used * 64, hipMemcpyDeviceToHost) == hipSuccess;
+    if (ok) memcpy(info, h3_stamp.info, sizeof(long long) * 8 * (size_t)n);
+    (void)hipFree(h3_stamp.dev);
+    h3_stamp.dev = nullptr;
+    return ok ? n : -1;
+}
+constexpr bool kH3TuningBuild = true;
+#else
+constexpr bool kH3TuningBuild = false;
 #endif
 
-template <int WC, int WP, int TC = 4, int TP = 4, bool FUSE_TAIL = false, bool UP = false, bool T4 = false, bool XONCE = false>
-static int launch_h3(gl_ctx *ctx, const GlGatherConv &p, int phases)
+template <int WC, int WP, int TC = 4, int TP = 4, bool FUSE_TAIL = false, bool UP = false, bool T4 = false, bool XONCE = false, bool EPI16 = false, bool STAMP = false>
+static int launch_h3(gl_ctx *ctx, const GlGatherConv &p_in, int phases)
 {
-    if constexpr (!UP && !FUSE_TAIL && !T4) {
+    GlGatherConv p = p_in;
+    if constexpr (!UP && !FUSE_TAIL && !T4 && !EPI16 && !STAMP) {
         if (p.up) return launch_h3<WC, WP, TC, TP, FUSE_TAIL, true>(ctx, p, phases);
     }
-    if constexpr (WC == 2 && WP == 4 && TC == 8 && TP == 4 && !UP && !FUSE_TAIL && !T4) {
+    if constexpr (WC == 2 && WP == 4 && TC == 8 && TP == 4 && !UP && !FUSE_TAIL && !T4 && !EPI16 && !STAMP) {
         // a 4 x 4 input grid: the fragment-per-position row order, which skips the MFMAs of taps that fall outside the image
         const bool plain = !p.up && !p.tail_w && !p.tap_V && !p.rgb_out && p.pixnorm_act == 0.0f && !p.planar;
         if (plain && p.H == 4 && p.W == 4 && gl_tuning_int("GL_H3_T4", 1)) return launch_h3<WC, WP, TC, TP, false, false, true>(ctx, p, phases);
@@ -448,21 +525,44 @@ static int launch_h3(gl_ctx *ctx, const GlGatherConv &p, int phases)
         // from the same image)
         if (plain && near && p.H == 16 && p.W == 16 && p.positions % 256 == 0 && gl_tuning_int("GL_H3_XONCE", 1)) return launch_h3<WC, WP, TC, TP, true, false, false, true>(ctx, p, phases);
     }
+    // the 256 x 256 tile (raster and T4, not UP; every channel of a tile is real: h3_tile_choice) stores its split output 16 bytes per lane.
+    // The shipped library holds that form alone; the tuning build keeps the 8-byte stores behind GL_H3_EPI16=0.
+    constexpr bool kEpi16Tile = WC == 2 && WP == 4 && TC == 8 && TP == 4 && !UP && !FUSE_TAIL && !XONCE;
+    if constexpr (kEpi16Tile && !EPI16 && !STAMP && !kH3TuningBuild) {
+        return launch_h3<WC, WP, TC, TP, FUSE_TAIL, UP, T4, XONCE, true>(ctx, p, phases);
+    } else {
+    if constexpr (kEpi16Tile && !EPI16 && !STAMP) {
+        if (gl_tuning_int("GL_H3_EPI16", 1)) return launch_h3<WC, WP, TC, TP, FUSE_TAIL, UP, T4, XONCE, true>(ctx, p, phases);
+    }
     constexpr int HTC = 16 * TC * WC, HTP = 16 * TP * WP;
     const int64_t m_tiles = gl_ceil_div(p.positions, HTP);
     const int n_tiles = (int)gl_ceil_div(p.cols, HTC);       // weight rows are padded to cols_pad >= n_tiles * HTC
     GL_REQUIRE(m_tiles * n_tiles * phases < (1ll << 31), "gather_conv_h3: grid too large");
+#ifdef GL_TUNING
+    if constexpr (kEpi16Tile && !STAMP) {
+        if (h3_stamp.dev && h3_stamp.ctx == ctx && h3_stamp.n < 256 && h3_stamp.used + m_tiles * n_tiles * phases <= h3_stamp.cap)
+            return launch_h3<WC, WP, TC, TP, FUSE_TAIL, UP, T4, XONCE, EPI16, true>(ctx, p, phases);
+    }
+    if constexpr (STAMP) {
+        const long long wgs = m_tiles * n_tiles * phases;
+        const long long rec[8] = {h3_stamp.used, wgs, p.H, p.W, (long long)p.ntaps * p.Cin / 32, T4, EPI16, 0};
+        memcpy(h3_stamp.info[h3_stamp.n++], rec, sizeof rec);
+        p.stamps = h3_stamp.dev + h3_stamp.used * 8;
+        h3_stamp.used += wgs;
+    }
+#endif
     constexpr int lds = 2 * (HTC + h3_x_rows(HTP, XONCE)) * HBK_BYTES;
-    auto kern = gather_conv_h3_kernel<WC, WP, TC, TP, FUSE_TAIL, UP, T4, XONCE>;
+    auto kern = gather_conv_h3_kernel<WC, WP, TC, TP, FUSE_TAIL, UP, T4, XONCE, EPI16, STAMP>;
     GL_ONCE_PER_DEVICE(ctx, \
         GL_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds)););
     gl_prof_scope prof_(ctx, GL_PROF_GATHER_CONV);
 #ifdef GL_TUNING
-    if (XONCE) ++h3_xonce_launches; gl_tune_conv_form = 0x200 | (TC == 8 ? (WC == 2 ? 2 : 5) : (WC == 2 ? 0 : 1) + (FUSE_TAIL ? 3 : 0)) | (UP ? 0x10 : 0) | (T4 ? 0x20 : 0) | (XONCE ? 0x40 : 0);   // on this line: a line more would move the __LINE__ of the checks below and with it the production object
+    if (XONCE) ++h3_xonce_launches; if (EPI16) ++h3_epi16_launches; gl_tune_conv_form = 0x200 | (TC == 8 ? (WC == 2 ? 2 : 5) : (WC == 2 ? 0 : 1) + (FUSE_TAIL ? 3 : 0)) | (UP ? 0x10 : 0) | (T4 ? 0x20 : 0) | (XONCE ? 0x40 : 0);   // on this line: a line more would move the __LINE__ of the checks below and with it the production object
 #endif
     hipLaunchKernelGGL(kern, dim3((unsigned)(m_tiles * n_tiles * phases)), dim3(64 * WC * WP), lds, ctx->stream, p, (int)m_tiles, n_tiles, phases);
     GL_LAUNCH_CHECK();
     return GL_OK;
+    }
 }
 
 // which tile gl_launch_gather_conv_h3 picks: 0 = <2,2> 128 x 128, 1 = <1,4> 64 channels x 256 positions, 2 = <2,4,8,4> 256 x 256,
@@ -475,7 +575,8 @@ static int h3_tile_choice(const GlGatherConv &p, int phases)
     if (p.cols <= 64) return 1;
     // wide layers with enough work to fill the chip: 256 channels x 256 positions, 8 waves of 128 x 64 (24 LDS fragment reads per 96
     // MFMAs instead of 16 per 48, half the staging per MFMA): +7 % on the DCGAN stack (A/B on one device, profiles/r01/README.md)
-    if (p.cols % 256 == 0 && gl_ceil_div(p.positions, 256) * (p.cols / 256) * phases >= 256) return 2;
+    // (tuning build: GL_H3_TILE256=1 puts every layer with whole 256-column tiles there, so that a test can reach this tile with a few positions)
+    if (p.cols % 256 == 0 && (gl_ceil_div(p.positions, 256) * (p.cols / 256) * phases >= 256 || gl_tuning_int("GL_H3_TILE256", 0))) return 2;
     // 65..128 columns with many positions (PGGAN's 128-channel block at 128 x 128): 128 channels x 512 positions, 8 waves of 128 x 64 like the
     // wide tile's, all 160 KiB of LDS
     const int wide128 = gl_tuning_int("GL_H3_TILE128", 1);

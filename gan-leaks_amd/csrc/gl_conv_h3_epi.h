@@ -14,7 +14,13 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 // returns whether a split store of this lane had to clamp to the fp16 range.
 // pool_dj: position tile j ^ pool_dj holds the row below / above tile j's (fused tap + pool only; 0 when the caller never fuses one)
-template <int WC, int WP, int TC, int TP>
+// EPI16 (round 5; the 8 x 4 wave tiles, whose launcher guarantees that every channel of the tile is real and that nothing is fused): the split
+// store as 16 bytes per lane.  A lane holds channels 4 fk .. 4 fk + 3 of tile i and the same four of tile i + 1, 16 channels further: 8 bytes of
+// hi and 8 of lo each, and the neighbouring 8 bytes of tile i sit in the lane 16 further (fk ^ 1).  One v_permlane16_swap per dword (tile i's
+// word as the first operand, tile i + 1's as the second: odd lane rows of the first swap with even rows of the second) leaves an even-fk lane with
+// 16 contiguous bytes of tile i (its own, then its neighbour's) and an odd-fk lane with 16 of tile i + 1 (its neighbour's, then its own): half
+// the store instructions for the same bytes at the same addresses.  One pair of accumulator tiles is converted and stored at a time.
+template <int WC, int WP, int TC, int TP, bool EPI16 = false>
 __device__ __forceinline__ bool epilogue(const GlGatherConv &p, v4f (&acc)[TC][TP], int c0, int wc, int wp_, int lane, const int (&o4)[TP], char *smem,
                                          int pool_dj = 0)
 {
@@ -246,6 +252,66 @@ __device__ __forceinline__ bool epilogue(const GlGatherConv &p, v4f (&acc)[TC][T
                 if (fk == 0 && o4[j] >= 0) *reinterpret_cast<float4 *>(p.rgb_out + (int64_t)o4[j] * 4) = make_float4(out4[0], out4[1], out4[2], out4[3]);
             }
             return saturated;
+        }
+    }
+    if constexpr (EPI16) {
+        static_assert(!kFusable && TC % 2 == 0, "16-byte split stores: the 8 x 4 wave tiles, pairs of 16-channel tiles");
+        if (p.out_mode == 2) {
+            typedef unsigned v2u __attribute__((ext_vector_type(2)));
+            unsigned satbits = 0;                               // c != v kept in a vector register: a compare per value would go through scalar pairs
+            const int sub = (fk & 1) * 32 + (fk & 2) * 8;       // the lane's 16 bytes inside the 64 hi bytes of a chunk: fk 0, 2 -> 0, 16 (tile i); 1, 3 -> 32, 48 (tile i + 1)
+#pragma unroll
+            for (int i = 0; i < TC; i += 2) {
+                const int chb = c0 + wc * 16 * TC + i * 16;     // first channel of the 32-channel chunk (a multiple of 32)
+                float sc[2][4], sh[2][4];
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int ch = chb + h * 16 + 4 * fk;
+                    const int chm = ch < p.cmod ? ch : ch % p.cmod;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) { sc[h][r] = p.scale[chm + r]; sh[h][r] = p.shift[chm + r]; }
+                }
+#pragma unroll
+                for (int j = 0; j < TP; ++j) {
+                    const int o = o4[j];
+                    v2u whi[2], wlo[2];                           // [tile i, tile i + 1]: the 4 hi / 4 lo halves as two dwords
+                    unsigned diff = 0;
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        v4h hi, lo;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            const float t = fmaf(acc[i + h][j][r], sc[h][r], sh[h][r]);
+                            const float v = fmaxf(fmaxf(t, t * neg_slope), relu_floor);
+                            const float c = fminf(fmaxf(v, -65504.0f), 65504.0f);
+                            diff |= __float_as_uint(c) ^ __float_as_uint(v);     // non-zero exactly when c != v (a clamped value, or a NaN)
+                            hi[r] = (_Float16)c;
+                            lo[r] = (_Float16)__fsub_rn(c, (float)hi[r]);
+                        }
+                        whi[h] = __builtin_bit_cast(v2u, hi);
+                        wlo[h] = __builtin_bit_cast(v2u, lo);
+                    }
+                    satbits |= o >= 0 ? diff : 0u;
+                    // materialised here: left alone, hipcc gathers the whole chain of ORs at the end of the epilogue and keeps every v and c
+                    // alive until then (124 bytes of scratch, all 256 registers)
+                    asm volatile("" : "+v"(satbits));
+                    // every lane takes part in the swaps (a column's four lanes share o, but the exchange must not sit under the branch)
+#pragma unroll
+                    for (int k = 0; k < 2; ++k) {
+                        const v2u s = __builtin_amdgcn_permlane16_swap(whi[0][k], whi[1][k], false, false);
+                        whi[0][k] = s[0]; whi[1][k] = s[1];
+                        const v2u u = __builtin_amdgcn_permlane16_swap(wlo[0][k], wlo[1][k], false, false);
+                        wlo[0][k] = u[0]; wlo[1][k] = u[1];
+                    }
+                    if (o < 0) continue;
+                    // 16-byte aligned as long as p.out is (a position is cols * 4 bytes, a multiple of 1 KiB here; the generators' split
+                    // activations are allocations of their own).  A merely dword-aligned p.out would still be correct, only slower
+                    char *dst = reinterpret_cast<char *>(p.out) + (int64_t)o * p.cols * 4 + (chb >> 5) * 128 + sub;
+                    *reinterpret_cast<uint4 *>(dst) = make_uint4(whi[0][0], whi[0][1], whi[1][0], whi[1][1]);
+                    *reinterpret_cast<uint4 *>(dst + 64) = make_uint4(wlo[0][0], wlo[0][1], wlo[1][0], wlo[1][1]);
+                }
+            }
+            return satbits != 0;
         }
     }
 #pragma unroll

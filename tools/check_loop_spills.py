@@ -10,6 +10,9 @@ that the 256-channel tile never runs was added to its epilogue (round 2).  tests
                                                  the K loop, --pipelined checks the hand-placed fragment reads of a gl_pair256.h kernel.
                                                  name@opcode brackets the K loop by that opcode prefix instead of v_mfma, for a VALU kernel:
                                                  gl_l2f32.hip:l2_pairs_f32_kernelILi5E@v_fma (over-counts if the epilogue uses it too)
+    ... --registers                              a second line per kernel: its VGPR count and the bytes of scratch of the WHOLE kernel (an epilogue
+                                                 that spills shows here, not in the K-loop count); exit status 1 above 256 VGPRs
+    ... --tuning                                 compile with -DGL_TUNING: the instantiations only the tuning build holds (A/B arms, STAMP)
 """
 import os
 import re
@@ -51,6 +54,16 @@ def loop_spills(asm, needle):
     if not mfma:
         return None
     return sum(1 for i, l in enumerate(lines) if "scratch_" in l and mfma[0] < i < mfma[-1])
+
+
+def registers(asm, needle):
+    """(VGPRs, bytes of scratch) of the kernel, from its .amdhsa block"""
+    needle = needle.partition("@")[0]
+    m = re.search(r"^\s*\.amdhsa_kernel (_Z\S*%s\S*)$(.*?)^\s*\.end_amdhsa_kernel" % re.escape(needle), asm, re.M | re.S)
+    if not m:
+        return None
+    get = lambda key: int(re.search(r"\.amdhsa_%s (\d+)" % key, m.group(2)).group(1))
+    return get("next_free_vgpr"), get("private_segment_fixed_size")
 
 
 def _vregs(text):
@@ -127,6 +140,8 @@ def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--kernels", default=None, help="file:name,... -- count K-loop spills of these kernels instead of the built-in list")
     ap.add_argument("--pipelined", default=None, help="file:name,... -- check the in-flight fragment reads of these kernels instead of the built-in list")
+    ap.add_argument("--registers", action="store_true", help="also print VGPR count and scratch bytes of each kernel; fail above 256 VGPRs")
+    ap.add_argument("--tuning", action="store_true", help="compile with -DGL_TUNING")
     args = ap.parse_args(argv)
     hot, pipelined = HOT, PIPELINED
     if args.kernels is not None or args.pipelined is not None:
@@ -139,6 +154,8 @@ def main(argv=None):
         for src, needles in hot.items():
             out = os.path.join(tmp, src + ".s")
             cmd = [HIPCC, "--offload-arch=gfx950", "-O3", "-std=c++17", "-fno-gpu-rdc", "--cuda-device-only", "-S", os.path.join(CSRC, src), "-o", out]
+            if args.tuning:
+                cmd.insert(1, "-DGL_TUNING")
             subprocess.run(cmd, check=True, stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             asm = open(out).read()
             for n in needles:
@@ -146,6 +163,11 @@ def main(argv=None):
                 print("%-20s %-52s %s" % (src, n, "not found" if c is None else "%d scratch instructions inside the K loop" % c))
                 if c is None or c > 0:
                     bad += 1
+                if args.registers and c is not None:
+                    vgprs, scratch = registers(asm, n)
+                    print("%-20s %-52s %d VGPRs, %d bytes of scratch in the whole kernel" % (src, n, vgprs, scratch))
+                    if vgprs > 256:
+                        bad += 1
             for n in pipelined.get(src, []):
                 r = inflight_hazards(asm, n)
                 if r is None:

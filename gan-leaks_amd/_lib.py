@@ -115,6 +115,13 @@ SIGNATURES = {
     "gl_wb_lbfgs_direction": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, _p]),
     "gl_wb_lbfgs_candidates": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, _p]),
     "gl_wb_lbfgs_advance": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64]),
+    "gl_pbb_powell_init": (_i, [_p, _p, _p, _i64, _i64, ctypes.c_float]),
+    "gl_pbb_powell_begin": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64]),
+    "gl_pbb_powell_candidates": (_i, [_p, _p, _p, _p, _i64, _i64, _i64, _i64, ctypes.c_float, _p]),
+    "gl_pbb_powell_advance": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, _i64, _i, ctypes.c_float, ctypes.c_float]),
+    "gl_pbb_powell_extrapolate": (_i, [_p, _p, _p, _p, _i64, _i64, ctypes.c_float, _p]),
+    "gl_pbb_powell_decide": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i]),
+    "gl_pbb_powell_replace": (_i, [_p, _p, _p, _p, _p, _i64, _i64]),
     "gl_dcgan_create": (_i, [_p, _i, _i, _i, _pp]),
     "gl_dcgan_destroy": (_i, [_p]),
     "gl_dcgan_set_conv_weight": (_i, [_p, _i, _p]),

@@ -453,6 +453,63 @@ int gl_wb_lbfgs_candidates(gl_ctx *ctx, const float *z_dev, const float *p_dev, 
 int gl_wb_lbfgs_advance(gl_ctx *ctx, float *t_dev, int32_t *count_dev, int32_t *head_dev, const uint8_t *flag_dev, const uint8_t *accepted_dev,
                         const int32_t *j_new_dev, int64_t nq, int64_t ladder);
 
+/* ---------------------------------------------------------------- partial-black-box attack: Powell's method with a parallel line search
+ * The paper's optimiser (section 5.3 runs Powell's conjugate-direction method per query).  All queries of a block advance in lock-step, and
+ * every line search is a two-sided ladder: a query scores L step widths along one direction in one batched forward, with the kernels of
+ * the evolution strategy.  Per-query state, all of it on the device: z [nq][nz]; the direction rows U [nq][nz + 1][nz] fp32 (rows 0 ..
+ * nz - 1 the direction set, row nz the current sweep's displacement); the trial widths t [nq][nz + 1] fp32, one per row; z0 [nq][nz], the
+ * latent at the sweep's start; the keys S_cur, S_prev, f0, S_e uint64 [nq]; drop_best double [nq], the largest decrease on one line in
+ * this sweep, and i_best int32 [nq], the line where it happened; a flag byte [nq].  A key is what gl_pbb_accept compares: the exact integer
+ * S (kind 0), or the uint32 pattern of the float32 distance, zero-extended (kind 1).  f(key) is its conversion to double: exact for S <
+ * 2^53 and for every float32.  A sweep, for all queries of a block:
+ *   gl_pbb_powell_begin -> for line = 0 .. nz - 1 { gl_pbb_powell_candidates -> the generator's 8-bit images of the nq * L candidates ->
+ *   gl_pbb_group_min (lambda = L; under 0.2 LPIPS + L2: gl_feat_pair_dist* and gl_pbb_group_min_keys) -> gl_pbb_accept (lambda = L, its
+ *   sigma a dummy of ones, up = down = 1) straight into z and S_cur -> gl_pbb_powell_advance } -> gl_pbb_powell_extrapolate -> the key of
+ *   z_e (lambda = 1) into S_e -> gl_pbb_powell_decide -> line nz as the lines before it -> gl_pbb_powell_replace.
+ * All seven run on the context's stream, do not synchronise, return GL_OK for nq == 0 without touching a pointer, read no tuning variable,
+ * use no atomics and draw no noise: the results are a pure function of the inputs.  1 <= nz < 2^31 - 1, nq < 2^31, nq (nz + 1) nz floats
+ * addressable; L even, 2 <= L <= GL_PBB_POWELL_MAX_LADDER; 0 <= line <= nz; float arrays and int32 arrays 4-byte, uint64 and double arrays
+ * 8-byte aligned.  Arithmetic: fp32 (fp64 in the test of gl_pbb_powell_decide and for drop), every product, sum and difference rounded on
+ * its own (no fma), so a host restatement reproduces U, t, z, flag and i_best bit for bit. */
+#define GL_PBB_POWELL_MAX_LADDER 32
+/* U[q][i][c] = 1 where i == c, else 0 (row nz is 0); t[q][i] = step0 for i < nz, t[q][nz] = 0.  Nothing is uploaded.  step0 finite and
+ * positive. */
+int gl_pbb_powell_init(gl_ctx *ctx, float *U_dev, float *t_dev, int64_t nq, int64_t nz, float step0);
+/* The start of a sweep: z0 = z, f0 = S_prev = S_cur, drop_best = 0, i_best = 0. */
+int gl_pbb_powell_begin(gl_ctx *ctx, const float *z_dev, const uint64_t *S_cur_dev, float *z0_dev, uint64_t *f0_dev, uint64_t *S_prev_dev,
+                        double *drop_best_dev, int32_t *i_best_dev, int64_t nq, int64_t nz);
+/* The ladder of line `line`: rung r < L has width a = fl(w_r t[q][line]), w_r = +2^-(r >> 1) for even r and -2^-(r >> 1) for odd r (a
+ * gradient-free line search looks both ways), and
+ *   out[(q * L + r) * nz + c] = clamp(fl(z[q][c] + fl(a U[q][line][c])), -z_max, z_max).
+ * With t[q][line] == 0 every candidate equals z[q] and is never strictly closer.  gl_pbb_group_min takes ties to the smaller r: the wider
+ * step, and of two equal widths the positive one.  out_dev [nq * L][nz]; z_max finite and positive.  One thread per value. */
+int gl_pbb_powell_candidates(gl_ctx *ctx, const float *z_dev, const float *U_dev, const float *t_dev, int64_t nq, int64_t nz, int64_t line,
+                             int64_t ladder, float z_max, float *out_dev);
+/* After gl_pbb_accept (accepted_dev, j_new_dev as it left and read them; S_cur_dev as it left it), with w = t[q][line]:
+ *   accepted at rung r = j_new[q] : t[q][line] = min(t_max, fl(fl(2 w) 2^-(r >> 1)))   the next ladder starts one rung above the one that won
+ *   rejected                      : t[q][line] = max(t_min, fl(w 2^-(L / 2)))           the next ladder goes on below where this one ended
+ * and for line < nz: drop = f(S_prev) - f(S_cur), one rounded difference in double; where drop > drop_best, strictly, drop_best = drop and
+ * i_best = line; then S_prev = S_cur.  For line == nz, S_prev, drop_best and i_best are left alone.  kind: 0 or 1, how f reads a key.
+ * 0 < t_min <= t_max, both finite.  One thread per query. */
+int gl_pbb_powell_advance(gl_ctx *ctx, float *t_dev, const uint8_t *accepted_dev, const int32_t *j_new_dev, const uint64_t *S_cur_dev,
+                          uint64_t *S_prev_dev, double *drop_best_dev, int32_t *i_best_dev, int64_t nq, int64_t nz, int64_t line, int64_t ladder,
+                          int kind, float t_min, float t_max);
+/* The sweep's displacement and the extrapolated point: U[q][nz][c] = dz = fl(z[q][c] - z0[q][c]), z_e[q][c] = clamp(fl(z[q][c] + dz),
+ * -z_max, z_max).  z_e_dev [nq][nz]; the caller scores it with lambda = 1 into S_e. */
+int gl_pbb_powell_extrapolate(gl_ctx *ctx, const float *z_dev, const float *z0_dev, float *U_dev, int64_t nq, int64_t nz, float z_max, float *z_e_dev);
+/* Whether the displacement joins the direction set (Numerical Recipes' test).  With f0 = f(f0_dev[q]), fN = f(S_cur_dev[q]), fE =
+ * f(S_e_dev[q]), D = drop_best[q], in double and each operation rounded on its own in this order:
+ *   A = fl(fl(f0 - fl(2 fN)) + fE),  B = fl(fl(f0 - fN) - D),  C = fl(f0 - fE),  lhs = fl(fl(2 A) fl(B B)),  rhs = fl(D fl(C C))
+ * flag[q] = 1 iff row nz of U has an element != 0 and fE < f0 and lhs < rhs, both strictly; else 0.  Then t[q][nz] = 2 where the flag is
+ * set and 0 where it is clear, so that line nz moves only the queries whose test held.  One wave per query. */
+int gl_pbb_powell_decide(gl_ctx *ctx, const float *U_dev, float *t_dev, const uint64_t *f0_dev, const uint64_t *S_cur_dev, const uint64_t *S_e_dev,
+                         const double *drop_best_dev, uint8_t *flag_dev, int64_t nq, int64_t nz, int kind);
+/* Where flag[q] != 0: U[q][i_best] = U[q][nz - 1] and t[q][i_best] = t[q][nz - 1], then U[q][nz - 1] = U[q][nz] and t[q][nz - 1] =
+ * t[q][nz]: the direction of the largest decrease leaves, the displacement comes last, and a row and its width move together (t[q][nz] is
+ * what gl_pbb_powell_advance left after line nz).  An i_best outside 0 .. nz - 1 is clamped into it.  One wave per query, lane l owning
+ * elements l, l + 64, ... */
+int gl_pbb_powell_replace(gl_ctx *ctx, float *U_dev, float *t_dev, const uint8_t *flag_dev, const int32_t *i_best_dev, int64_t nq, int64_t nz);
+
 /* ---------------------------------------------------------------- sharded bank: the cross-GPU minimum (RCCL over xGMI) */
 /* The reference runs on one device (attack_models/fbb.py:40) and takes the minimum over the whole bank with torch.min (fbb.py:86).  With the bank
  * sharded over GPUs every rank holds keys[q] = min over ITS rows, global indices inside; the minimum over ranks of the unsigned

@@ -137,6 +137,32 @@ __global__ void __launch_bounds__(kThreads) relu_bn_grad_kernel(const float *__r
     *reinterpret_cast<float4 *>(out + dst) = o;
 }
 
+// One launch of every kernel above, with its grid and its template instance: backward_pass and the tuning build's single-launch hook
+// (gl_tune_dcgan_grad_op, at the end of this file) both go through these.
+void launch_tanh_grad(hipStream_t st, const float *y, const float *cot, const uint8_t *target, int64_t m, float *g4, float *loss)
+{
+    if (target)
+        hipLaunchKernelGGL(tanh_grad_kernel<true>, dim3((unsigned)m), dim3(kThreads), 0, st, y, (const float *)nullptr, target, g4, loss);
+    else
+        hipLaunchKernelGGL(tanh_grad_kernel<false>, dim3((unsigned)m), dim3(kThreads), 0, st, y, cot, (const uint8_t *)nullptr, g4, (float *)nullptr);
+}
+
+void launch_patch_rgb(hipStream_t st, const float *g4, int64_t m, float *patch)
+{
+    hipLaunchKernelGGL(patch_rgb_kernel, dim3((unsigned)gl_ceil_div(m * 1024 * 16, kThreads)), dim3(kThreads), 0, st, g4, m, patch);
+}
+
+// planar: the phase-planar form of layers 3, 2, 1 (kc unused); otherwise layer 0's rows in K chunks of kc floats
+void launch_relu_bn_grad(hipStream_t st, bool planar, const float *dA, const float *a, const float *scale, int64_t m, int Ho, int Wo, int C, int kc, float *out)
+{
+    const int64_t elems4 = m * Ho * Wo * (C / 4);
+    const dim3 grid((unsigned)gl_ceil_div(elems4, kThreads)), block(kThreads);
+    if (planar)
+        hipLaunchKernelGGL(relu_bn_grad_kernel<true>, grid, block, 0, st, dA, a, scale, m, Ho, Wo, C, 0, out);
+    else
+        hipLaunchKernelGGL(relu_bn_grad_kernel<false>, grid, block, 0, st, dA, a, scale, m, Ho, Wo, C, kc, out);
+}
+
 int upload_pack(gl_ctx *ctx, float **dev, const std::vector<float> &host)
 {
     (void)hipFree(*dev);
@@ -250,13 +276,9 @@ int ensure_grad_workspace(gl_dcgan *g, int64_t n)
 int backward_pass(gl_dcgan *g, int64_t m, const float *y, const float *cot, const uint8_t *target, float *grad_z, float *loss)
 {
     gl_ctx *ctx = g->ctx;
-    if (target)
-        hipLaunchKernelGGL(tanh_grad_kernel<true>, dim3((unsigned)m), dim3(kThreads), 0, ctx->stream, y, (const float *)nullptr, target, g->gws_g4, loss);
-    else
-        hipLaunchKernelGGL(tanh_grad_kernel<false>, dim3((unsigned)m), dim3(kThreads), 0, ctx->stream, y, cot, (const uint8_t *)nullptr, g->gws_g4,
-                           (float *)nullptr);
+    launch_tanh_grad(ctx->stream, y, cot, target, m, g->gws_g4, loss);
     GL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(patch_rgb_kernel, dim3((unsigned)gl_ceil_div(m * 1024 * 16, kThreads)), dim3(kThreads), 0, ctx->stream, g->gws_g4, m, g->gws_patch);
+    launch_patch_rgb(ctx->stream, g->gws_g4, m, g->gws_patch);
     GL_LAUNCH_CHECK();
     // layer 4: dA_3 [m * 32 * 32][C3] = patch [.][64] x gw[4]^T
     {
@@ -273,9 +295,7 @@ int backward_pass(gl_dcgan *g, int64_t m, const float *y, const float *cot, cons
     int hw = 16;                                             // grid of a_{l-1}
     for (int l = 3; l >= 1; --l) {
         const int Cl = g->cout[l];
-        const int64_t elems4 = m * (2 * hw) * (2 * hw) * (Cl / 4);
-        hipLaunchKernelGGL(relu_bn_grad_kernel<true>, dim3((unsigned)gl_ceil_div(elems4, kThreads)), dim3(kThreads), 0, ctx->stream, g->gws_da[l], g->ws_a[l],
-                           g->scale[l], m, 2 * hw, 2 * hw, Cl, 0, g->gws_gp[l]);
+        launch_relu_bn_grad(ctx->stream, true, g->gws_da[l], g->ws_a[l], g->scale[l], m, 2 * hw, 2 * hw, Cl, 0, g->gws_gp[l]);
         GL_LAUNCH_CHECK();
         const int K = 4 * Cl, cols_pad = (int)gl_ceil_div(g->cin[l], 128) * 128;
         for (int py = 0; py < 2; ++py)
@@ -321,8 +341,7 @@ int backward_pass(gl_dcgan *g, int64_t m, const float *y, const float *cot, cons
     // the residual, in ascending order: the rounding error of a row stays that of a kGradK0-term sum whatever the width.
     {
         const int C1 = g->cout[0], chunks = 16 * C1 / kGradK0;
-        hipLaunchKernelGGL(relu_bn_grad_kernel<false>, dim3((unsigned)gl_ceil_div(m * 16 * (C1 / 4), kThreads)), dim3(kThreads), 0, ctx->stream, g->gws_da[0],
-                           g->ws_a[0], g->scale[0], m, 4, 4, C1, kGradK0, g->gws_gp[0]);
+        launch_relu_bn_grad(ctx->stream, false, g->gws_da[0], g->ws_a[0], g->scale[0], m, 4, 4, C1, kGradK0, g->gws_gp[0]);
         GL_LAUNCH_CHECK();
         const int cols_pad = (int)gl_ceil_div(g->z_dim, 128) * 128;
         for (int ch = 0; ch < chunks; ++ch) {
@@ -423,3 +442,57 @@ int gl_dcgan_l2_grad_z(gl_dcgan *g, const float *z_dev, const uint8_t *target_u8
 }
 
 }  // extern "C"
+
+#ifdef GL_TUNING
+// One launch of one kernel of this file on device buffers that gl_tune_grad_op (gl_tune.hip) has put between guards: through the launchers
+// backward_pass uses.  ip[0] = images.  nb: the bytes of in[0 .. 3] and out[0 .. 1] (0 for a NULL slot); every buffer a kernel touches must have
+// exactly the size its shape gives.
+#define GL_TUNE_NEED(slot, bytes)                                                                                                              \
+    GL_REQUIRE(nb[slot] == (int64_t)(bytes), "%s: buffer %d (inputs 0 - 3, outputs 4 - 5) has %lld bytes, the shape needs %lld", __func__, slot, \
+               (long long)nb[slot], (long long)(bytes))
+int gl_tune_dcgan_grad_op(gl_ctx *ctx, int op, const int64_t *ip, const int64_t *nb, void *const *in, void *const *out)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t m = ip[0];
+    GL_REQUIRE(m > 0 && m <= 4096, "gl_tune_dcgan_grad_op: images in 1..4096");
+    switch (op) {
+    case 0:   // tanh_grad_kernel<false>: in = y, cot [m][3][64][64]; out = g4
+        GL_TUNE_NEED(0, m * IMG * 4);
+        GL_TUNE_NEED(1, m * IMG * 4);
+        GL_TUNE_NEED(4, m * IMG * 4);
+        launch_tanh_grad(st, (const float *)in[0], (const float *)in[1], nullptr, m, (float *)out[0], nullptr);
+        break;
+    case 1:   // tanh_grad_kernel<true>: in = y, target codes; out = g4, loss [m]
+        GL_TUNE_NEED(0, m * IMG * 4);
+        GL_TUNE_NEED(1, m * IMG);
+        GL_TUNE_NEED(4, m * IMG * 4);
+        GL_TUNE_NEED(5, m * 4);
+        launch_tanh_grad(st, (const float *)in[0], nullptr, (const uint8_t *)in[1], m, (float *)out[0], (float *)out[1]);
+        break;
+    case 2:   // patch_rgb_kernel: in = g4 [m][3][64][64]; out = patch [m][1024][64]
+        GL_TUNE_NEED(0, m * IMG * 4);
+        GL_TUNE_NEED(4, m * 1024 * 64 * 4);
+        launch_patch_rgb(st, (const float *)in[0], m, (float *)out[0]);
+        break;
+    case 3: { // relu_bn_grad_kernel<ip[4] != 0>: ip[1..3] = Ho, Wo, C, ip[5] = kc; in = dA, a [m][Ho][Wo][C], scale [C]; out = gpre
+        GL_REQUIRE(ip[1] > 0 && ip[1] <= 1024 && ip[2] > 0 && ip[2] <= 1024 && ip[3] > 0 && ip[3] <= 4096 && ip[3] % 4 == 0, "gl_tune_dcgan_grad_op: bad shape");
+        GL_REQUIRE(ip[4] ? (ip[1] % 2 == 0 && ip[2] % 2 == 0) : (ip[5] > 0 && ip[5] % 4 == 0 && (ip[1] * ip[2] * ip[3]) % ip[5] == 0),
+                   "gl_tune_dcgan_grad_op: odd grid, or kc does not divide the row");
+        const int64_t bytes = m * ip[1] * ip[2] * ip[3] * 4;
+        GL_TUNE_NEED(0, bytes);
+        GL_TUNE_NEED(1, bytes);
+        GL_TUNE_NEED(2, ip[3] * 4);
+        GL_TUNE_NEED(4, bytes);
+        launch_relu_bn_grad(st, ip[4] != 0, (const float *)in[0], (const float *)in[1], (const float *)in[2], m, (int)ip[1], (int)ip[2], (int)ip[3], (int)ip[5],
+                            (float *)out[0]);
+        break;
+    }
+    default:
+        gl_set_error("gl_tune_dcgan_grad_op: unknown op %d", op);
+        return GL_ERR_INVALID;
+    }
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+#undef GL_TUNE_NEED
+#endif

@@ -407,12 +407,68 @@ unsigned wave_blocks(int64_t positions)
     return (unsigned)(b < 1 ? 1 : (b > 16384 ? 16384 : b));
 }
 
+// One launch of every kernel above, with its grid and its template instance: the passes below and the tuning build's single-launch hook
+// (gl_tune_lpips_grad_op, at the end of this file) both go through these.
+template <typename T>
+void launch_conv1(hipStream_t st, const T *img, int64_t m, int H, int W, const float *w, const float *bias, float *out)
+{
+    hipLaunchKernelGGL(lg_conv1_kernel<T>, dim3(wave_blocks(m * H * W)), dim3(kThreads), 0, st, img, m * H * W, H, W, w, bias, out);
+}
+
+void launch_maxpool(hipStream_t st, const float *in, int64_t m, int h, int w, int C, float *out)
+{
+    const int64_t items = m * (h / 2) * (w / 2) * (C / 4);
+    int64_t blocks = gl_ceil_div(items, kThreads);
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(lg_maxpool_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, in, m, h, w, C, out);
+}
+
+void launch_ref(hipStream_t st, int C, const float *f, int64_t positions, int hw, float *ref, int64_t ref_ld, int64_t off)
+{
+    const dim3 grid(wave_blocks(positions)), block(kThreads);
+    switch (C) {
+    case 64: hipLaunchKernelGGL(lg_ref_kernel<1>, grid, block, 0, st, f, positions, hw, ref, ref_ld, off); break;
+    case 128: hipLaunchKernelGGL(lg_ref_kernel<2>, grid, block, 0, st, f, positions, hw, ref, ref_ld, off); break;
+    case 256: hipLaunchKernelGGL(lg_ref_kernel<4>, grid, block, 0, st, f, positions, hw, ref, ref_ld, off); break;
+    default: hipLaunchKernelGGL(lg_ref_kernel<8>, grid, block, 0, st, f, positions, hw, ref, ref_ld, off); break;
+    }
+}
+
+void launch_act_grad(hipStream_t st, int C, const float *a, const float *D, int mode, int64_t m, int h, int w, const float *ref, int64_t ref_ld, int64_t ref_off,
+                     const float *lin, float *part, int64_t part_ld, int64_t part_off, float *out)
+{
+    const int64_t positions = m * h * w;
+    const float coef = (float)(0.4 / ((double)h * w));
+    const dim3 grid(wave_blocks(positions)), block(kThreads);
+#define GL_ACT_GRAD(J) hipLaunchKernelGGL(lg_act_grad_kernel<J>, grid, block, 0, st, a, D, mode, positions, h, w, ref, ref_ld, ref_off, lin, coef, part, part_ld, \
+                                          part_off, out)
+    switch (C) {
+    case 64: GL_ACT_GRAD(1); break;
+    case 128: GL_ACT_GRAD(2); break;
+    case 256: GL_ACT_GRAD(4); break;
+    default: GL_ACT_GRAD(8); break;
+    }
+#undef GL_ACT_GRAD
+}
+
+void launch_conv1_grad(hipStream_t st, const float *gpre, const float *w, const float *y, const uint8_t *target, int64_t m, int H, int W, float *cot)
+{
+    const int64_t D = 3ll * H * W;
+    hipLaunchKernelGGL(lg_conv1_grad_kernel<uint8_t>, dim3(wave_blocks(m * H * W)), dim3(kThreads), 0, st, gpre, w, y, target, m * H * W, H, W,
+                       (float)(2.0 / (double)D), cot);
+}
+
+void launch_loss(hipStream_t st, const float *part, int64_t part_ld, const TapGeom &tap, const float *y, const uint8_t *target, int64_t m, int64_t D, float *loss)
+{
+    hipLaunchKernelGGL(lg_loss_kernel<uint8_t>, dim3((unsigned)m), dim3(kThreads), 0, st, part, part_ld, tap, y, target, D, loss);
+}
+
 // the keep-mode forward of m images: keep[ci] = relu(conv_ci), keep_pool[k] = the max-pool after taps 0 .. 3
 template <typename T>
 int forward_keep(gl_lpips *l, const T *img, int64_t m, int H, int W, const Geom &g)
 {
     gl_ctx *ctx = l->ctx;
-    hipLaunchKernelGGL(lg_conv1_kernel<T>, dim3(wave_blocks(m * H * W)), dim3(kThreads), 0, ctx->stream, img, m * H * W, H, W, l->gw[0], l->bias[0], l->keep[0]);
+    launch_conv1<T>(ctx->stream, img, m, H, W, l->gw[0], l->bias[0], l->keep[0]);
     GL_LAUNCH_CHECK();
     const float *cur = l->keep[0];
     int pool = 0;
@@ -430,10 +486,7 @@ int forward_keep(gl_lpips *l, const T *img, int64_t m, int H, int W, const Geom 
         if (rc != GL_OK) return rc;
         cur = l->keep[ci];
         if (kAfter[ci] == 2) {
-            const int64_t items = m * (h / 2) * (w / 2) * (kCout[ci] / 4);
-            int64_t blocks = gl_ceil_div(items, kThreads);
-            if (blocks > 4096) blocks = 4096;
-            hipLaunchKernelGGL(lg_maxpool_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, cur, m, h, w, kCout[ci], l->keep_pool[pool]);
+            launch_maxpool(ctx->stream, cur, m, h, w, kCout[ci], l->keep_pool[pool]);
             GL_LAUNCH_CHECK();
             cur = l->keep_pool[pool++];
         }
@@ -449,14 +502,7 @@ int ref_rows(gl_lpips *l, int64_t m, const Geom &g, float *ref)
     for (int ci = 0; ci < kLpNumConv; ++ci) {
         if (!kAfter[ci]) continue;
         const int hw = g.h[ci] * g.w[ci];
-        const int64_t positions = m * hw;
-        const dim3 grid(wave_blocks(positions)), block(kThreads);
-        switch (kCout[ci]) {
-        case 64: hipLaunchKernelGGL(lg_ref_kernel<1>, grid, block, 0, st, l->keep[ci], positions, hw, ref, g.ref_dim, g.ref_off[t]); break;
-        case 128: hipLaunchKernelGGL(lg_ref_kernel<2>, grid, block, 0, st, l->keep[ci], positions, hw, ref, g.ref_dim, g.ref_off[t]); break;
-        case 256: hipLaunchKernelGGL(lg_ref_kernel<4>, grid, block, 0, st, l->keep[ci], positions, hw, ref, g.ref_dim, g.ref_off[t]); break;
-        default: hipLaunchKernelGGL(lg_ref_kernel<8>, grid, block, 0, st, l->keep[ci], positions, hw, ref, g.ref_dim, g.ref_off[t]); break;
-        }
+        launch_ref(st, kCout[ci], l->keep[ci], m * hw, hw, ref, g.ref_dim, g.ref_off[t]);
         GL_LAUNCH_CHECK();
         ++t;
     }
@@ -493,23 +539,12 @@ int backward_pass(gl_lpips *l, int64_t m, int H, int W, const Geom &g, const flo
     int t = kLpTaps - 1, lin_off = 64 + 128 + 256 + 512;
     for (int ci = kLpNumConv - 1; ci >= 0; --ci) {
         const int h = g.h[ci], w = g.w[ci], C = kCout[ci];
-        const int64_t positions = m * h * w;
         const int mode = ci == kLpNumConv - 1 ? 0 : (kAfter[ci] == 2 ? 2 : 1);
         const bool tap = kAfter[ci] != 0;
         const float *rp = tap ? ref : nullptr;
         const int64_t ro = tap ? g.ref_off[t] : 0, po = tap ? g.tap.off[t] : 0;
         const float *lin = l->g_lin + (tap ? lin_off : 0);
-        const float coef = (float)(0.4 / ((double)h * w));
-        const dim3 grid(wave_blocks(positions)), block(kThreads);
-#define GL_ACT_GRAD(J) hipLaunchKernelGGL(lg_act_grad_kernel<J>, grid, block, 0, st, l->keep[ci], A, mode, positions, h, w, rp, g.ref_dim, ro, lin, coef, \
-                                          l->g_part, g.part_dim, po, B)
-        switch (C) {
-        case 64: GL_ACT_GRAD(1); break;
-        case 128: GL_ACT_GRAD(2); break;
-        case 256: GL_ACT_GRAD(4); break;
-        default: GL_ACT_GRAD(8); break;
-        }
-#undef GL_ACT_GRAD
+        launch_act_grad(st, C, l->keep[ci], A, mode, m, h, w, rp, g.ref_dim, ro, lin, l->g_part, g.part_dim, po, B);
         GL_LAUNCH_CHECK();
         if (tap) { --t; if (t >= 0) lin_off -= kTapC[t]; }
         if (ci == 0) break;
@@ -517,10 +552,9 @@ int backward_pass(gl_lpips *l, int64_t m, int H, int W, const Geom &g, const flo
         if (rc != GL_OK) return rc;
     }
     const int64_t D = 3ll * H * W;
-    hipLaunchKernelGGL(lg_conv1_grad_kernel<uint8_t>, dim3(wave_blocks(m * H * W)), dim3(kThreads), 0, st, B, l->gw[0], y, target, m * H * W, H, W,
-                       (float)(2.0 / (double)D), cot);
+    launch_conv1_grad(st, B, l->gw[0], y, target, m, H, W, cot);
     GL_LAUNCH_CHECK();
-    hipLaunchKernelGGL(lg_loss_kernel<uint8_t>, dim3((unsigned)m), dim3(kThreads), 0, st, l->g_part, g.part_dim, g.tap, y, target, D, loss);
+    launch_loss(st, l->g_part, g.part_dim, g.tap, y, target, m, D, loss);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }
@@ -607,3 +641,94 @@ int gl_lpips_grad_image(gl_lpips *l, const float *y_f32_dev, const uint8_t *targ
 }
 
 }  // extern "C"
+
+#ifdef GL_TUNING
+// One launch of one kernel of this file on device buffers that gl_tune_grad_op (gl_tune.hip) has put between guards: through the launchers the
+// passes use.  ip: the integer arguments in the order given per op; a NULL in[] slot reaches the kernel as NULL (D without mode, ref without a tap).
+// nb: the bytes of in[0 .. 3] and out[0 .. 1] (0 for a NULL slot); every buffer a kernel touches must have exactly the size its shape gives.
+#define GL_TUNE_NEED(slot, bytes)                                                                                                              \
+    GL_REQUIRE(nb[slot] == (int64_t)(bytes), "%s: buffer %d (inputs 0 - 3, outputs 4 - 5) has %lld bytes, the shape needs %lld", __func__, slot, \
+               (long long)nb[slot], (long long)(bytes))
+int gl_tune_lpips_grad_op(gl_ctx *ctx, int op, const int64_t *ip, const int64_t *nb, void *const *in, void *const *out)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t m = ip[0];
+    const int H = (int)ip[1], W = (int)ip[2], C = (int)ip[3];
+    GL_REQUIRE(m > 0 && m <= 4096 && ip[1] > 0 && ip[1] <= (1 << 20) && ip[2] > 0 && ip[2] <= (1 << 20) && ip[3] >= 0 && ip[3] <= 512,
+               "gl_tune_lpips_grad_op: bad shape");
+    const int64_t hw = (int64_t)H * W;
+    const bool jwidth = C == 64 || C == 128 || C == 256 || C == 512;
+    switch (op) {
+    case 0:   // lg_conv1_kernel<float>: in = img [m][3][H][W], w [64][3][3][3], bias [64]; out = [m H W][64]
+    case 1:   // lg_conv1_kernel<uint8_t>
+        GL_TUNE_NEED(0, m * 3 * hw * (op == 0 ? 4 : 1));
+        GL_TUNE_NEED(1, 64 * 27 * 4);
+        GL_TUNE_NEED(2, 64 * 4);
+        GL_TUNE_NEED(4, m * hw * 64 * 4);
+        if (op == 0) launch_conv1<float>(st, (const float *)in[0], m, H, W, (const float *)in[1], (const float *)in[2], (float *)out[0]);
+        else launch_conv1<uint8_t>(st, (const uint8_t *)in[0], m, H, W, (const float *)in[1], (const float *)in[2], (float *)out[0]);
+        break;
+    case 2:   // lg_maxpool_kernel: in = [m][H][W][C]; out = [m][H/2][W/2][C]
+        GL_REQUIRE(H % 2 == 0 && W % 2 == 0 && C > 0 && C % 4 == 0, "gl_tune_lpips_grad_op: max-pool needs even H, W and C %% 4 == 0");
+        GL_TUNE_NEED(0, m * hw * C * 4);
+        GL_TUNE_NEED(4, m * (hw / 4) * C * 4);
+        launch_maxpool(st, (const float *)in[0], m, H, W, C, (float *)out[0]);
+        break;
+    case 3:   // lg_ref_kernel<C / 64>: in = f [m H W][C]; out = ref [m][ip[4]] written from ip[5] on
+        GL_REQUIRE(jwidth, "gl_tune_lpips_grad_op: C must be 64, 128, 256 or 512");
+        GL_REQUIRE(ip[5] >= 0 && ip[5] + hw * C <= ip[4], "gl_tune_lpips_grad_op: reference rows too short");
+        GL_TUNE_NEED(0, m * hw * C * 4);
+        GL_TUNE_NEED(4, m * ip[4] * 4);
+        launch_ref(st, C, (const float *)in[0], m * hw, (int)hw, (float *)out[0], ip[4], ip[5]);
+        break;
+    case 4: { // lg_act_grad_kernel<C / 64>: in = a, D, ref [m][ip[5]] (tap values from ip[6] on), lin [C]; out = gpre chunks, part [m][ip[7]] (from ip[8] on)
+        const int mode = (int)ip[4];
+        GL_REQUIRE(jwidth, "gl_tune_lpips_grad_op: C must be 64, 128, 256 or 512");
+        GL_REQUIRE(mode >= 0 && mode <= 2 && (mode != 2 || (H % 2 == 0 && W % 2 == 0)), "gl_tune_lpips_grad_op: bad mode");
+        GL_TUNE_NEED(0, m * hw * C * 4);
+        GL_TUNE_NEED(1, mode == 0 ? 0 : (mode == 1 ? m * hw * C * 4 : m * (hw / 4) * C * 4));
+        GL_TUNE_NEED(4, m * hw * C * 4);
+        if (in[2]) {
+            GL_REQUIRE(ip[6] >= 0 && ip[6] + hw * C <= ip[5] && ip[8] >= 0 && ip[8] + hw <= ip[7], "gl_tune_lpips_grad_op: tap rows too short");
+            GL_TUNE_NEED(2, m * ip[5] * 4);
+            GL_TUNE_NEED(3, C * 4);
+            GL_TUNE_NEED(5, m * ip[7] * 4);
+        }
+        launch_act_grad(st, C, (const float *)in[0], (const float *)in[1], mode, m, H, W, (const float *)in[2], ip[5], ip[6], (const float *)in[3],
+                        (float *)out[1], ip[7], ip[8], (float *)out[0]);
+        break;
+    }
+    case 5:   // lg_conv1_grad_kernel<uint8_t>: in = gpre [m H W][64], w [64][3][3][3], y [m][3][H][W], target codes; out = cot [m][3][H][W]
+        GL_TUNE_NEED(0, m * hw * 64 * 4);
+        GL_TUNE_NEED(1, 64 * 27 * 4);
+        GL_TUNE_NEED(2, m * 3 * hw * 4);
+        GL_TUNE_NEED(3, m * 3 * hw);
+        GL_TUNE_NEED(4, m * 3 * hw * 4);
+        launch_conv1_grad(st, (const float *)in[0], (const float *)in[1], (const float *)in[2], (const uint8_t *)in[3], m, H, W, (float *)out[0]);
+        break;
+    case 6: { // lg_loss_kernel<uint8_t>: ip[1] = values per image, ip[2] = part_ld, ip[4 + t] = hw of tap t (offsets: their running sum);
+              // in = part [m][part_ld], y [m][ip[1]], target codes; out = loss [m]
+        TapGeom tg = {};
+        int64_t off = 0;
+        for (int t = 0; t < kLpTaps; ++t) {
+            GL_REQUIRE(ip[4 + t] > 0 && ip[4 + t] <= (1 << 24), "gl_tune_lpips_grad_op: bad tap size");
+            tg.off[t] = off; tg.hw[t] = (int)ip[4 + t];
+            off += ip[4 + t];
+        }
+        GL_REQUIRE(off <= ip[2], "gl_tune_lpips_grad_op: part rows too short");
+        GL_TUNE_NEED(0, m * ip[2] * 4);
+        GL_TUNE_NEED(1, m * ip[1] * 4);
+        GL_TUNE_NEED(2, m * ip[1]);
+        GL_TUNE_NEED(4, m * 4);
+        launch_loss(st, (const float *)in[0], ip[2], tg, (const float *)in[1], (const uint8_t *)in[2], m, ip[1], (float *)out[0]);
+        break;
+    }
+    default:
+        gl_set_error("gl_tune_lpips_grad_op: unknown op %d", op);
+        return GL_ERR_INVALID;
+    }
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+#undef GL_TUNE_NEED
+#endif

@@ -171,6 +171,42 @@ __global__ void __launch_bounds__(kThreads) pg_rowpn_grad_kernel(const float *__
     for (int c = lane; c < d; c += 64) gp[c] = __fmul_rn(inv, __fsub_rn(gp[c], __fmul_rn(__fmul_rn(src[c], inv), mean)));
 }
 
+// One launch of every kernel above, with its grid and its template instance: backward_pass and the tuning build's single-launch hook
+// (gl_tune_pggan_grad_op, at the end of this file) both go through these.
+void launch_out_grad(hipStream_t st, const float *y, const float *cot, const uint8_t *target, int64_t m, int img, int use_tanh, float *gout, float *loss)
+{
+    if (target)
+        hipLaunchKernelGGL(pg_out_grad_kernel<true>, dim3((unsigned)m), dim3(kThreads), 0, st, y, (const float *)nullptr, target, img, use_tanh, gout, loss);
+    else
+        hipLaunchKernelGGL(pg_out_grad_kernel<false>, dim3((unsigned)m), dim3(kThreads), 0, st, y, cot, (const uint8_t *)nullptr, img, use_tanh, gout,
+                           (float *)nullptr);
+}
+
+// H: the grid of dA (half the image's with `pool`)
+void launch_rgb_grad(hipStream_t st, const float *gout, const float *w, int64_t m, int H, int C, int nc, int pool, float factor, float *dA)
+{
+    const int64_t total = m * H * H * C;
+    hipLaunchKernelGGL(pg_rgb_grad_kernel, dim3((unsigned)gl_ceil_div(total, kThreads)), dim3(kThreads), 0, st, gout, w, total, H, C, nc, pool, factor, dA);
+}
+
+void launch_pn_grad(hipStream_t st, const float *dA, const float *a, const float *inv, const float *extra, int64_t m, int H, int C, int pool, float *out)
+{
+    const int64_t positions = m * H * H;
+    int64_t blocks = gl_ceil_div(positions, 4);
+    if (blocks > 16384) blocks = 16384;
+    hipLaunchKernelGGL(pg_pn_grad_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, st, dA, a, inv, extra, positions, H, C, pool, out);
+}
+
+void launch_leaky_grad(hipStream_t st, const float *dA, const float *h, int64_t m, int K, float *out)
+{
+    hipLaunchKernelGGL(pg_leaky_grad_kernel, dim3((unsigned)gl_ceil_div(m * K, kThreads)), dim3(kThreads), 0, st, dA, h, m, K, out);
+}
+
+void launch_rowpn_grad(hipStream_t st, const float *z, int64_t m, int d, float *grad)
+{
+    hipLaunchKernelGGL(pg_rowpn_grad_kernel, dim3((unsigned)gl_ceil_div(m, 4)), dim3(kThreads), 0, st, z, m, d, grad);
+}
+
 int upload_pack(gl_ctx *ctx, float **dev, const std::vector<float> &host)
 {
     (void)hipFree(*dev);
@@ -315,37 +351,24 @@ int backward_pass(gl_pggan *g, int64_t m, int steps, float alpha, const float *z
 {
     gl_ctx *ctx = g->ctx;
     const int R = 4 << steps, nc = g->nc, top = 1 + 2 * steps, img = nc * R * R;
-    if (target)
-        hipLaunchKernelGGL(pg_out_grad_kernel<true>, dim3((unsigned)m), dim3(kThreads), 0, ctx->stream, y, (const float *)nullptr, target, img, steps > 0 ? 1 : 0,
-                           g->gws_g, loss);
-    else
-        hipLaunchKernelGGL(pg_out_grad_kernel<false>, dim3((unsigned)m), dim3(kThreads), 0, ctx->stream, y, cot, (const uint8_t *)nullptr, img, steps > 0 ? 1 : 0,
-                           g->gws_g, (float *)nullptr);
+    launch_out_grad(ctx->stream, y, cot, target, m, img, steps > 0 ? 1 : 0, g->gws_g, loss);
     GL_LAUNCH_CHECK();
     float *A = g->gws_roll[0], *B = g->gws_roll[1], *E = nullptr;
     {
         const Layer L = layer_of(g, top);
-        const int64_t total = m * R * R * L.C;
-        hipLaunchKernelGGL(pg_rgb_grad_kernel, dim3((unsigned)gl_ceil_div(total, kThreads)), dim3(kThreads), 0, ctx->stream, g->gws_g, g->w_rgb[steps], total, R,
-                           L.C, nc, 0, steps > 0 ? alpha : 1.0f, A);
+        launch_rgb_grad(ctx->stream, g->gws_g, g->w_rgb[steps], m, R, L.C, nc, 0, steps > 0 ? alpha : 1.0f, A);
         GL_LAUNCH_CHECK();
     }
     if (steps > 0 && alpha != 1.0f) {
         const Layer L = layer_of(g, top - 2);
-        const int64_t total = m * (R / 2) * (R / 2) * L.C;
         E = g->gws_roll[2];
-        hipLaunchKernelGGL(pg_rgb_grad_kernel, dim3((unsigned)gl_ceil_div(total, kThreads)), dim3(kThreads), 0, ctx->stream, g->gws_g, g->w_rgb[steps - 1], total,
-                           R / 2, L.C, nc, 1, 1.0f - alpha, E);
+        launch_rgb_grad(ctx->stream, g->gws_g, g->w_rgb[steps - 1], m, R / 2, L.C, nc, 1, 1.0f - alpha, E);
         GL_LAUNCH_CHECK();
     }
     bool pooled = false;      // A holds the gradient on the 2x grid of the layer that takes it next
     for (int l = top; l >= 1; --l) {
         const Layer L = layer_of(g, l);
-        const int64_t positions = m * L.hw * L.hw;
-        int64_t blocks = gl_ceil_div(positions, 4);
-        if (blocks > 16384) blocks = 16384;
-        hipLaunchKernelGGL(pg_pn_grad_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, A, g->keep_act[l], g->keep_inv[l],
-                           l == top - 2 ? E : (const float *)nullptr, positions, L.hw, L.C, pooled ? 1 : 0, B);
+        launch_pn_grad(ctx->stream, A, g->keep_act[l], g->keep_inv[l], l == top - 2 ? E : (const float *)nullptr, m, L.hw, L.C, pooled ? 1 : 0, B);
         GL_LAUNCH_CHECK();
         const int rc = conv_bwd(g, l, m, B, A);
         if (rc != GL_OK) return rc;
@@ -355,7 +378,7 @@ int backward_pass(gl_pggan *g, int64_t m, int steps, float alpha, const float *z
     // kGradK0 terms added through the residual, in ascending order
     {
         const int K = 16 * g->C, chunks = (int)gl_ceil_div(K, kGradK0);
-        hipLaunchKernelGGL(pg_leaky_grad_kernel, dim3((unsigned)gl_ceil_div(m * K, kThreads)), dim3(kThreads), 0, ctx->stream, A, g->keep_act[0], m, K, B);
+        launch_leaky_grad(ctx->stream, A, g->keep_act[0], m, K, B);
         GL_LAUNCH_CHECK();
         const int cols_pad = (int)gl_ceil_div(g->z_dim, 128) * 128;
         for (int ch = 0; ch < chunks; ++ch) {
@@ -370,7 +393,7 @@ int backward_pass(gl_pggan *g, int64_t m, int steps, float alpha, const float *z
             const int rc = gl_launch_gather_conv(ctx, p, 1);
             if (rc != GL_OK) return rc;
         }
-        hipLaunchKernelGGL(pg_rowpn_grad_kernel, dim3((unsigned)gl_ceil_div(m, 4)), dim3(kThreads), 0, ctx->stream, z, m, g->z_dim, grad_z);
+        launch_rowpn_grad(ctx->stream, z, m, g->z_dim, grad_z);
         GL_LAUNCH_CHECK();
     }
     return GL_OK;
@@ -450,3 +473,76 @@ int gl_pggan_l2_grad_z(gl_pggan *g, const float *z_dev, const uint8_t *target_u8
 }
 
 }  // extern "C"
+
+#ifdef GL_TUNING
+// One launch of one kernel of this file on device buffers that gl_tune_grad_op (gl_tune.hip) has put between guards: through the launchers
+// backward_pass uses.  ip[0] = images; fp[0]: the toRGB factor.  nb: the bytes of in[0 .. 3] and out[0 .. 1] (0 for a NULL slot); every buffer a
+// kernel touches must have exactly the size its shape gives.
+#define GL_TUNE_NEED(slot, bytes)                                                                                                              \
+    GL_REQUIRE(nb[slot] == (int64_t)(bytes), "%s: buffer %d (inputs 0 - 3, outputs 4 - 5) has %lld bytes, the shape needs %lld", __func__, slot, \
+               (long long)nb[slot], (long long)(bytes))
+int gl_tune_pggan_grad_op(gl_ctx *ctx, int op, const int64_t *ip, const int64_t *nb, const float *fp, void *const *in, void *const *out)
+{
+    hipStream_t st = ctx->stream;
+    const int64_t m = ip[0];
+    GL_REQUIRE(m > 0 && m <= 4096, "gl_tune_pggan_grad_op: images in 1..4096");
+    for (int k = 1; k <= 4; ++k) GL_REQUIRE(ip[k] >= 0 && ip[k] <= (1 << 20), "gl_tune_pggan_grad_op: argument %d out of range", k);
+    switch (op) {
+    case 0:   // pg_out_grad_kernel<false>: ip[1] = values per image, ip[2] = use_tanh; in = y, cot; out = g
+        GL_REQUIRE(ip[1] > 0, "gl_tune_pggan_grad_op: bad shape");
+        GL_TUNE_NEED(0, m * ip[1] * 4);
+        GL_TUNE_NEED(1, m * ip[1] * 4);
+        GL_TUNE_NEED(4, m * ip[1] * 4);
+        launch_out_grad(st, (const float *)in[0], (const float *)in[1], nullptr, m, (int)ip[1], (int)ip[2], (float *)out[0], nullptr);
+        break;
+    case 1:   // pg_out_grad_kernel<true>: in = y, target codes; out = g, loss [m]
+        GL_REQUIRE(ip[1] > 0, "gl_tune_pggan_grad_op: bad shape");
+        GL_TUNE_NEED(0, m * ip[1] * 4);
+        GL_TUNE_NEED(1, m * ip[1]);
+        GL_TUNE_NEED(4, m * ip[1] * 4);
+        GL_TUNE_NEED(5, m * 4);
+        launch_out_grad(st, (const float *)in[0], nullptr, (const uint8_t *)in[1], m, (int)ip[1], (int)ip[2], (float *)out[0], (float *)out[1]);
+        break;
+    case 2: { // pg_rgb_grad_kernel: ip[1..4] = H (grid of dA), C, nc, pool; in = g [m][nc][R][R] (R = H, or 2 H with pool), w [nc][C]; out = dA [m][H][H][C]
+        GL_REQUIRE(ip[1] > 0 && ip[2] > 0 && ip[3] > 0 && ip[3] <= 4, "gl_tune_pggan_grad_op: bad shape");
+        const int64_t R = ip[4] ? 2 * ip[1] : ip[1];
+        GL_TUNE_NEED(0, m * ip[3] * R * R * 4);
+        GL_TUNE_NEED(1, ip[3] * ip[2] * 4);
+        GL_TUNE_NEED(4, m * ip[1] * ip[1] * ip[2] * 4);
+        launch_rgb_grad(st, (const float *)in[0], (const float *)in[1], m, (int)ip[1], (int)ip[2], (int)ip[3], (int)ip[4], fp[0], (float *)out[0]);
+        break;
+    }
+    case 3: { // pg_pn_grad_kernel: ip[1..3] = H, C, pool; in = dA ([m][H][H][C], or on the 2H grid with pool), a, inv [m][H][H], extra or NULL; out = gpre chunks
+        GL_REQUIRE(ip[1] > 0 && ip[2] > 0 && ip[2] % 32 == 0, "gl_tune_pggan_grad_op: bad shape");
+        const int64_t bytes = m * ip[1] * ip[1] * ip[2] * 4;
+        GL_TUNE_NEED(0, ip[3] ? 4 * bytes : bytes);
+        GL_TUNE_NEED(1, bytes);
+        GL_TUNE_NEED(2, m * ip[1] * ip[1] * 4);
+        if (in[3]) GL_TUNE_NEED(3, bytes);
+        GL_TUNE_NEED(4, bytes);
+        launch_pn_grad(st, (const float *)in[0], (const float *)in[1], (const float *)in[2], (const float *)in[3], m, (int)ip[1], (int)ip[2], (int)ip[3],
+                       (float *)out[0]);
+        break;
+    }
+    case 4:   // pg_leaky_grad_kernel: ip[1] = K; in = dA, h [m][K]; out = [chunk][m][<= kGradK0]
+        GL_REQUIRE(ip[1] > 0, "gl_tune_pggan_grad_op: bad shape");
+        GL_TUNE_NEED(0, m * ip[1] * 4);
+        GL_TUNE_NEED(1, m * ip[1] * 4);
+        GL_TUNE_NEED(4, m * ip[1] * 4);
+        launch_leaky_grad(st, (const float *)in[0], (const float *)in[1], m, (int)ip[1], (float *)out[0]);
+        break;
+    case 5:   // pg_rowpn_grad_kernel, in place on out (which the caller has filled with d zn): ip[1] = d; in = z [m][d]
+        GL_REQUIRE(ip[1] > 0, "gl_tune_pggan_grad_op: bad shape");
+        GL_TUNE_NEED(0, m * ip[1] * 4);
+        GL_TUNE_NEED(4, m * ip[1] * 4);
+        launch_rowpn_grad(st, (const float *)in[0], m, (int)ip[1], (float *)out[0]);
+        break;
+    default:
+        gl_set_error("gl_tune_pggan_grad_op: unknown op %d", op);
+        return GL_ERR_INVALID;
+    }
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+#undef GL_TUNE_NEED
+#endif

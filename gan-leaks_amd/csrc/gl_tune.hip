@@ -575,3 +575,86 @@ extern "C" int gl_tune_attention_grad(gl_ctx *ctx, GlTuneAttentionGrad *q)
     cleanup();
     return GL_OK;
 }
+
+// gl_tune_grad_op: ONE launch of one element-wise or per-position kernel of the white-box backward passes (csrc/gl_dcgan_grad.hip, gl_pggan_grad.hip,
+// gl_lpips_grad.hip) on plain host arrays, for tests/test_gpu_grad_kernels.py.  family 0 / 1 / 2 names the file, `op` the kernel and ip / f0 its
+// arguments as the file's launcher at its end lists them; the launch goes through the function the production pass calls, so the grid, its cap and the
+// template instance are the production ones.  Every input given sits between 4 KiB guards of `poison` (fp32 values); every output is pre-filled with
+// `sentinel` bytes and sits between 4 KiB sentinel guards, which come back.  copy_in >= 0: out[0] starts as a copy of that input (a kernel that works
+// in place).  A NULL input or output slot reaches the kernel as NULL.
+struct GlTuneGradOp {                    // mirrored field by field in tests/grad_kernels_common.py
+    int32_t family, op;
+    int32_t sentinel, copy_in;
+    float poison, f0;
+    int64_t ip[12];
+    const void *in[4];
+    int64_t in_bytes[4];
+    void *out[2];                        // <- out_bytes[k] bytes each
+    int64_t out_bytes[2];
+    void *out_guards;                    // <- 4 * 4096 bytes: below | above out[0], below | above out[1]
+};
+static_assert(sizeof(GlTuneGradOp) == 224 && offsetof(GlTuneGradOp, ip) == 24 && offsetof(GlTuneGradOp, in) == 120 && offsetof(GlTuneGradOp, in_bytes) == 152 &&
+                  offsetof(GlTuneGradOp, out) == 184 && offsetof(GlTuneGradOp, out_bytes) == 200 && offsetof(GlTuneGradOp, out_guards) == 216,
+              "GlTuneGradOp: tests/grad_kernels_common.py mirrors this layout");
+
+// nb: the bytes of in[0 .. 3] and out[0 .. 1], 0 for a NULL slot: each file checks them against the shapes in ip before it launches
+int gl_tune_dcgan_grad_op(gl_ctx *ctx, int op, const int64_t *ip, const int64_t *nb, void *const *in, void *const *out);                       // gl_dcgan_grad.hip
+int gl_tune_pggan_grad_op(gl_ctx *ctx, int op, const int64_t *ip, const int64_t *nb, const float *fp, void *const *in, void *const *out);      // gl_pggan_grad.hip
+int gl_tune_lpips_grad_op(gl_ctx *ctx, int op, const int64_t *ip, const int64_t *nb, void *const *in, void *const *out);                       // gl_lpips_grad.hip
+
+extern "C" int gl_tune_grad_op(gl_ctx *ctx, GlTuneGradOp *q)
+{
+    GL_REQUIRE(ctx && q && q->out_guards && q->in[0] && q->out[0], "gl_tune_grad_op: NULL argument");
+    gl_make_current(ctx);
+    GL_REQUIRE(q->family >= 0 && q->family <= 2, "gl_tune_grad_op: family must be 0 (dcgan), 1 (pggan) or 2 (lpips)");
+    constexpr int64_t G = 4096, kMax = 256ll << 20;
+    for (int b = 0; b < 4; ++b) GL_REQUIRE(!q->in[b] || (q->in_bytes[b] > 0 && q->in_bytes[b] <= kMax), "gl_tune_grad_op: in_bytes[%d] out of range", b);
+    for (int b = 0; b < 2; ++b) GL_REQUIRE(!q->out[b] || (q->out_bytes[b] > 0 && q->out_bytes[b] <= kMax), "gl_tune_grad_op: out_bytes[%d] out of range", b);
+    GL_REQUIRE(q->copy_in < 4 && (q->copy_in < 0 || (q->in[q->copy_in] && q->in_bytes[q->copy_in] == q->out_bytes[0])),
+               "gl_tune_grad_op: copy_in names no input of out[0]'s size");
+    char *d_in[4] = {nullptr, nullptr, nullptr, nullptr}, *d_out[2] = {nullptr, nullptr};
+    auto cleanup = [&]() {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (int b = 0; b < 4; ++b) (void)hipFree(d_in[b]);
+        for (int b = 0; b < 2; ++b) (void)hipFree(d_out[b]);
+    };
+#define TUNE_HIP(e) do { if ((e) != hipSuccess) { gl_set_error("gl_tune_grad_op: %s failed", #e); cleanup(); return GL_ERR_HIP; } } while (0)
+#define TUNE_RC(e) do { const int rc_ = (e); if (rc_ != GL_OK) { cleanup(); return rc_; } } while (0)
+    std::vector<float> gf((size_t)(G / 4), q->poison);
+    void *k_in[4] = {nullptr, nullptr, nullptr, nullptr}, *k_out[2] = {nullptr, nullptr};
+    for (int b = 0; b < 4; ++b) {
+        if (!q->in[b]) continue;
+        TUNE_HIP(hipMalloc((void **)&d_in[b], (size_t)(q->in_bytes[b] + 2 * G)));
+        TUNE_HIP(hipMemcpy(d_in[b], gf.data(), (size_t)G, hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_in[b] + G, q->in[b], (size_t)q->in_bytes[b], hipMemcpyHostToDevice));
+        TUNE_HIP(hipMemcpy(d_in[b] + G + q->in_bytes[b], gf.data(), (size_t)G, hipMemcpyHostToDevice));
+        k_in[b] = d_in[b] + G;
+    }
+    for (int b = 0; b < 2; ++b) {
+        if (!q->out[b]) continue;
+        TUNE_HIP(hipMalloc((void **)&d_out[b], (size_t)(q->out_bytes[b] + 2 * G)));
+        TUNE_HIP(hipMemset(d_out[b], q->sentinel & 0xFF, (size_t)(q->out_bytes[b] + 2 * G)));
+        k_out[b] = d_out[b] + G;
+    }
+    if (q->copy_in >= 0) TUNE_HIP(hipMemcpy(d_out[0] + G, q->in[q->copy_in], (size_t)q->out_bytes[0], hipMemcpyHostToDevice));
+    TUNE_HIP(hipDeviceSynchronize());
+    int64_t nb[6];
+    for (int b = 0; b < 4; ++b) nb[b] = q->in[b] ? q->in_bytes[b] : 0;
+    for (int b = 0; b < 2; ++b) nb[4 + b] = q->out[b] ? q->out_bytes[b] : 0;
+    if (q->family == 0) TUNE_RC(gl_tune_dcgan_grad_op(ctx, q->op, q->ip, nb, k_in, k_out));
+    else if (q->family == 1) TUNE_RC(gl_tune_pggan_grad_op(ctx, q->op, q->ip, nb, &q->f0, k_in, k_out));
+    else TUNE_RC(gl_tune_lpips_grad_op(ctx, q->op, q->ip, nb, k_in, k_out));
+    TUNE_HIP(hipStreamSynchronize(ctx->stream));
+    std::memset(q->out_guards, q->sentinel & 0xFF, (size_t)(4 * G));
+    for (int b = 0; b < 2; ++b) {
+        if (!q->out[b]) continue;
+        char *og = reinterpret_cast<char *>(q->out_guards) + 2 * b * G;
+        TUNE_HIP(hipMemcpy(og, d_out[b], (size_t)G, hipMemcpyDeviceToHost));
+        TUNE_HIP(hipMemcpy(og + G, d_out[b] + G + q->out_bytes[b], (size_t)G, hipMemcpyDeviceToHost));
+        TUNE_HIP(hipMemcpy(q->out[b], d_out[b] + G, (size_t)q->out_bytes[b], hipMemcpyDeviceToHost));
+    }
+#undef TUNE_HIP
+#undef TUNE_RC
+    cleanup();
+    return GL_OK;
+}

@@ -96,6 +96,46 @@ def test_rows_do_not_depend_on_the_batch(synth, model):
         model.grad_image(y[:2], targets[:2], ref)
 
 
+def test_grid_stride_loops_wrap(synth, model):
+    """65 images at 64 x 64 in ONE pass: the wave-per-position kernels (conv1_1, the reference rows, the activation gradients, conv1_1 backwards)
+    are launched with at most 16384 workgroups of 4 waves and the max-pool with at most 4096 workgroups of 256 threads, one float4 each, so here
+    the second trip of their grid-stride loops runs.  Rows do not depend on the pass (above), so the same call in passes of 8 -- whose launches
+    stay under both caps -- must give the same bits; so must the reference rows"""
+    n, H, W = 65, 64, 64
+    import re
+    src = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gan-leaks_amd", "csrc", "gl_lpips_grad.hip")).read()
+    wb = src[src.index("unsigned wave_blocks("):]
+    wb = wb[:wb.index("\n}\n")]
+    mp = src[src.index("void launch_maxpool("):]
+    mp = mp[:mp.index("\n}\n")]
+    # the caps as the code under test has them: 16384 workgroups of 4 waves, 4096 workgroups of kThreads = 256 items
+    wave_cap = int(re.search(r"b > (\d+) \? \1 : b", wb).group(1)) * int(re.search(r"gl_ceil_div\(positions, (\d+)\)", wb).group(1))
+    pool_cap = int(re.search(r"if \(blocks > (\d+)\) blocks = \1;", mp).group(1)) * int(re.search(r"constexpr int kThreads = (\d+);", src).group(1))
+    keep_mib = int(re.search(r"kKeepBytes = (\d+)ull << 20", src).group(1))
+    assert (wave_cap, pool_cap) == (16384 * 4, 4096 * 256)     # what the sizes below were chosen for
+    kept = sum(h * h * c for h, c in ((64, 64), (64, 64), (32, 64), (32, 128), (32, 128), (16, 128), (16, 256), (16, 256), (16, 256), (8, 256),
+                                      (8, 512), (8, 512), (8, 512), (4, 512), (4, 512), (4, 512), (4, 512)))      # the 13 outputs and the 4 pools
+    assert n * kept * 4 < keep_mib << 20                       # the default pass holds all of them (kKeepBytes)
+    assert n * H * W > wave_cap and n * (H // 2) * (W // 2) > wave_cap       # conv1_1, conv1_2 and the first tap; conv2_x: 66 560 positions
+    assert n * (H // 2) * (W // 2) * (64 // 4) > pool_cap      # the first max-pool's float4 items
+    assert 8 * H * W <= wave_cap and 8 * (H // 2) * (W // 2) * (64 // 4) <= pool_cap
+    targets = np.ascontiguousarray(synth.lowpass_u8_images(8, n, res=64))
+    x = (2.0 * (targets.astype(np.float64) / 255.0) - 1.0).astype(np.float32)
+    y = np.clip(x + np.float32(0.1) * np.random.default_rng(13).standard_normal(x.shape).astype(np.float32), -1.0, 1.0).astype(np.float32)
+    together = _bits(model.grad_image(y, targets))
+    ref = model.reference_rows(targets).numpy().view(np.uint32)
+    try:
+        model.set_chunk(8)
+        chunked = _bits(model.grad_image(y, targets))
+        ref_chunked = model.reference_rows(targets).numpy().view(np.uint32)
+    finally:
+        model.set_chunk(0)
+    assert np.isfinite(together[0].view(np.float32)).all() and np.isfinite(together[1].view(np.float32)).all()
+    assert not np.array_equal(together[0][0], together[0][64])
+    assert np.array_equal(together[0], chunked[0]) and np.array_equal(together[1], chunked[1])
+    assert np.array_equal(ref, ref_chunked)
+
+
 def test_all_lin_weights_zero(gl, synth):
     """without LPIPS the loss is the L2 term and the gradient 2 (y - x) / (3 H W): a failure here is in the tail, not in VGG16.  x is the
     float32 value of 2 u / 255 - 1, as the device forms it (against the exact x the difference of two close floats would carry x's rounding,

@@ -121,6 +121,57 @@ def test_gradient_rows_do_not_depend_on_the_batch(gl, small):
         assert np.array_equal(bits(view.vjp_z(z[3:], cot[3:]))[k], vjp[k][3:])
 
 
+def gen_channels(s, in_channels=64):
+    """output channels of block s (model_torch.py: factors 1, 1, 1, 1, 1/2, 1/4, ... from the initial block on)"""
+    factors = [1, 1, 1, 1, 1 / 2, 1 / 4, 1 / 8, 1 / 16, 1 / 32]
+    return int(in_channels * factors[s + 1])
+
+
+def _source_constants(path, function):
+    """the integer literals of one function of a csrc file, and the file's kKeepBytes in MiB: the caps below are read from the code under test"""
+    import os
+    import re
+    text = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gan-leaks_amd", "csrc", path)).read()
+    body = text[text.index(function):]
+    body = body[:body.index("\n}\n")]
+    return body, int(re.search(r"kKeepBytes = (\d+)ull << 20", text).group(1))
+
+
+def test_grid_stride_loop_wraps(gl, small):
+    """17 images at 64 x 64 in ONE pass: pg_pn_grad_kernel is launched with at most 16384 workgroups of 4 waves, one wave per position, so at the two
+    64 x 64 layers the second trip of its loop runs.  Rows do not depend on the pass (above): passes of 4 stay under the cap and must give the
+    same bits"""
+    gen = small[0]
+    steps, n = 4, 17
+    R = 4 << steps
+    import re
+    body, keep_mib = _source_constants("gl_pggan_grad.hip", "void launch_pn_grad(")
+    blocks_cap = int(re.search(r"if \(blocks > (\d+)\) blocks = \1;", body).group(1))
+    per_block = int(re.search(r"gl_ceil_div\(positions, (\d+)\)", body).group(1))
+    wave_cap = blocks_cap * per_block                        # 16384 workgroups of 4 waves
+    assert n * R * R > wave_cap and 4 * R * R <= wave_cap
+    # the default pass holds all 17: grad_sizes() keeps hw^2 (C + 1) floats per layer -- two 4 x 4 layers of 64 channels, then two layers per block
+    widths = [64, 64] + [c for s in range(steps) for c in (gen_channels(s),) * 2]
+    grids = [4, 4] + [4 << (s + 1) for s in range(steps) for _ in (0, 1)]
+    kept = sum(h * h * (c + 1) for h, c in zip(grids, widths))
+    assert n * kept * 4 <= keep_mib << 20
+    view = gen.at(steps, 0.4)
+    rng = np.random.default_rng(65)
+    z = rng.standard_normal((n, 64)).astype(np.float32)
+    targets = view.generate_u8(rng.standard_normal((n, 64)).astype(np.float32)).numpy()
+    cot = rng.standard_normal((n, 3, R, R)).astype(np.float32)
+    bits = lambda pair: [a.numpy().view(np.uint32) for a in pair]        # noqa: E731
+    together, vjp = bits(view.l2_grad_z(z, targets)), bits(view.vjp_z(z, cot))
+    try:
+        gen.set_chunk(4)
+        chunked, vjp_chunked = bits(view.l2_grad_z(z, targets)), bits(view.vjp_z(z, cot))
+    finally:
+        gen.set_chunk(0)
+    assert np.isfinite(together[0].view(np.float32)).all() and not np.array_equal(together[0][0], together[0][16])
+    for k in (0, 1):
+        assert np.array_equal(chunked[k], together[k]) and np.array_equal(vjp_chunked[k], vjp[k])
+
+
 def test_search(gl, small):
     from ganleaks_amd.attack import _dist32
     gen = small[0]

@@ -21,3 +21,4 @@ from .attack import kde_coef, kde_loss, kde_scores, kde_sums  # noqa: F401
 from .attack import kde_cut_bits_rows, kde_sums_f32, pair_kde_scores  # noqa: F401
 from .pbb import pair_pbb_attack, pair_pbb_init_from_bank, pbb_attack, pbb_init_from_bank  # noqa: F401
 from .wb import pair_grad_z, pair_wb_attack, wb_attack  # noqa: F401
+from .recon import recon_attack, recon_latents  # noqa: F401

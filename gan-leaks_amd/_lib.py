@@ -109,6 +109,7 @@ SIGNATURES = {
     "gl_pbb_group_min": (_i, [_p, _p, _p, _i64, _i64, _i64, _p, _p, _p]),
     "gl_pbb_group_min_keys": (_i, [_p, _p, _i64, _i64, _i64, _p, _p]),
     "gl_pbb_accept": (_i, [_p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64, ctypes.c_float, ctypes.c_float, ctypes.c_float, ctypes.c_float, _p]),
+    "gl_recon_latents": (_i, [_p, _p, _p, _i64, _i64, _i64, ctypes.c_uint64, _i64, ctypes.c_float, _p]),
     "gl_wb_adam_step": (_i, [_p, _p, _p, _p, _p, _i64, _i64] + [ctypes.c_float] * 7),
     "gl_wb_diag_keys": (_i, [_p, _p, _i64, _i64, _p]),
     "gl_wb_lbfgs_push": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, _i64, _i64, _i64]),
@@ -156,6 +157,12 @@ SIGNATURES = {
     "gl_medgan_generate": (_i, [_p, _p, _i64, _p]),
     "gl_medgan_decode": (_i, [_p, _p, _i64, _p, _p]),
     "gl_medgan_codes": (_i, [_p, _p, _p, _i64, _p]),
+    "gl_vaegan_enc_create": (_i, [_p, _i, _i, _pp]),
+    "gl_vaegan_enc_destroy": (_i, [_p]),
+    "gl_vaegan_enc_set_chunk": (_i, [_p, _i64]),
+    "gl_vaegan_enc_set_conv": (_i, [_p, _i, _p, _p, _p, _p, _p, _p]),
+    "gl_vaegan_enc_set_head": (_i, [_p, _i, _p, _p, _p, _p, _p, _p, _p, _p]),
+    "gl_vaegan_enc_encode": (_i, [_p, _p, _p, _i64, _p, _p]),
     "gl_lpips_create": (_i, [_p, _pp]),
     "gl_lpips_destroy": (_i, [_p]),
     "gl_lpips_set_conv": (_i, [_p, _i, _p, _p]),
@@ -209,6 +216,12 @@ SIGNATURES = {
     "gl_comm_group_end": (_i, []),
 }
 
+# exports whose names carry an upper-case letter (S is the library's name for the exact sum of squared differences); the header check of
+# tests/test_abi.py collects lower-case names, so these are kept apart and checked by tests/test_vaegan_enc_cpu.py
+SIGNATURES_CASED = {
+    "gl_pbb_group_S": (_i, [_p, _p, _p, _i64, _i64, _i64, _p]),
+}
+
 _lib = None
 _lock = threading.Lock()
 
@@ -241,7 +254,7 @@ def load():
             except ImportError:
                 pass
         lib = ctypes.CDLL(LIB_PATH)
-        for name, (res, args) in SIGNATURES.items():
+        for name, (res, args) in list(SIGNATURES.items()) + list(SIGNATURES_CASED.items()):
             fn = getattr(lib, name)   # AttributeError if the export is missing
             fn.restype = res
             fn.argtypes = args

@@ -88,7 +88,7 @@ def parse_arguments(argv=None):
     """eval_roc.py:43-54 (same flags)"""
     parser = argparse.ArgumentParser()
     parser.add_argument('--result_load_dir', '-ldir', type=str, default=None, help='directory of the attack result')
-    parser.add_argument('--attack_type', type=str, choices=['fbb', 'pbb', 'wb'], help='type of the attack')
+    parser.add_argument('--attack_type', type=str, choices=['fbb', 'pbb', 'wb', 'recon'], help='type of the attack')
     parser.add_argument('--reference_load_dir', '-rdir', default=None, help='directory for the reference model result (optional)')
     parser.add_argument('--save_dir', '-sdir', type=bool, default=True, help='directory for saving the evaluation results (optional)')
     parser.add_argument("--wandb", default=None, help="accepted for compatibility; logging to WandB is not performed")

@@ -26,6 +26,9 @@ only improve on.
                          --pos_data_dir / --neg_data_dir name 2-D .npy tables of whole numbers (bank_io.load_rows); --resolution is not
                          consulted; the loss files hold fl32(S / F), S the number of differing columns; --pair_distance is refused (LPIPS is
                          defined on images)
+--encoder_path           VAEGAN only: the encoder's state dict (or a checkpoint dict with netE_state_dict).  The start is then the encoder's
+                         posterior mean of every query (ganleaks_amd.recon), not the nearest bank latent: no bank is read, and --noise_path
+                         and --num_init are not needed (and refused).  Exact l2 only
 --noise_path             the .npz the generate branches write under npz_noise/ (array `noise`): the latents of the sample bank
 --num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
 --BATCH_SIZE             only the first (N // BATCH_SIZE) * BATCH_SIZE latents take part in the start, as in fbb.py:77
@@ -62,7 +65,7 @@ from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, sa
 
 # options added after params.txt got its form: an unused one leaves the file as it was before the option existed
 LATER_OPTIONS = ("pair_distance",)
-VAEGAN_OPTIONS = ("sn_forwards",)        # the same: params.txt names K only where --gan vaegan gave it
+VAEGAN_OPTIONS = ("sn_forwards", "encoder_path")        # the same: params.txt names K and the encoder only where --gan vaegan gave them
 MEDGAN_OPTIONS = ("autoencoder_path", "input_size", "binary")        # and these only where --gan medgan gave them
 POWELL_OPTIONS = ("optimizer", "sweeps", "ladder", "step0")          # and these only where --optimizer was given (powell: what it ran with)
 
@@ -85,6 +88,8 @@ def parse_arguments(argv=None):
     parser.add_argument('--steps', type=int, default=4, help='pggan: resolution steps (4 * 2^steps pixels)')
     parser.add_argument('--alpha', type=float, default=1.0, help='pggan: fade-in weight of the last block')
     parser.add_argument('--sn_forwards', type=int, default=None, help='vaegan: hold the spectral-norm state of the K-th forward after loading; no default')
+    parser.add_argument('--encoder_path', type=str, default=None,
+                        help="vaegan: start from the encoder's posterior mean instead of the nearest bank latent (state dict, or a checkpoint with netE_state_dict)")
     parser.add_argument('--noise_path', type=str, default=None, help="npz with the bank's latents (array 'noise'), as the generate branches write it")
     parser.add_argument('--num_init', type=int, default=None, help='without --noise_path: draw this many starting latents')
     parser.add_argument('--init_seed', type=int, default=0, help='seed of the drawn starting latents')
@@ -143,7 +148,14 @@ def _request(args):
         raise SystemExit("--pair_distance l2-lpips needs a --resolution that is a multiple of 16 (VGG16 pools four times), got %s" % (args.resolution,))
     if getattr(args, "generator_path", None) is None:
         raise SystemExit("--generator_path is needed: the partial-black-box attacker holds the generator")
-    if (getattr(args, "noise_path", None) is None) == (getattr(args, "num_init", None) is None):
+    if getattr(args, "encoder_path", None) is not None:
+        if args.gan != "vaegan":
+            raise SystemExit("--encoder_path belongs to --gan vaegan (the family with an encoder), got --gan %s" % (args.gan,))
+        if pair is not None:
+            raise SystemExit("--encoder_path starts the exact-l2 search; with --pair_distance l2-lpips the start is the bank latent nearest under that distance")
+        if getattr(args, "noise_path", None) is not None or getattr(args, "num_init", None) is not None:
+            raise SystemExit("--encoder_path starts from the encoder's posterior mean: no bank is read, so --noise_path and --num_init do not apply")
+    elif (getattr(args, "noise_path", None) is None) == (getattr(args, "num_init", None) is None):
         raise SystemExit("give exactly one of --noise_path (the bank's latents) and --num_init (draw that many)")
     if args.num_init is not None and int(args.num_init) < 1:
         raise SystemExit("--num_init must be at least 1, got %s" % (args.num_init,))
@@ -248,6 +260,12 @@ def main(args):
     n_pos = len(pos_query_imgs)
 
     gen, kw, nz = load_generator(args)
+    if getattr(args, "encoder_path", None) is not None:
+        # the start is the encoder's (clamped) posterior mean of every query: no bank is read
+        from ..recon import recon_attack
+        from .recon import load_encoder
+        z_init = recon_attack(both, load_encoder(args.encoder_path, nz), gen, samples=0)[3]
+        return _main_l2(args, save_dir, both, n_pos, gen, kw, kind, z_init)
     if args.noise_path is not None:
         with np.load(args.noise_path) as data:
             z_bank = np.asarray(data["noise"], np.float32)
@@ -262,6 +280,11 @@ def main(args):
     if getattr(args, "pair_distance", None) is not None:
         return _main_pair(args, save_dir, both, n_pos, gen, kw, z_bank)
     z_init, _ = pbb_init_from_bank(both, gen, z_bank, batch_size=int(args.BATCH_SIZE), **kw)
+    return _main_l2(args, save_dir, both, n_pos, gen, kw, kind, z_init)
+
+
+def _main_l2(args, save_dir, both, n_pos, gen, kw, kind, z_init):
+    """the search on exact l2 from z_init, and its files"""
     dist, z_star, S, trace = pbb_attack(both, gen, z_init, rounds=int(args.rounds), population=int(args.population), sigma=float(args.sigma),
                                         seed=int(args.seed), history=True, **_optimizer_keywords(args), **kw)
     d = int(np.prod(both.shape[1:]))

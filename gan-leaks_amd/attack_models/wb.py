@@ -10,7 +10,7 @@ so that eval_roc.py scores the result unchanged.  The search is ganleaks_amd.wb.
            [--nz --ngf] [--noise_path npz | --num_init N --init_seed s] [--steps --lr --beta1 --beta2] [--BATCH_SIZE]
            [--optimizer {adam,lbfgs} [--memory m --ladder L --step0 s]]
     python -m ganleaks_amd.attack_models.wb ... --gan pggan --pg_steps N [--alpha a] [--in_channels C] --nz Z --resolution R ...
-    python -m ganleaks_amd.attack_models.wb ... --gan vaegan --sn_forwards K [--nz Z --ngf d]
+    python -m ganleaks_amd.attack_models.wb ... --gan vaegan --sn_forwards K [--nz Z --ngf d] [--encoder_path encoder.pth]
     python -m ganleaks_amd.attack_models.wb ... --pair_distance l2-lpips
 
 --gan, --generator_path  the generator class and its state dict (what the training scripts save as generator.pth)
@@ -20,6 +20,9 @@ so that eval_roc.py scores the result unchanged.  The search is ganleaks_amd.wb.
 --nz, --ngf              latent length and width (features_g)
 --pg_steps, --alpha, --in_channels   PGGAN only: the depth (images of 4 * 2^pg_steps pixels; no default, --steps is the descent's), the
                          fade-in weight of the last block (default 1) and the channel count of the first block (default 256)
+--encoder_path           VAEGAN only: the encoder's state dict (or a checkpoint dict with netE_state_dict).  The start is then the encoder's
+                         posterior mean of every query (ganleaks_amd.recon), not the nearest bank latent: no bank is read, and --noise_path
+                         and --num_init are not needed (and refused).  Exact l2 only
 --noise_path             the .npz the generate branches write under npz_noise/ (array `noise`): the latents of the sample bank
 --num_init, --init_seed  without --noise_path: that many standard-normal latents drawn from numpy's default_rng(init_seed)
 --BATCH_SIZE             only the first (N // BATCH_SIZE) * BATCH_SIZE latents take part in the start, as in fbb.py:77
@@ -55,7 +58,7 @@ from .fbb import update_args  # noqa: F401  (the YAML overlay of the command lin
 from .utils import check_folder, get_filepaths_from_dir, read_images_u8_nchw, save_files
 
 # options added after params.txt got its form: an unused one leaves the file as it was before the option existed
-LATER_OPTIONS = ("pg_steps", "alpha", "in_channels", "pair_distance", "sn_forwards", "optimizer", "memory", "ladder", "step0")
+LATER_OPTIONS = ("pg_steps", "alpha", "in_channels", "pair_distance", "sn_forwards", "optimizer", "memory", "ladder", "step0", "encoder_path")
 LBFGS_DEFAULTS = (("memory", 8), ("ladder", 8), ("step0", 1.0))
 PGGAN_OPTIONS = LATER_OPTIONS[:3]
 
@@ -81,6 +84,8 @@ def parse_arguments(argv=None):
     parser.add_argument('--alpha', type=float, default=None, help='pggan: fade-in weight of the last block (default 1)')
     parser.add_argument('--in_channels', type=int, default=None, help='pggan: channel count of the first block (default 256)')
     parser.add_argument('--sn_forwards', type=int, default=None, help='vaegan: hold the spectral-norm state of the K-th forward after loading; no default')
+    parser.add_argument('--encoder_path', type=str, default=None,
+                        help="vaegan: start from the encoder's posterior mean instead of the nearest bank latent (state dict, or a checkpoint with netE_state_dict)")
     parser.add_argument('--steps', type=int, default=64, help='gradient steps')
     parser.add_argument('--lr', type=float, default=0.05, help="Adam's step size")
     parser.add_argument('--beta1', type=float, default=0.9)
@@ -151,7 +156,14 @@ def _request(args):
                              % (kw["memory"], kw["ladder"], kw["step0"]))
     if getattr(args, "generator_path", None) is None:
         raise SystemExit("--generator_path is needed: the white-box attacker holds the generator")
-    if (getattr(args, "noise_path", None) is None) == (getattr(args, "num_init", None) is None):
+    if getattr(args, "encoder_path", None) is not None:
+        if args.gan != "vaegan":
+            raise SystemExit("--encoder_path belongs to --gan vaegan (the family with an encoder), got --gan %s" % (args.gan,))
+        if pair is not None:
+            raise SystemExit("--encoder_path starts the exact-l2 descent; with --pair_distance l2-lpips the start is the bank latent nearest under that distance")
+        if getattr(args, "noise_path", None) is not None or getattr(args, "num_init", None) is not None:
+            raise SystemExit("--encoder_path starts from the encoder's posterior mean: no bank is read, so --noise_path and --num_init do not apply")
+    elif (getattr(args, "noise_path", None) is None) == (getattr(args, "num_init", None) is None):
         raise SystemExit("give exactly one of --noise_path (the bank's latents) and --num_init (draw that many)")
     if args.num_init is not None and int(args.num_init) < 1:
         raise SystemExit("--num_init must be at least 1, got %s" % (args.num_init,))
@@ -199,6 +211,8 @@ def main(args):
     n_pos = len(pos_query_imgs)
 
     gen, nz = load_generator(args)
+    if getattr(args, "encoder_path", None) is not None:
+        return _main_l2(args, save_dir, both, n_pos, encoder_start(args, both, gen, nz))
     if args.noise_path is not None:
         with np.load(args.noise_path) as data:
             z_bank = np.asarray(data["noise"], np.float32)
@@ -213,6 +227,20 @@ def main(args):
     if getattr(args, "pair_distance", None) is not None:
         return _main_pair(args, save_dir, both, n_pos, gen, z_bank)
     z_init, _ = pbb_init_from_bank(both, gen, z_bank, batch_size=int(args.BATCH_SIZE))
+    return _main_l2(args, save_dir, both, n_pos, (gen, z_init))
+
+
+def encoder_start(args, both, gen, nz):
+    """--encoder_path: -> (gen, z_init), the start the encoder's (clamped) posterior mean of every query -- no bank is read"""
+    from ..recon import recon_attack
+    from .recon import load_encoder
+    enc = load_encoder(args.encoder_path, nz)
+    return gen, recon_attack(both, enc, gen, samples=0)[3]
+
+
+def _main_l2(args, save_dir, both, n_pos, start):
+    """the descent on exact l2 from the start (generator, z_init), and its files"""
+    gen, z_init = start
     dist, z_star, S, trace = wb_attack(both, gen, z_init, steps=int(args.steps), lr=float(args.lr), beta1=float(args.beta1), beta2=float(args.beta2),
                                        history=True, **_optimizer_keywords(args))
     d = int(np.prod(both.shape[1:]))

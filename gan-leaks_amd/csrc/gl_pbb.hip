@@ -65,6 +65,25 @@ __global__ void __launch_bounds__(kThreads) pbb_candidates_kernel(const float *_
     }
 }
 
+// the reconstruction attack's posterior draws: gl_pbb_candidates with a width per coordinate, round 0 of the same noise, and draw 0 the mean
+// itself.  out[(q * lambda + j) * nz + c] = clamp(fl32(mu[q][c] + fl32(std[q][c] * eps)), -z_max, z_max), eps = 0 for j = 0
+__global__ void __launch_bounds__(kThreads) recon_latents_kernel(const float *__restrict__ mu, const float *__restrict__ sd, int64_t nq, int nz, int lambda,
+                                                                 uint32_t k0, uint32_t k1, uint64_t query_base, float z_max, float *__restrict__ out)
+{
+    const int64_t total = nq * (int64_t)lambda * nz;
+    const int64_t stride = (int64_t)gridDim.x * blockDim.x;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += stride) {
+        const int64_t row = i / nz;
+        const int c = (int)(i - row * nz);
+        const int64_t q = row / lambda;
+        const int j = (int)(row - q * lambda);
+        const float eps = j ? pbb_noise(k0, k1, 0u, (uint32_t)(query_base + (uint64_t)q), (uint32_t)j, (uint32_t)c) : 0.0f;
+        const float step = sd[q * nz + c] * eps;
+        const float v = mu[q * nz + c] + step;
+        out[i] = fminf(fmaxf(v, -z_max), z_max);
+    }
+}
+
 // ---------------------------------------------------------------------------------------------------------------- grouped distance
 // Block (q, g): query q against candidates [g * GROUP, min(lambda, (g + 1) * GROUP)) of ITS lambda rows.  The query row goes through LDS in
 // chunks of KC bytes; each of the four waves owns PER_WAVE whole candidates and streams them with 16-byte loads, so one LDS read of the
@@ -92,9 +111,11 @@ __device__ __forceinline__ unsigned long long wave_sum(unsigned long long v)
 }
 
 // VEC: d % 16 == 0 and both base pointers 16-byte aligned, so every row starts on a 16-byte boundary.  Otherwise bytes, one per lane.
-template <bool VEC>
+// ALL (gl_pbb_group_S): the same sums, every S(q, j) stored to all_S[q * lambda + j] instead of the minimum; part is not touched.
+template <bool VEC, bool ALL = false>
 __global__ void __launch_bounds__(kThreads) pbb_group_min_kernel(const uint8_t *__restrict__ queries, const uint8_t *__restrict__ cand, int lambda,
-                                                                 int64_t d, pbb_partial *__restrict__ part, int64_t nq)
+                                                                 int64_t d, pbb_partial *__restrict__ part, int64_t nq,
+                                                                 unsigned long long *__restrict__ all_S = nullptr)
 {
     __shared__ __attribute__((aligned(16))) uint8_t qs[KC];
     __shared__ pbb_partial wave_best[WAVES];
@@ -171,9 +192,13 @@ __global__ void __launch_bounds__(kThreads) pbb_group_min_kernel(const uint8_t *
 #pragma unroll
         for (int i = 0; i < PER_WAVE; ++i) {
             const unsigned long long S = AA + wave_sum(bb[i]) - 2ull * wave_sum(ab[i]);
+            if constexpr (ALL) {
+                if (i < n_valid && lane == 0) all_S[q * (int64_t)lambda + j0 + i] = S;
+            }
             if (i < n_valid && S < best.S) { best.S = S; best.j = j0 + i; }      // ascending j: strict < keeps the lower index on a tie
         }
     }
+    if constexpr (ALL) return;                         // no barrier below is needed: every S has been stored by its own wave
     if (lane == 0) wave_best[wave] = best;
     __syncthreads();
     if (threadIdx.x == 0) {
@@ -299,12 +324,62 @@ int gl_pbb_group_min(gl_ctx *ctx, const uint8_t *queries_u8_dev, const uint8_t *
     pbb_partial *part = reinterpret_cast<pbb_partial *>(workspace_dev);
     const dim3 grid((unsigned)nq, (unsigned)groups);
     if (vec)
-        hipLaunchKernelGGL(pbb_group_min_kernel<true>, grid, dim3(kThreads), 0, ctx->stream, queries_u8_dev, cand_u8_dev, (int)lambda, d, part, nq);
+        hipLaunchKernelGGL((pbb_group_min_kernel<true, false>), grid, dim3(kThreads), 0, ctx->stream, queries_u8_dev, cand_u8_dev, (int)lambda, d, part, nq,
+                           (unsigned long long *)nullptr);
     else
-        hipLaunchKernelGGL(pbb_group_min_kernel<false>, grid, dim3(kThreads), 0, ctx->stream, queries_u8_dev, cand_u8_dev, (int)lambda, d, part, nq);
+        hipLaunchKernelGGL((pbb_group_min_kernel<false, false>), grid, dim3(kThreads), 0, ctx->stream, queries_u8_dev, cand_u8_dev, (int)lambda, d, part, nq,
+                           (unsigned long long *)nullptr);
     GL_LAUNCH_CHECK();
     hipLaunchKernelGGL(pbb_combine_kernel, dim3((unsigned)gl_ceil_div(nq, kThreads)), dim3(kThreads), 0, ctx->stream, part, nq, (int)groups,
                        reinterpret_cast<unsigned long long *>(out_S_dev), out_j_dev);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_pbb_group_S(gl_ctx *ctx, const uint8_t *queries_u8_dev, const uint8_t *cand_u8_dev, int64_t nq, int64_t lambda, int64_t d, uint64_t *out_S_dev)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx, "gl_pbb_group_S: NULL ctx");
+    GL_REQUIRE(nq >= 0 && nq < (1ll << 31) && lambda >= 1 && d > 0 && d <= GL_L2_WIDE_MAX_D, "gl_pbb_group_S: bad sizes nq=%lld lambda=%lld d=%lld (d <= %lld)",
+               (long long)nq, (long long)lambda, (long long)d, (long long)GL_L2_WIDE_MAX_D);
+    const int64_t groups = gl_ceil_div(lambda, GROUP);
+    GL_REQUIRE(groups <= 65535, "gl_pbb_group_S: lambda=%lld exceeds %d candidates per query", (long long)lambda, 65535 * GROUP);
+    if (nq == 0) return GL_OK;
+    GL_REQUIRE(nq <= INT64_MAX / lambda / d, "gl_pbb_group_S: nq * lambda * d overflows");
+    GL_REQUIRE(queries_u8_dev && cand_u8_dev && out_S_dev, "gl_pbb_group_S: NULL device pointer");
+    GL_REQUIRE((reinterpret_cast<uintptr_t>(out_S_dev) & 7) == 0, "gl_pbb_group_S: out_S_dev must be 8-byte aligned");
+    const bool vec = (d & 15) == 0 && ((reinterpret_cast<uintptr_t>(queries_u8_dev) | reinterpret_cast<uintptr_t>(cand_u8_dev)) & 15) == 0;
+    unsigned long long *out = reinterpret_cast<unsigned long long *>(out_S_dev);
+    const dim3 grid((unsigned)nq, (unsigned)groups);
+    if (vec)
+        hipLaunchKernelGGL((pbb_group_min_kernel<true, true>), grid, dim3(kThreads), 0, ctx->stream, queries_u8_dev, cand_u8_dev, (int)lambda, d,
+                           (pbb_partial *)nullptr, nq, out);
+    else
+        hipLaunchKernelGGL((pbb_group_min_kernel<false, true>), grid, dim3(kThreads), 0, ctx->stream, queries_u8_dev, cand_u8_dev, (int)lambda, d,
+                           (pbb_partial *)nullptr, nq, out);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+int gl_recon_latents(gl_ctx *ctx, const float *mu_dev, const float *std_dev, int64_t nq, int64_t nz, int64_t lambda, uint64_t seed, int64_t query_base,
+                     float z_max, float *out_dev)
+{
+    gl_make_current(ctx);
+    GL_REQUIRE(ctx, "gl_recon_latents: NULL ctx");
+    GL_REQUIRE(nq >= 0 && nz >= 1 && nz < (1ll << 31) && lambda >= 1 && lambda < (1ll << 31), "gl_recon_latents: bad sizes nq=%lld nz=%lld lambda=%lld",
+               (long long)nq, (long long)nz, (long long)lambda);
+    GL_REQUIRE(query_base >= 0 && nq <= (1ll << 32) && query_base <= (1ll << 32) - nq,
+               "gl_recon_latents: query_base + nq = %lld + %lld exceeds 2^32 (the noise counter holds 32 bits of the query index)", (long long)query_base,
+               (long long)nq);
+    GL_REQUIRE(finite_f(z_max) && z_max > 0.0f, "gl_recon_latents: z_max must be finite and positive");
+    if (nq == 0) return GL_OK;
+    GL_REQUIRE(nq <= INT64_MAX / lambda / nz, "gl_recon_latents: nq * lambda * nz overflows");
+    GL_REQUIRE(mu_dev && std_dev && out_dev, "gl_recon_latents: NULL device pointer");
+    const int64_t total = nq * lambda * nz;
+    int64_t blocks = gl_ceil_div(total, kThreads);
+    if (blocks > 65536) blocks = 65536;
+    hipLaunchKernelGGL(recon_latents_kernel, dim3((unsigned)blocks), dim3(kThreads), 0, ctx->stream, mu_dev, std_dev, nq, (int)nz, (int)lambda,
+                       (uint32_t)(seed & 0xffffffffull), (uint32_t)(seed >> 32), (uint64_t)query_base, z_max, out_dev);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }

@@ -1,6 +1,6 @@
 """Counterpart of the `Generator` class of the reference's gan_models/vaegan/train.py:109-135 (with `SpectralNorm`
-and `SelfAttention` from gan_models/vaegan/ops.py:23-75,86-120) for inference.  Encoder, discriminators and
-training are out of scope.
+and `SelfAttention` from gan_models/vaegan/ops.py:23-75,86-120) and of its `Encoder` class (train.py:61-106), for inference.
+Discriminators and training are out of scope.
 
     Generator(z_dim, d=64)(x[N,z_dim,1,1]) -> [N,3,64,64]
     4 x [SpectralNorm(ConvTranspose2d + bias) -> BatchNorm2d -> ReLU], SelfAttention after the third, ConvTranspose2d -> tanh
@@ -13,6 +13,10 @@ ConvTranspose bias and BatchNorm(eval) into the convolution epilogue and runs th
 
 `Generator.frozen(k)` -> `FrozenGenerator`: the same generator with the state of its k-th next forward held for good, a fixed function of z
 with gradients with respect to z -- what the partial-black-box and the white-box attack take (the plain Generator stays stateful and refused).
+
+    Encoder(z_dim, d=64).encode(x[N,3,64,64]) -> (z_mu, z_var) [N,z_dim]
+    4 x [Conv2d(k4, s2, p1) -> BatchNorm2d -> ReLU], then two heads Linear(8192, 4 z) -> BatchNorm1d -> ReLU -> Linear(4 z, z)
+on the HIP encoder (csrc/gl_vaegan_enc.hip): what the reconstruction attack (recon.py) and `--encoder_path` of pbb.py / wb.py read.
 """
 from __future__ import annotations
 
@@ -20,7 +24,7 @@ import ctypes
 
 import numpy as np
 
-from ..._lib import Context, as_device, check
+from ..._lib import Context, DeviceArray, as_device, check
 
 _p = ctypes.c_void_p
 
@@ -310,3 +314,144 @@ class FrozenGenerator:
         grad, loss = self._ctx.empty((n, self.z_dim), np.float32), self._ctx.empty((n,), np.float32)
         check(self._ctx.lib.gl_dcgan_l2_grad_z(self._handle, _p(zd.ptr), _p(td.ptr), n, _p(grad.ptr), _p(loss.ptr)))
         return grad, loss
+
+
+ENCODER_BN = ("weight", "bias", "running_mean", "running_var")
+
+
+def encoder_keys(z_dim, d=64):
+    """{key: shape} of the reference's Encoder(z_dim, d).state_dict() (train.py:61-85)"""
+    ch = [3, d, 2 * d, 4 * d, 8 * d]
+    keys = {}
+    for l in range(4):
+        keys["cv%d.weight" % (l + 1)] = (ch[l + 1], ch[l], 4, 4)
+        keys["cv%d.bias" % (l + 1)] = (ch[l + 1],)
+        for k in ENCODER_BN:
+            keys["bn%d.%s" % (l + 1, k)] = (ch[l + 1],)
+        keys["bn%d.num_batches_tracked" % (l + 1)] = ()
+    for fc, bn in (("fc1", "bn6"), ("fc2", "bn7")):
+        keys[fc + ".weight"] = (4 * z_dim, 512 * 4 * 4)
+        keys[fc + ".bias"] = (4 * z_dim,)
+        keys[fc + "_1.weight"] = (z_dim, 4 * z_dim)
+        keys[fc + "_1.bias"] = (z_dim,)
+        for k in ENCODER_BN:
+            keys["%s.%s" % (bn, k)] = (4 * z_dim,)
+        keys[bn + ".num_batches_tracked"] = ()
+    return keys
+
+
+class Encoder:
+    """The reference's Encoder (train.py:61-106) for inference: encode(x) = (z_mu, z_var) of images x [N,3,64,64], BatchNorm in eval mode.
+    d must be 64: the reference hard-wires 512 * 4 * 4 inputs to the heads, so no other width loads.  x: uint8 images, or float32 values (the
+    reference feeds 2 u / 255 - 1); a byte u is read as float32(2 * (u / 255.) - 1), the library's 8-bit lattice, so both give the same bits on it."""
+    image_shape = (3, 64, 64)
+
+    def __init__(self, z_dim, d=64, ctx=None):
+        self.z_dim, self.d = int(z_dim), int(d)
+        if self.d != 64:
+            raise ValueError("Encoder: d must be 64, got %r: the reference hard-wires 512 * 4 * 4 inputs to the encoder's heads "
+                             "(gan_models/vaegan/train.py:79,83), so no other width loads" % (d,))
+        if not 1 <= self.z_dim <= 4096:
+            raise ValueError("Encoder: z_dim must be in 1..4096, got %r" % (z_dim,))
+        self._ctx = ctx
+        self._handle = None
+        self._loaded = False
+
+    @property
+    def ctx(self):
+        if self._ctx is None:
+            self._ctx = Context.get()
+        return self._ctx
+
+    def _ensure(self):
+        if self._handle is None:
+            h = _p()
+            check(self.ctx.lib.gl_vaegan_enc_create(self.ctx.handle, self.z_dim, self.d, ctypes.byref(h)))
+            self._handle = h
+        return self._handle
+
+    def __del__(self):
+        if getattr(self, "_handle", None) is not None:
+            try:
+                self.ctx.lib.gl_vaegan_enc_destroy(self._handle)
+            except Exception:  # noqa: BLE001
+                pass
+
+    def load_state_dict(self, sd, strict=True):
+        """the reference's keys (encoder_keys); a missing key raises KeyError, a wrong shape ValueError naming the key; with strict, a key the
+        reference's Encoder does not have raises KeyError as well.  num_batches_tracked is required and not used (eval mode)."""
+        want = encoder_keys(self.z_dim, self.d)
+        arrays = {}
+        for key, shape in want.items():
+            if key not in sd:
+                raise KeyError("Encoder.load_state_dict: missing key %r" % key)
+            if key.endswith("num_batches_tracked"):
+                continue
+            a = _np(sd[key])
+            if a.shape != shape:
+                raise ValueError("Encoder.load_state_dict: %s has shape %s, expected %s" % (key, a.shape, shape))
+            arrays[key] = a
+        if strict:
+            extra = sorted(k for k in sd if k not in want)
+            if extra:
+                raise KeyError("Encoder.load_state_dict: unexpected key(s) %s" % ", ".join(repr(k) for k in extra))
+        lib, h = self.ctx.lib, self._ensure()
+        ptr = lambda key: arrays[key].ctypes.data_as(_p)   # noqa: E731
+        for l in range(4):
+            cv, bn = "cv%d" % (l + 1), "bn%d" % (l + 1)
+            check(lib.gl_vaegan_enc_set_conv(h, l, ptr(cv + ".weight"), ptr(cv + ".bias"), *[ptr("%s.%s" % (bn, k)) for k in ENCODER_BN]))
+        for i, (fc, bn) in enumerate((("fc1", "bn6"), ("fc2", "bn7"))):
+            check(lib.gl_vaegan_enc_set_head(h, i, ptr(fc + ".weight"), ptr(fc + ".bias"), *[ptr("%s.%s" % (bn, k)) for k in ENCODER_BN],
+                                             ptr(fc + "_1.weight"), ptr(fc + "_1.bias")))
+        self._loaded = True
+        return "<All keys matched successfully>"
+
+    def eval(self):
+        return self
+
+    def to(self, *a, **k):
+        return self
+
+    def cuda(self, *a, **k):
+        return self
+
+    def train(self, mode=True):              # inference only: BatchNorm always uses its running statistics
+        return self
+
+    def set_chunk(self, images_per_pass):
+        """images per pass on the device (0 = the default); results do not depend on it"""
+        check(self.ctx.lib.gl_vaegan_enc_set_chunk(self._ensure(), int(images_per_pass)))
+
+    def encode_device(self, x):
+        """x [N,3,64,64]: uint8 or float32, numpy / torch / DeviceArray -> (mu, logvar) float32 DeviceArrays [N, z_dim].  Before the weights
+        are loaded the library refuses (GL_ERR_STATE) and names the missing part."""
+        if not isinstance(x, DeviceArray) and not type(x).__module__.startswith("torch"):
+            x = np.asarray(x)
+            if x.dtype != np.uint8:
+                x = x.astype(np.float32, copy=False)
+        xd = as_device(self.ctx, x)
+        if xd.dtype not in (np.dtype(np.uint8), np.dtype(np.float32)):
+            raise TypeError("Encoder: images must be uint8 or float32, got %s" % xd.dtype)
+        if tuple(xd.shape[1:]) != self.image_shape:
+            raise ValueError("Encoder: expected images of shape [N,3,64,64], got %s" % (xd.shape,))
+        n = xd.shape[0]
+        mu, logvar = self.ctx.empty((n, self.z_dim), np.float32), self.ctx.empty((n, self.z_dim), np.float32)
+        u8 = xd.dtype == np.dtype(np.uint8)
+        check(self.ctx.lib.gl_vaegan_enc_encode(self._ensure(), _p(xd.ptr if u8 else 0), _p(0 if u8 else xd.ptr), n, _p(mu.ptr), _p(logvar.ptr)))
+        return mu, logvar
+
+    def encode(self, x):
+        """-> (z_mu, z_var) float32 numpy arrays [N, z_dim] (the reference's names: z_var is what reparametrize calls logvar)"""
+        mu, logvar = self.encode_device(x)
+        return mu.numpy(), logvar.numpy()
+
+    def forward(self, x, seed=0, query_base=0):
+        """the reference's forward is reparametrize(encode(x)) = mu + exp(logvar) * eps with eps from torch's RNG stream.  That stream is NOT
+        reproduced: eps here is the library's counter-based noise, draw j = 1 of recon_latents(mu, logvar, 1, seed, query_base), clamped to
+        [-4, 4] like every latent the attacks draw.  -> float32 [N, z_dim]"""
+        from ...recon import recon_latents
+        mu, logvar = self.encode(x)
+        z = recon_latents(mu, logvar, 1, seed=seed, query_base=query_base, ctx=self.ctx).numpy()
+        return np.ascontiguousarray(z.reshape(len(mu), 2, self.z_dim)[:, 1])
+
+    __call__ = forward

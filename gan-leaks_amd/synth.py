@@ -217,3 +217,42 @@ def vaegan_state_dict(seed=777, z_dim=100, d=64):
         sd["sa1.%s_conv.bias" % n] = rng.normal(0.0, 0.1, size=co).astype(np.float32)
     sd["sa1.gamma"] = np.array([0.7], np.float32)
     return sd
+
+
+def vaegan_encoder_state_dict(seed=778, z_dim=100, d=64):
+    """Random VAEGAN encoder weights under the reference's key names (gan_models/vaegan/train.py:61-85): cv{1..4}.{weight [Co,Ci,4,4], bias},
+    bn{1..4}.* (BatchNorm2d), fc{1,2}.{weight [4 z, 8192], bias}, bn{6,7}.* (BatchNorm1d), fc{1,2}_1.{weight [z, 4 z], bias}.  He-scaled
+    weights keep activations O(1) through the stack; BN statistics are randomised so that folding them is exercised."""
+    rng = np.random.default_rng(seed)
+    ch = [3, d, 2 * d, 4 * d, 8 * d]
+    sd = {}
+
+    def bn(name, n):
+        sd[name + ".weight"] = rng.normal(1.0, 0.1, size=n).astype(np.float32)
+        sd[name + ".bias"] = rng.normal(0.0, 0.1, size=n).astype(np.float32)
+        sd[name + ".running_mean"] = rng.normal(0.0, 0.1, size=n).astype(np.float32)
+        sd[name + ".running_var"] = rng.uniform(0.5, 1.5, size=n).astype(np.float32)
+        sd[name + ".num_batches_tracked"] = np.array(1, np.int64)
+
+    for l in range(4):
+        cin, cout = ch[l], ch[l + 1]
+        sd["cv%d.weight" % (l + 1)] = rng.normal(0.0, np.sqrt(2.0 / (cin * 16)), size=(cout, cin, 4, 4)).astype(np.float32)
+        sd["cv%d.bias" % (l + 1)] = rng.normal(0.0, 0.05, size=cout).astype(np.float32)
+        bn("bn%d" % (l + 1), cout)
+    flat, hid = 8 * d * 16, 4 * z_dim
+    for fc, b in (("fc1", "bn6"), ("fc2", "bn7")):
+        sd[fc + ".weight"] = rng.normal(0.0, np.sqrt(2.0 / flat), size=(hid, flat)).astype(np.float32)
+        sd[fc + ".bias"] = rng.normal(0.0, 0.05, size=hid).astype(np.float32)
+        bn(b, hid)
+        sd[fc + "_1.weight"] = rng.normal(0.0, np.sqrt(2.0 / hid), size=(z_dim, hid)).astype(np.float32)
+        sd[fc + "_1.bias"] = rng.normal(0.0, 0.1, size=z_dim).astype(np.float32)
+    return sd
+
+
+def vaegan_encoder_images(seed=779, n=8):
+    """u8 images [n,3,64,64] for the encoder's fixtures: structured images, the last two all 255 (+1) and all 0 (-1), which make an error in
+    the zero padding visible"""
+    x = lowpass_u8_images(seed, n, 64)
+    x[n - 2] = 255
+    x[n - 1] = 0
+    return x

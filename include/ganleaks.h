@@ -43,6 +43,7 @@ typedef struct gl_dcgan gl_dcgan;   /* opaque: packed DCGAN / WGAN-GP generator 
 typedef struct gl_lpips gl_lpips;   /* opaque: VGG16 + LPIPS v0.1 lin layers */
 typedef struct gl_pggan gl_pggan;   /* opaque: packed progressive-GAN generator */
 typedef struct gl_medgan gl_medgan; /* opaque: medGAN residual-MLP generator + autoencoder decoder */
+typedef struct gl_vaegan_enc gl_vaegan_enc; /* opaque: VAEGAN encoder (four strided convolutions + two heads) */
 typedef struct gl_comm gl_comm;     /* opaque: one rank of an RCCL communicator, bound to a gl_ctx */
 
 /* ---------------------------------------------------------------- library / context */
@@ -388,6 +389,25 @@ int gl_pbb_accept(gl_ctx *ctx, float *z_dev, float *sigma_dev, uint64_t *S_cur_d
                   const int32_t *j_new_dev, int64_t nq, int64_t nz, int64_t lambda, float up, float down, float sigma_min, float sigma_max,
                   uint8_t *accepted_dev);
 
+/* ---------------------------------------------------------------- reconstruction attack (VAE-type models)
+ * The second attack of Hilprecht et al. (the paper of the Monte-Carlo attacks): the attacker holds the whole VAEGAN and scores a query x by how
+ * well the model reconstructs it, |x - G(z)| for z at the encoder's posterior mean and over draws from the posterior.  A block of queries is
+ * gl_vaegan_enc_encode -> gl_recon_latents -> the generator on all nq * lambda latents -> gl_pbb_group_S.  Both calls below follow the
+ * conventions of the partial-black-box calls: the context's stream, no synchronisation, GL_OK for nq == 0, no tuning variable, no atomics. */
+/* out[(q * lambda + j) * nz + c] = clamp(fl32(mu[q * nz + c] + fl32(std[q * nz + c] * eps)), -z_max, z_max), each operation rounded on its own
+ * (no fma): gl_pbb_candidates with a width per coordinate.  eps = 0 for j = 0, so row 0 of every query is the clamped mean itself; for j >= 1
+ * eps = eps(seed, round = 0, query_base + q, j, c), the noise gl_pbb_candidates documents above.  mu_dev, std_dev [nq][nz], out_dev
+ * [nq * lambda][nz], fp32; lambda = draws + 1.  std is an input: the caller computes it on the host (float32 exp), which keeps a device expf
+ * out of the contract.  NOTE the reference's quirk: Encoder.reparametrize (gan_models/vaegan/train.py:98-101) computes
+ * std = logvar.mul(1.0).exp_(), that is exp(logvar) and not exp(logvar / 2); callers that follow the reference pass exp(logvar). */
+int gl_recon_latents(gl_ctx *ctx, const float *mu_dev, const float *std_dev, int64_t nq, int64_t nz, int64_t lambda, uint64_t seed, int64_t query_base,
+                     float z_max, float *out_dev);
+/* gl_pbb_group_min's sibling that keeps every value: out_S_dev[q * lambda + j] = S(q, j) = sum_k (queries[q][k] - cand[q * lambda + j][k])^2,
+ * the exact integer, uint64 (8-byte aligned).  The same kernel body and the same constraints (any d >= 1, byte loads where d is no multiple of
+ * 16 or a base pointer is not 16-byte aligned, 64-bit totals), so for a table generator's 0 / 1 rows it counts what gl_pbb_group_min counts.
+ * No workspace: every wave stores the S of its own candidates. */
+int gl_pbb_group_S(gl_ctx *ctx, const uint8_t *queries_u8_dev, const uint8_t *cand_u8_dev, int64_t nq, int64_t lambda, int64_t d, uint64_t *out_S_dev);
+
 /* ---------------------------------------------------------------- white-box attack: gradient descent on the latent
  * GAN-Leaks' third attack (section 5.4 of the paper): z* = argmin_z L(x, G(z)) by gradient descent with the generator's weights in hand.
  * A step is gl_dcgan_l2_grad_z -> gl_wb_adam_step -> the generator's 8-bit images of the new iterate -> gl_pbb_group_min (lambda = 1) ->
@@ -660,6 +680,31 @@ int gl_medgan_decode(gl_medgan *g, const float *hidden_dev, int64_t n, float *de
  * gl_medgan_codes: codes_u8_dev [n][input_size] = (gl_medgan_decode(dec, gl_medgan_generate(gen, z)) >= 0.5) as bytes 0 / 1 -- the rows the
  * generate branch writes, through the forward's own launches, so bit for bit what gl_medgan_decode's binary_dev holds. */
 int gl_medgan_codes(gl_medgan *gen, gl_medgan *dec, const float *z_dev, int64_t n, uint8_t *codes_u8_dev);
+
+/* ---------------------------------------------------------------- VAEGAN encoder (csrc/gl_vaegan_enc.hip) */
+/* gan_models/vaegan/train.py:61-96 Encoder(z_dim, d).encode for inference: four Conv2d(k4, s2, p1) + BatchNorm2d + ReLU (3 -> 64 -> 128 ->
+ * 256 -> 512 channels, 64 x 64 -> 4 x 4) and two heads Linear(8192, 4 z) + BatchNorm1d + ReLU + Linear(4 z, z).  d must be 64: the reference
+ * hard-wires 512 * 4 * 4 inputs to the heads (train.py:79,83), so nothing else loads; 1 <= z_dim <= 4096.
+ * Arithmetic: BatchNorm in eval mode with eps 1e-5, folded on the host in double together with the bias, y = s (conv + b - mean) + beta,
+ * s = gamma / sqrt(var + eps); fp32 products; every output is one sum in a fixed order that depends on its own image alone, not on the images
+ * that share a call or a pass (no atomics, no split K).  A byte u is read as fl32(2 * (u / 255.) - 1) with the expression in float64 -- the lattice of
+ * gl_decode_u8 / gl_encode_lattice_f32 --, so the u8 path gives bit for bit what the f32 path gives for those values.  Zero padding pads each layer's input. */
+int gl_vaegan_enc_create(gl_ctx *ctx, int z_dim, int d, gl_vaegan_enc **out);
+int gl_vaegan_enc_destroy(gl_vaegan_enc *e);
+/* images per pass of gl_vaegan_enc_encode (0 = the default, 512: 384 KiB of activations per image); results do not depend on it */
+int gl_vaegan_enc_set_chunk(gl_vaegan_enc *e, int64_t images_per_pass);
+/* layer 0..3 = cv1 / bn1 .. cv4 / bn4: w_host [Co][Ci][4][4], bias_host [Co], the BatchNorm2d vectors [Co] */
+int gl_vaegan_enc_set_conv(gl_vaegan_enc *e, int layer, const float *w_host, const float *bias_host, const float *bn_weight_host, const float *bn_bias_host,
+                           const float *bn_running_mean_host, const float *bn_running_var_host);
+/* head 0 = fc1 / bn6 / fc1_1 (z_mu), head 1 = fc2 / bn7 / fc2_1 (z_var): fc_w_host [4 z][8192] in the reference's layout (ChannelsToLinear
+ * flattens NCHW: column c * 16 + y * 4 + x; repacked here), fc_b_host and the BatchNorm1d vectors [4 z], out_w_host [z][4 z], out_b_host [z] */
+int gl_vaegan_enc_set_head(gl_vaegan_enc *e, int head, const float *fc_w_host, const float *fc_b_host, const float *bn_weight_host,
+                           const float *bn_bias_host, const float *bn_running_mean_host, const float *bn_running_var_host, const float *out_w_host,
+                           const float *out_b_host);
+/* images [n][3][64][64], exactly one of images_u8_dev / images_f32_dev non-NULL -> mu_dev, logvar_dev [n][z_dim] fp32 (the reference's z_mu
+ * and z_var).  GL_ERR_STATE, naming the missing part, before all six parts are loaded; n == 0 returns GL_OK and touches nothing.  On the
+ * context's stream, no synchronisation (the first call, and a call with more images per pass than any before, allocate the workspace). */
+int gl_vaegan_enc_encode(gl_vaegan_enc *e, const uint8_t *images_u8_dev, const float *images_f32_dev, int64_t n, float *mu_dev, float *logvar_dev);
 
 /* ---------------------------------------------------------------- LPIPS (0.2 * LPIPS + L2, the reference's fbb distance) */
 /* PerceptualLoss(model='net-lin', net='vgg') (attack_models/lpips_pytorch/__init__.py:9-32) -> PNetLin
